@@ -7,7 +7,17 @@ One STEP = one bfir_engine_run_device call over `--blocks` consecutive blocks
 of input that is already resident in HBM (generated there).  Metric: output
 channel-samples/s.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints one JSON line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, config).  Everything
+else the benchmark measures or checks runs only with --full (below).
+
+--dump-outputs DIR writes what the last timed step left in the output buffer, as
+DIR/output.npy (float32 or float64 frames, shape (blocks, L, C)): a fixed sample
+of at most 32 MiB of rank 0's engine-blocks, drawn with numpy default_rng(0),
+in ascending order.  The inputs depend on the arguments only, so two builds run
+with the same arguments can be compared output for output.
 
 N > 1: one process per GPU.  Under torch.distributed.run (WORLD_SIZE set) this
 process is one rank; started plainly with --gpus N it spawns the N ranks itself
@@ -20,7 +30,7 @@ process is one rank; started plainly with --gpus N it spawns the N ranks itself
 No rank ever exchanges audio with another; the only communication is the MAX /
 SUM reduction of the timing.
 
-The JSON line also carries
+With --full the JSON line also carries (the --no-* switches drop single items)
   roofline      per kernel: algorithmic HBM bytes / mean launch time (HIP events
                 on the launch stream, inside the timed region) against 8 TB/s, the
                 same from an untimed serial-schedule pass (*_exclusive), the
@@ -276,6 +286,12 @@ def parse_args(argv=None):
     ap.add_argument("--streams", type=int, default=0,
                     help="total independent engines dealt out to the ranks (0 = one per rank); "
                          "configs[3]: --workload cfg4_stereo_65536tap_L4096_fp32 --streams 256 --blocks 1024")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beyond the headline: kernel events in the timed region and the roofline, the "
+                         "serial-schedule pass, parity of the timed output against the oracle, the CPU baseline, "
+                         "end_to_end and latency_one_block_us (the --no-* switches below apply to a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write a fixed sample of the last timed step's output (at most 32 MiB) to DIR/output.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="no oracle at all: neither the CPU timing nor the parity check")
     ap.add_argument("--no-cpu-timing", action="store_true", help="keep the parity check of the timed output, skip the CPU timing")
     ap.add_argument("--no-extras", action="store_true", help="skip end_to_end and latency_one_block_us")
@@ -289,7 +305,10 @@ def parse_args(argv=None):
     ap.add_argument("--device", type=int, default=-1, help="HIP device ordinal (default: LOCAL_RANK)")
     ap.add_argument("--channels", type=int, default=0, help="override the workload's channel count (1..8); the line's config says so")
     ap.add_argument("--spawn-check", action="store_true", help=argparse.SUPPRESS)
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run does what the headline figure needs and nothing else
+        args.no_cpu_baseline = args.no_extras = args.no_exclusive_pass = args.no_kernel_events = True
+    return args
 
 
 def auto_chunk(n_ch, N, B, s):
@@ -428,6 +447,8 @@ def main():
         assert eng.sync() == 0
         prof = eng.profile()
         eng.set_profiling(False)
+    if args.dump_outputs and eng is not None and rank == 0:
+        dump_outputs(args.dump_outputs, torch, d_out, L, C)
 
     # parity of the TIMED output: sampled blocks of d_out as the last timed step left it.  Every step
     # reads the same resident input and continues the previous step's history, so global block g of
@@ -620,6 +641,20 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     return result
+
+
+DUMP_BYTES = 32 << 20
+
+
+def dump_outputs(path, torch, d_out, L, C):
+    """DIR/output.npy: the engine-blocks (L frames x C channels of one engine) of d_out picked by default_rng(0), in
+    ascending order -- all of them when they fit DUMP_BYTES.  The sample depends on the buffer's shape only."""
+    blocks = d_out.reshape(-1, L, C)
+    n = min(blocks.shape[0], DUMP_BYTES // (L * C * d_out.element_size()))
+    idx = np.sort(np.random.default_rng(0).choice(blocks.shape[0], size=n, replace=False))
+    sample = blocks.index_select(0, torch.as_tensor(idx, device=d_out.device)).cpu().numpy()
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "output.npy"), sample)
 
 
 def host_path_figures(bfir, torch, L, B, s, C, h, d_in, local):

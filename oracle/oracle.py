@@ -36,6 +36,16 @@ def build(force=False):
     return _SO
 
 
+REF_HASH_SO = os.path.join(_HERE, "_ref", "libref_hash.so")
+
+
+def build_ref():
+    """Compile the reference's own hash.c into _ref/ (make -C oracle ref) where its sources are present.
+    Returns the library's path, or None where there is nothing to build it from."""
+    r = subprocess.run(["make", "-C", _HERE, "ref"], stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    return REF_HASH_SO if r.returncode == 0 else None
+
+
 _lib = None
 
 

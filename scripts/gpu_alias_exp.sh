@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-alias}
 mkdir -p $OUT
 export BFIR_LIB_OVERRIDE=$PWD/foo-dsp-bfir_amd/lib/libbfir_hip_alias.so
 run() {
-  timeout -k 10 300 python bench.py --blocks 32768 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/$1.json 2>>$OUT/err.log || { echo "$1 failed"; tail -3 $OUT/err.log; return; }
+  timeout -k 10 300 python bench.py --full --blocks 32768 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/$1.json 2>>$OUT/err.log || { echo "$1 failed"; tail -3 $OUT/err.log; return; }
   python - <<PY
 import json
 d=json.load(open("$OUT/$1.json")); r=d["roofline"]

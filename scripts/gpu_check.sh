@@ -13,11 +13,11 @@ timeout -k 10 900 python -m pytest tests -m gpu -x -q > $OUT/pytest_gpu.log 2>&1
 echo "pytest rc=$?" | tee -a $OUT/progress.log
 tail -3 $OUT/pytest_gpu.log
 echo "== bench default" | tee -a $OUT/progress.log
-timeout -k 10 600 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo bench failed; tail -20 $OUT/bench_default.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo bench failed; tail -20 $OUT/bench_default.err; exit 1; }
 cat $OUT/bench_default.json
 echo "== chunk sweep" | tee -a $OUT/progress.log
 for c in ${SWEEP:-512 1024 2048}; do
-  timeout -k 10 300 python bench.py --chunk $c --steps 4 --warmup 1 --no-cpu-baseline >> $OUT/bench_sweep.jsonl 2>> $OUT/bench_sweep.err || exit 1
+  timeout -k 10 300 python bench.py --full --chunk $c --steps 4 --warmup 1 --no-cpu-baseline >> $OUT/bench_sweep.jsonl 2>> $OUT/bench_sweep.err || exit 1
 done
 python - <<PY
 import json
@@ -25,7 +25,7 @@ for l in open("$OUT/bench_sweep.jsonl"):
     d=json.loads(l); r=d["roofline"]; print(d["config"]["blocks_per_launch"], d["value"], r["kernel_ms_share"], r["kernel"], r["avg_launch_ms"])
 PY
 echo "== rocprof kernel stats" | tee -a $OUT/progress.log
-CMD="python bench.py --chunk $CHUNK --steps 4 --warmup 1 --no-cpu-baseline --no-exclusive-pass"
+CMD="python bench.py --full --chunk $CHUNK --steps 4 --warmup 1 --no-cpu-baseline --no-exclusive-pass"
 echo "{\"workload\": \"$WORKLOAD\", \"chunk\": $CHUNK, \"command\": \"$CMD\"}" > $OUT/pmc_meta.json
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -o stats -- $CMD > $OUT/rocprof_stats.log 2>&1 || { tail -20 $OUT/rocprof_stats.log; exit 1; }
 echo "== rocprof pmc FETCH_SIZE" | tee -a $OUT/progress.log

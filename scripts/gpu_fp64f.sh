@@ -8,7 +8,7 @@ for v in 9; do
 done
 for v in 0 9 7 8 0; do
   for wl in cfg5_2ch_262144tap_L4096_fp64 plugin_2ch_65536tap_L1024_fp64_f32frames; do
-    BFIR_MAC64_VARIANT=$v timeout -k 10 300 python bench.py --workload $wl --blocks 16384 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/${wl}_$v.json 2>>$OUT/err.log || { echo "$wl v$v failed"; tail -3 $OUT/err.log; continue; }
+    BFIR_MAC64_VARIANT=$v timeout -k 10 300 python bench.py --full --workload $wl --blocks 16384 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/${wl}_$v.json 2>>$OUT/err.log || { echo "$wl v$v failed"; tail -3 $OUT/err.log; continue; }
     python - <<PY
 import json
 d=json.load(open("$OUT/${wl}_$v.json")); r=d["roofline"]

@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-other}
 mkdir -p $OUT
 run() {
   name=$1; shift
-  timeout -k 10 600 python bench.py "$@" --steps 4 --warmup 1 --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; return; }
+  timeout -k 10 600 python bench.py --full "$@" --steps 4 --warmup 1 --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; return; }
   python - <<PY
 import json
 d=json.load(open("$OUT/$name.json")); r=d["roofline"]

@@ -12,9 +12,9 @@ export TMPDIR=/tmp
 SHA=$(python -c "import bench; print(bench.csrc_sha())")
 echo "csrc sha $SHA" | tee $OUT/progress.log
 echo "== bench default" | tee -a $OUT/progress.log
-timeout -k 10 900 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo bench failed; tail -20 $OUT/bench_default.err; exit 1; }
+timeout -k 10 900 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { echo bench failed; tail -20 $OUT/bench_default.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/bench_default.json')); print(d['value'], d['roofline']['pipeline'], d['roofline']['exclusive_launch_ms'])"
-CMD="python bench.py --blocks 32768 --steps 4 --warmup 1 --no-cpu-baseline --no-extras --no-exclusive-pass"
+CMD="python bench.py --full --blocks 32768 --steps 4 --warmup 1 --no-cpu-baseline --no-extras --no-exclusive-pass"
 echo "{\"workload\": \"$WORKLOAD\", \"chunk\": 4096, \"csrc_sha\": \"$SHA\", \"command\": \"$CMD\"}" > $OUT/pmc_meta.json
 echo "== rocprof kernel stats" | tee -a $OUT/progress.log
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_stats -o stats -- $CMD > $OUT/rocprof_stats.log 2>&1 || { tail -20 $OUT/rocprof_stats.log; exit 1; }
@@ -25,7 +25,7 @@ echo "== rocprof pmc WRITE_SIZE" | tee -a $OUT/progress.log
 timeout -k 10 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/prof_write -o write -- $CMD --no-kernel-events > $OUT/rocprof_write.log 2>&1 || { tail -20 $OUT/rocprof_write.log; exit 1; }
 python scripts/summarize_pmc.py $OUT > $OUT/pmc_summary.txt 2>&1; cat $OUT/pmc_summary.txt
 echo "== SQ counters (serial schedule: each kernel alone)" | tee -a $OUT/progress.log
-SQCMD="python bench.py --blocks 16384 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-exclusive-pass --no-kernel-events"
+SQCMD="python bench.py --full --blocks 16384 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-exclusive-pass --no-kernel-events"
 export BFIR_PIPE=1
 timeout -k 10 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/sq1 -o p1 -- $SQCMD > $OUT/sq1.log 2>&1 || tail -5 $OUT/sq1.log
 timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VMEM --output-format csv -d $OUT/sq2 -o p2 -- $SQCMD > $OUT/sq2.log 2>&1 || tail -5 $OUT/sq2.log
@@ -51,7 +51,7 @@ for k in sorted(acc):
 PY
 cat $OUT/sq_summary.txt
 echo "== other configs" | tee -a $OUT/progress.log
-run() { name=$1; shift; timeout -k 10 600 python bench.py "$@" --steps 6 --warmup 2 --no-extras --no-cpu-timing > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; return; }
+run() { name=$1; shift; timeout -k 10 600 python bench.py --full "$@" --steps 6 --warmup 2 --no-extras --no-cpu-timing > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; return; }
   python - <<PY | tee -a $OUT/other_configs.txt
 import json
 d=json.load(open("$OUT/$name.json")); r=d["roofline"]
@@ -76,7 +76,7 @@ for g in 0.01 0.0005; do timeout -k 10 300 python scripts/plugin_shape.py $g 2>&
 timeout -k 10 300 python scripts/host_path.py 2>&1 | grep -v amdgpu.ids | tee $OUT/host_path.txt
 bash scripts/gpu_lat_prof.sh $TAG/latprof 2>&1 | grep -v amdgpu.ids | tee $OUT/latency_kernels.txt
 echo "== two ranks on this one GPU (gloo), both sharding modes" | tee -a $OUT/progress.log
-timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --device 0 --blocks 32768 --steps 6 --warmup 2 --no-extras --no-cpu-baseline > $OUT/gpus2_replicas.json 2>$OUT/gpus2.err; python -c "import json; d=json.load(open('$OUT/gpus2_replicas.json')); print('replicas', d['n_gpus'], d['scaling'], d['value'])"
-timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --device 0 --shard channels --blocks 32768 --steps 6 --warmup 2 --no-extras --no-cpu-baseline > $OUT/gpus2_channels.json 2>>$OUT/gpus2.err; python -c "import json; d=json.load(open('$OUT/gpus2_channels.json')); print('channels', d['n_gpus'], d['scaling'], d['value'])"
+timeout -k 10 300 python bench.py --full --gpus 2 --dist-backend gloo --device 0 --blocks 32768 --steps 6 --warmup 2 --no-extras --no-cpu-baseline > $OUT/gpus2_replicas.json 2>$OUT/gpus2.err; python -c "import json; d=json.load(open('$OUT/gpus2_replicas.json')); print('replicas', d['n_gpus'], d['scaling'], d['value'])"
+timeout -k 10 300 python bench.py --full --gpus 2 --dist-backend gloo --device 0 --shard channels --blocks 32768 --steps 6 --warmup 2 --no-extras --no-cpu-baseline > $OUT/gpus2_channels.json 2>>$OUT/gpus2.err; python -c "import json; d=json.load(open('$OUT/gpus2_channels.json')); print('channels', d['n_gpus'], d['scaling'], d['value'])"
 find $OUT -name "*.db" -delete; find $OUT -size +8M -delete
 echo "== done" | tee -a $OUT/progress.log

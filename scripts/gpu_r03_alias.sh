@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-r03g}; mkdir -p $OUT
 run() { # name lib [env...]
   name=$1; lib=$2; shift 2
   if [ "$lib" = product ]; then unset BFIR_LIB_OVERRIDE; else export BFIR_LIB_OVERRIDE=$PWD/foo-dsp-bfir_amd/lib/libbfir_hip_$lib.so; fi
-  env "$@" timeout -k 10 300 python bench.py --blocks 32768 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/$name.json 2>>$OUT/err.log || { echo "$name failed"; tail -3 $OUT/err.log; return; }
+  env "$@" timeout -k 10 300 python bench.py --full --blocks 32768 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/$name.json 2>>$OUT/err.log || { echo "$name failed"; tail -3 $OUT/err.log; return; }
   python - <<PY | tee -a $OUT/alias.txt
 import json
 d=json.load(open("$OUT/$name.json")); r=d["roofline"]

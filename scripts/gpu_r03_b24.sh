@@ -3,7 +3,7 @@
 set -o pipefail
 OUT=gpurun_out/b24
 mkdir -p $OUT
-run() { name=$1; shift; timeout -k 10 600 python bench.py "$@" --steps 6 --warmup 2 --no-extras --no-cpu-timing > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; return 1; }
+run() { name=$1; shift; timeout -k 10 600 python bench.py --full "$@" --steps 6 --warmup 2 --no-extras --no-cpu-timing > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; return 1; }
   python - <<PY | tee -a $OUT/summary.txt
 import json
 d=json.load(open("$OUT/$name.json")); r=d["roofline"]

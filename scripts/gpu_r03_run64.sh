@@ -7,5 +7,5 @@ pick='import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(sy
 for wl in ${WLS:-cfg5_2ch_262144tap_L4096_fp64}; do
 for len in ${LENS:-0 default 2 4 8 16 32}; do
   if [ $len = default ]; then unset BFIR_RUN64; else export BFIR_RUN64=$len; fi
-  timeout -k 10 300 python bench.py --workload $wl ${EXTRA} --steps 4 --warmup 1 --no-cpu-timing --no-extras 2>$OUT/err.log | python -c "$pick" ${wl}_run$len | tee -a $OUT/run64.txt
+  timeout -k 10 300 python bench.py --full --workload $wl ${EXTRA} --steps 4 --warmup 1 --no-cpu-timing --no-extras 2>$OUT/err.log | python -c "$pick" ${wl}_run$len | tee -a $OUT/run64.txt
 done; done

@@ -7,7 +7,7 @@ mkdir -p $OUT
 timeout -k 10 600 python -m pytest tests/test_mac_sys_gpu.py tests/test_isa_audit.py -x -q > $OUT/pytest.log 2>&1; rc=$?
 tail -5 $OUT/pytest.log
 [ $rc -eq 0 ] || exit $rc
-run() { name=$1; shift; timeout -k 10 600 python bench.py "$@" --steps 6 --warmup 2 --no-extras --no-cpu-timing > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; return 1; }
+run() { name=$1; shift; timeout -k 10 600 python bench.py --full "$@" --steps 6 --warmup 2 --no-extras --no-cpu-timing > $OUT/$name.json 2> $OUT/$name.err || { echo "$name failed"; tail -5 $OUT/$name.err; return 1; }
   python - <<PY | tee -a $OUT/summary.txt
 import json
 d=json.load(open("$OUT/$name.json")); r=d["roofline"]

@@ -4,7 +4,7 @@
 set -o pipefail
 OUT=gpurun_out/${1:-r03sq64}; mkdir -p $OUT; export TMPDIR=/tmp
 for wl in plugin_2ch_65536tap_L1024_fp64_f32frames cfg5_2ch_262144tap_L4096_fp64; do
-  CMD="python bench.py --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-exclusive-pass --no-kernel-events"
+  CMD="python bench.py --full --workload $wl --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-exclusive-pass --no-kernel-events"
   timeout -k 10 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/${wl}_p1 -o p1 -- $CMD > $OUT/${wl}_p1.log 2>&1 || tail -5 $OUT/${wl}_p1.log
   timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_SALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VMEM --output-format csv -d $OUT/${wl}_p2 -o p2 -- $CMD > $OUT/${wl}_p2.log 2>&1 || tail -5 $OUT/${wl}_p2.log
   timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${wl}_kt -o kt -- $CMD > $OUT/${wl}_kt.log 2>&1 || tail -5 $OUT/${wl}_kt.log

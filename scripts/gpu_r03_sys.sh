@@ -8,7 +8,7 @@ echo "== parity" | tee $OUT/progress.log
 timeout -k 10 600 python -m pytest tests/test_mac_sys_gpu.py -x -q > $OUT/pytest.log 2>&1
 rc=$?; tail -5 $OUT/pytest.log; echo "pytest rc=$rc" | tee -a $OUT/progress.log
 [ $rc -ne 0 ] && exit $rc
-B="python bench.py --steps 6 --warmup 2 --no-cpu-timing --no-extras --blocks 65536"
+B="python bench.py --full --steps 6 --warmup 2 --no-cpu-timing --no-extras --blocks 65536"
 pick='import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(sys.argv[1], "value %.0f" % d["value"], "ms/set %.4f" % r["pipeline"]["ms_per_launch_set"], "overlapped", {k: round(v["avg_launch_ms"],3) for k,v in r["kernels"].items()}, "exclusive", {k: round(v,3) for k,v in r["exclusive_launch_ms"].items()}, "parity", d.get("parity_rel_err_vs_oracle"))'
 echo "== A/B" | tee -a $OUT/progress.log
 for rep in 1 2; do

@@ -3,7 +3,7 @@
 # hand-over, 2 no relay of x, 4 no stores, 8 no loads, 16 no negated operand, 32 no tail test; exclusive kernel times.
 set -o pipefail
 OUT=gpurun_out/${1:-r03f}; mkdir -p $OUT
-B="python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras --blocks 16384"
+B="python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras --blocks 16384"
 pick='import json,sys; d=json.loads(sys.stdin.read()); r=d["roofline"]; print(sys.argv[1], "value %.0f" % d["value"], "exclusive", {k: round(v,3) for k,v in r["exclusive_launch_ms"].items()})'
 L=$PWD/foo-dsp-bfir_amd/lib
 BFIR_MAC_SYS=0 timeout -k 10 300 $B 2>$OUT/err.log | python -c "$pick" stream | tee -a $OUT/exp.txt

@@ -9,5 +9,5 @@ L=$PWD/foo-dsp-bfir_amd/lib
 for wl in cfg5_2ch_262144tap_L4096_fp64 plugin_2ch_65536tap_L1024_fp64_f32frames; do
 for v in "" e1 e2 e3 e4 e8 e15 e47; do
   if [ -n "$v" ]; then export BFIR_LIB_OVERRIDE=$L/libbfir_hip_$v.so; else unset BFIR_LIB_OVERRIDE; fi
-  timeout -k 10 300 python bench.py --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>$OUT/err.log | python -c "$pick" "${wl}_${v:-product}" | tee -a $OUT/exp64.txt
+  timeout -k 10 300 python bench.py --full --workload $wl --steps 3 --warmup 1 --no-cpu-baseline --no-extras 2>$OUT/err.log | python -c "$pick" "${wl}_${v:-product}" | tee -a $OUT/exp64.txt
 done; done

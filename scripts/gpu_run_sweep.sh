@@ -4,7 +4,7 @@ set -o pipefail
 OUT=gpurun_out/${1:-runs}
 mkdir -p $OUT
 for r in 1 2 4 8 16 32 64; do
-  BFIR_PAIR_RUN=$r timeout -k 10 300 python bench.py --blocks 32768 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/r$r.json 2>>$OUT/err.log || { echo "r$r failed"; tail -3 $OUT/err.log; continue; }
+  BFIR_PAIR_RUN=$r timeout -k 10 300 python bench.py --full --blocks 32768 --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/r$r.json 2>>$OUT/err.log || { echo "r$r failed"; tail -3 $OUT/err.log; continue; }
   python - <<PY
 import json
 d=json.load(open("$OUT/r$r.json")); r=d["roofline"]

@@ -5,7 +5,7 @@ OUT=gpurun_out/${1:-sq64}; mkdir -p $OUT; export TMPDIR=/tmp
 export BFIR_PIPE=1
 for v in 0 12; do
   export BFIR_MAC64_VARIANT=$v
-  CMD="python bench.py --workload plugin_2ch_65536tap_L1024_fp64_f32frames --blocks 16384 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-exclusive-pass --no-kernel-events"
+  CMD="python bench.py --full --workload plugin_2ch_65536tap_L1024_fp64_f32frames --blocks 16384 --steps 2 --warmup 1 --no-cpu-baseline --no-extras --no-exclusive-pass --no-kernel-events"
   timeout -k 10 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVES --output-format csv -d $OUT/v${v}_p1 -o p1 -- $CMD > $OUT/v${v}_p1.log 2>&1 || tail -5 $OUT/v${v}_p1.log
   timeout -k 10 600 rocprofv3 --pmc SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INST_CYCLES_VMEM SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VMEM TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/v${v}_p2 -o p2 -- $CMD > $OUT/v${v}_p2.log 2>&1 || tail -5 $OUT/v${v}_p2.log
   timeout -k 10 600 rocprofv3 --pmc GRBM_GUI_ACTIVE FETCH_SIZE --output-format csv -d $OUT/v${v}_p3 -o p3 -- $CMD > $OUT/v${v}_p3.log 2>&1 || tail -5 $OUT/v${v}_p3.log

@@ -7,7 +7,7 @@ for v in 1 2 3; do
 done
 for v in 0 1 2 3 0; do
   for wl in plugin_8ch_65536tap_L1024_fp32 plugin_8ch_131072tap_L1024_fp32 plugin_2ch_65536tap_L1024_fp32; do
-    BFIR_MAC_TS=$v timeout -k 10 300 python bench.py --workload $wl --blocks 32768 --steps 6 --warmup 2 --no-cpu-timing --no-extras > $OUT/${wl}_$v.json 2>>$OUT/err.log || { echo "$wl v$v failed"; tail -3 $OUT/err.log; continue; }
+    BFIR_MAC_TS=$v timeout -k 10 300 python bench.py --full --workload $wl --blocks 32768 --steps 6 --warmup 2 --no-cpu-timing --no-extras > $OUT/${wl}_$v.json 2>>$OUT/err.log || { echo "$wl v$v failed"; tail -3 $OUT/err.log; continue; }
     python - <<PY
 import json
 d=json.load(open("$OUT/${wl}_$v.json")); r=d["roofline"]

@@ -5,7 +5,7 @@ OUT=gpurun_out/$1; shift
 mkdir -p $OUT
 for v in "$@"; do
   if [ "$v" = base ]; then unset BFIR_LIB_OVERRIDE; else export BFIR_LIB_OVERRIDE=$PWD/foo-dsp-bfir_amd/lib/libbfir_hip_$v.so; fi
-  timeout -k 10 300 python bench.py --blocks ${BLOCKS:-32768} --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/$v.json 2>>$OUT/err.log || { echo "$v failed"; tail -3 $OUT/err.log; continue; }
+  timeout -k 10 300 python bench.py --full --blocks ${BLOCKS:-32768} --steps 6 --warmup 2 --no-cpu-baseline --no-extras > $OUT/$v.json 2>>$OUT/err.log || { echo "$v failed"; tail -3 $OUT/err.log; continue; }
   python - <<PY
 import json
 d=json.load(open("$OUT/$v.json")); r=d["roofline"]

@@ -6,7 +6,7 @@ OUT=gpurun_out/$TAG
 mkdir -p $OUT
 for v in ${VARIANTS:-0 1 2 3 4}; do
   for c in ${CHUNKS:-128 256}; do
-    BFIR_MAC_VARIANT=$v timeout -k 10 300 python bench.py --chunk $c --steps 6 --warmup 2 --no-cpu-baseline > $OUT/v${v}_c${c}.json 2>> $OUT/err.log || { echo "variant $v chunk $c failed"; tail -5 $OUT/err.log; continue; }
+    BFIR_MAC_VARIANT=$v timeout -k 10 300 python bench.py --full --chunk $c --steps 6 --warmup 2 --no-cpu-baseline > $OUT/v${v}_c${c}.json 2>> $OUT/err.log || { echo "variant $v chunk $c failed"; tail -5 $OUT/err.log; continue; }
     python - <<PY
 import json
 d=json.load(open("$OUT/v${v}_c${c}.json")); r=d["roofline"]
