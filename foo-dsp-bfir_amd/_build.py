@@ -26,7 +26,6 @@ def _stale(target, deps):
 
 
 FLAGS_FILE = os.path.join(LIBDIR, "flags.txt")
-USAGE_FILE = os.path.join(LIBDIR, "resource_usage.json")
 
 
 def _compile(cmd, src):

@@ -272,10 +272,7 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
     e->in_scale = fmt_info(in_format).isfloat ? 1.0 : 1.0 / fmt_full_scale(in_format);
     e->out_scale = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format);
     e->of_max = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format) - 1.0;
-    {   // BFIR_MAC_VARIANT != 0 (tuning aid) keeps the grouped layout and the other MAC kernels
-        const char *mv = getenv("BFIR_MAC_VARIANT");
-        e->ilv = realsize == 4 && e->N >= 512 && !(mv && atoi(mv) != 0);
-    }
+    e->ilv = realsize == 4 && e->N >= 512;   // fp32: (re, im) pairs from N = 512 (whole 256-bin columns)
     {   // BFIR_PAIR=0 (tuning aid) keeps the planar staging kernels
         const char *pv = getenv("BFIR_PAIR");
         // the persistent kernels only (BFIR_PAIR_PERSIST=0 keeps odd channel counts on the general path)
@@ -307,8 +304,8 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
         // partitions) -- so the switches that pick other kernels keep the groups (all read HERE, at creation, for such engines).
         // BFIR_F64_PAIRS=0: off (A/B).  Same arithmetic either way: the same bits.
         {
-            const char *fp = getenv("BFIR_F64_PAIRS"), *ms = getenv("BFIR_MAC_SYS"), *mv = getenv("BFIR_MAC_VARIANT");
-            const bool other_mac = (ms && atoi(ms) == 0) || getenv("BFIR_MAC64_VARIANT") || getenv("BFIR_MAC_BATCHED") || (mv && atoi(mv) != 0);
+            const char *fp = getenv("BFIR_F64_PAIRS"), *ms = getenv("BFIR_MAC_SYS");
+            const bool other_mac = (ms && atoi(ms) == 0) || getenv("BFIR_MAC_BATCHED");
             if (realsize == 8 && e->direct && pairs64_supported(filter_length, realsize) && filter_blocks <= BFIR_MAC_SYS_MAX_B && !other_mac &&
                 !(fp && atoi(fp) == 0))
                 e->ilv = true;

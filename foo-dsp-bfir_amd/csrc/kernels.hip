@@ -1177,7 +1177,7 @@ __global__ __launch_bounds__(256, WPE) void k_mac(MacArgs a, int nbt, int nTT, i
 }
 
 // ---------------------------------------------------------------------------
-// k_mac_lds: the same sums with the operands shared through LDS (fp32)
+// k_mac_lds: the same sums with the operands shared through LDS (fp32, (re, im) pairs)
 // ---------------------------------------------------------------------------
 // A workgroup of 4 waves owns 64 groups (256 bins) of one channel for 32
 // consecutive output blocks: wave w computes blocks tb+8w .. tb+8w+7 with the
@@ -1189,21 +1189,12 @@ __global__ __launch_bounds__(256, WPE) void k_mac(MacArgs a, int nbt, int nTT, i
 // 16 KiB), one 16-byte load per lane, issued D steps ahead; everything else is
 // ds_read_b128 of lane-contiguous data (conflict free).  One barrier per step.
 // Sums are formed in the same order with the same fma chain as k_mac, so the
-// two kernels give bit-identical results.
-// Native 4-wide vectors (not HIP's float4 struct): they are register-tuple aligned, so their
-// .lo / .hi halves feed v_pk_fma_f32 directly; scalarised struct members needed ~30 v_mov per step.
+// two kernels give bit-identical results.  The spectra are (re, im) pairs
+// (MacArgs.interleaved): "planes" 0 / 1 of a group are its first / second 16
+// bytes (bins 0-1 / bins 2-3).  (The grouped-layout build is removed: fp32
+// engines with N >= 512 always keep pairs.)
 typedef float v4f __attribute__((ext_vector_type(4)));
-// nhi = -hi, negated once per step by the caller (fma(-xi, hi, ar) == fma(xi, -hi, ar) exactly)
-__device__ __forceinline__ void cmac4(v4f &ar, v4f &ai, const v4f &xr, const v4f &xi, const v4f &hr, const v4f &hi,
-                                      const v4f &nhi)
-{
-    ar.lo = __builtin_elementwise_fma(xr.lo, hr.lo, ar.lo); ar.lo = __builtin_elementwise_fma(xi.lo, nhi.lo, ar.lo);
-    ar.hi = __builtin_elementwise_fma(xr.hi, hr.hi, ar.hi); ar.hi = __builtin_elementwise_fma(xi.hi, nhi.hi, ar.hi);
-    ai.lo = __builtin_elementwise_fma(xr.lo, hi.lo, ai.lo); ai.lo = __builtin_elementwise_fma(xi.lo, hr.lo, ai.lo);
-    ai.hi = __builtin_elementwise_fma(xr.hi, hi.hi, ai.hi); ai.hi = __builtin_elementwise_fma(xi.hi, hr.hi, ai.hi);
-}
-
-// (re, im) pair layout: a group is A = (r0 i0 r1 i1), B = (r2 i2 r3 i3); the same four fused
+// a group is A = (r0 i0 r1 i1), B = (r2 i2 r3 i3); the same four fused
 // multiply-adds per bin as cmac4, on the components where they lie (no shuffle, same rounding)
 __device__ __forceinline__ void cmac4_pairs(v4f &aA, v4f &aB, const v4f &xA, const v4f &xB, const v4f &hA, const v4f &hB)
 {
@@ -1213,16 +1204,14 @@ __device__ __forceinline__ void cmac4_pairs(v4f &aA, v4f &aB, const v4f &xA, con
     aB.z = fmaf(xB.z, hB.z, aB.z); aB.z = fmaf(xB.w, -hB.w, aB.z); aB.w = fmaf(xB.z, hB.w, aB.w); aB.w = fmaf(xB.w, hB.z, aB.w);
 }
 
-// PAIRS: the spectra are (re, im) pairs (MacArgs.interleaved); "planes" 0 / 1 of a group are then its
-// first / second 16 bytes (bins 0-1 / bins 2-3) instead of the real / imaginary parts.
-template <int D, bool DCNY, bool PAIRS>
+template <int D, bool DCNY>
 __device__ __forceinline__ void mac_lds_steps(v4f (&accr)[8], v4f (&acci)[8], float (&dc)[8], float (&ny)[8],
                                               v4f (&wr)[8], v4f (&wi)[8], v4f (*s_ring)[2][64],
                                               v4f (*s_h)[2][64], const v4f *__restrict__ duty_base,
                                               long duty_slot4, bool duty_is_h, int duty_plane, int nb, int ring,
                                               int sl_tb, int lane, int wv)
 {
-    // duty: this wave fetches one plane (re or im) of H_s (waves 0,1) or of
+    // duty: this wave fetches one plane of H_s (waves 0,1) or of
     // X[tb - s] (waves 2,3) for every step s, D steps ahead of its use
     v4f q[D];
     const v4f *__restrict__ dbase = duty_base;
@@ -1251,7 +1240,6 @@ __device__ __forceinline__ void mac_lds_steps(v4f (&accr)[8], v4f (&acci)[8], fl
             const int i = i0 + ii;
             if (i < nb) {   // uniform over the workgroup
                 const v4f hr = s_h[ii & 1][0][lane], hi = s_h[ii & 1][1][lane];
-                const v4f nhi = -hi;
                 if (i > 0) {
                     const int e = (8 * wv - i) & 31;             // ring entry holding X[tb + 8 wv - i]
                     wr[(8 - ii) % 8] = s_ring[e][0][lane]; wi[(8 - ii) % 8] = s_ring[e][1][lane];
@@ -1259,18 +1247,10 @@ __device__ __forceinline__ void mac_lds_steps(v4f (&accr)[8], v4f (&acci)[8], fl
 #pragma unroll
                 for (int j = 0; j < 8; j++) {
                     const int idx = (j - ii + 8) % 8;            // window slot holding X[t0 + j - i]
-                    if constexpr (PAIRS) {
-                        cmac4_pairs(accr[j], acci[j], wr[idx], wi[idx], hr, hi);
-                        if constexpr (DCNY) {              // bin 0 = (DC, Nyquist): .x and .y of the first half
-                            dc[j] = fma(wr[idx].x, hr.x, dc[j]);
-                            ny[j] = fma(wr[idx].y, hr.y, ny[j]);
-                        }
-                    } else {
-                        cmac4(accr[j], acci[j], wr[idx], wi[idx], hr, hi, nhi);
-                        if constexpr (DCNY) {
-                            dc[j] = fma(wr[idx].x, hr.x, dc[j]);
-                            ny[j] = fma(wi[idx].x, hi.x, ny[j]);
-                        }
+                    cmac4_pairs(accr[j], acci[j], wr[idx], wi[idx], hr, hi);
+                    if constexpr (DCNY) {                  // bin 0 = (DC, Nyquist): .x and .y of the first half
+                        dc[j] = fma(wr[idx].x, hr.x, dc[j]);
+                        ny[j] = fma(wr[idx].y, hr.y, ny[j]);
                     }
                 }
                 // publish the operands of step i+1, refill the queue slot with those of step i+1+D
@@ -1286,7 +1266,7 @@ __device__ __forceinline__ void mac_lds_steps(v4f (&accr)[8], v4f (&acci)[8], fl
 #undef BFIR_DUTY_STORE
 }
 
-template <int D, bool PAIRS>
+template <int D>
 __global__ __launch_bounds__(256, 2) void k_mac_lds(MacArgs a, int nbt, int nTQ)
 {
     __shared__ __attribute__((aligned(16))) v4f s_ring[32][2][64];
@@ -1319,20 +1299,17 @@ __global__ __launch_bounds__(256, 2) void k_mac_lds(MacArgs a, int nbt, int nTQ)
     const bool duty_is_h = wv < 2;
     const int plane = wv & 1;
     if (bt == 0)
-        mac_lds_steps<D, true, PAIRS>(accr, acci, dc, ny, wr, wi, s_ring, s_h, duty_is_h ? H : X, slot4, duty_is_h, plane,
+        mac_lds_steps<D, true>(accr, acci, dc, ny, wr, wi, s_ring, s_h, duty_is_h ? H : X, slot4, duty_is_h, plane,
                                nb, ring, sl_tb, lane, wv);
     else
-        mac_lds_steps<D, false, PAIRS>(accr, acci, dc, ny, wr, wi, s_ring, s_h, duty_is_h ? H : X, slot4, duty_is_h, plane,
+        mac_lds_steps<D, false>(accr, acci, dc, ny, wr, wi, s_ring, s_h, duty_is_h ? H : X, slot4, duty_is_h, plane,
                                 nb, ring, sl_tb, lane, wv);
     float *__restrict__ Y = (float *)a.y + (long)gc * a.y_ch_stride;
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const int t = t0 + j;
         if (t < a.n_t) {
-            if (g == 0) {
-                if constexpr (PAIRS) { accr[j].x = dc[j]; accr[j].y = ny[j]; }
-                else { accr[j].x = dc[j]; acci[j].x = ny[j]; }
-            }
+            if (g == 0) { accr[j].x = dc[j]; accr[j].y = ny[j]; }
             v4f *yo = (v4f *)(Y + (long)t * a.N) + 2 * g;
             yo[0] = accr[j]; yo[1] = acci[j];
         }
@@ -1459,7 +1436,7 @@ __global__ __launch_bounds__(256, 2) void k_mac_lds_d(MacArgs a, int nbt, int nT
 }
 
 // ---------------------------------------------------------------------------
-// k_mac_lds_d2: the fp64 LDS MAC with TWO bins per lane and EIGHT blocks per wave
+// k_mac_lds_d2g: the fp64 LDS MAC with TWO bins per lane and EIGHT blocks per wave
 // ---------------------------------------------------------------------------
 // k_mac_lds_d reads 128 bytes of LDS per lane and step (H_i and one delay-line spectrum, 4 bins each) for
 // 64 double FMAs; eight waves per CU doing that need the whole 256 B/clk of the LDS, which is what bounds it
@@ -1469,6 +1446,11 @@ __global__ __launch_bounds__(256, 2) void k_mac_lds_d(MacArgs a, int nbt, int nT
 // k_mac_lds (16-byte planes, 32-entry ring, 32-block time tiles, duty waves 0/1 fetch H re/im, 2/3 fetch
 // X[tb - s] re/im); lanes 2g and 2g+1 share group g of the grouped layout.  Same fma chain per bin and the
 // same partition order as every other MAC kernel: bit-identical sums.
+// G partition steps per barrier: a barrier after every partition (64 double FMAs per lane, ~0.3 us) costs a
+// third of the time at two waves per SIMD (measured on the G = 1 form, since removed: see git history).  Here the four duty
+// waves publish the operands of G steps at a time (H_s into a 2G-deep buffer, X[tb - s] into the ring: an
+// entry is overwritten 8 steps after its last reader, so up to 4 steps ahead is safe) and the workgroup meets
+// once per G steps.
 typedef double v2d __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void cmac2d(v2d &ar, v2d &ai, const v2d &xr, const v2d &xi, const v2d &hr, const v2d &hi)
 {
@@ -1476,118 +1458,6 @@ __device__ __forceinline__ void cmac2d(v2d &ar, v2d &ai, const v2d &xr, const v2
     ai = __builtin_elementwise_fma(xr, hi, ai); ai = __builtin_elementwise_fma(xi, hr, ai);
 }
 
-template <int D, bool DCNY>
-__device__ __forceinline__ void mac_lds_steps_d2(v2d (&accr)[8], v2d (&acci)[8], double (&dc)[8], double (&ny)[8],
-                                                 v2d (&wr)[8], v2d (&wi)[8], v2d (*s_ring)[2][64], v2d (*s_h)[2][64],
-                                                 const v2d *__restrict__ dbase, long duty_slot, bool duty_is_h,
-                                                 int nb, int ring, int sl_tb, int lane, int wv, int duty_plane)
-{
-    // duty: this wave fetches one plane (re or im; dbase already points at it) of H_s (waves 0, 1) or of
-    // X[tb - s] (waves 2, 3) for every step s, D steps ahead of its use
-    v2d q[D];
-    int dnext = duty_is_h ? 0 : sl_tb;
-#define BFIR_DUTY_ADVANCE()                                                                         \
-    do {                                                                                            \
-        if (duty_is_h) { if (dnext < nb - 1) dnext += 1; }                                          \
-        else { dnext -= 1; if (dnext < 0) dnext += ring; }                                          \
-    } while (0)
-#define BFIR_DUTY_LOAD() dbase[dnext * duty_slot]
-#define BFIR_DUTY_STORE(s_, v_)                                                                     \
-    do {                                                                                            \
-        v2d *dst_ = duty_is_h ? &s_h[(s_) & 1][duty_plane][lane] : &s_ring[(-(s_)) & 31][duty_plane][lane]; \
-        *dst_ = (v_);                                                                               \
-    } while (0)
-    if (duty_is_h) { const v2d h0 = BFIR_DUTY_LOAD(); BFIR_DUTY_STORE(0, h0); }
-#pragma unroll
-    for (int d = 0; d < D; d++) { BFIR_DUTY_ADVANCE(); q[(1 + d) % D] = BFIR_DUTY_LOAD(); }   // steps 1 .. D
-    __syncthreads();
-    for (int i0 = 0; i0 < nb; i0 += 8) {
-#pragma unroll
-        for (int ii = 0; ii < 8; ii++) {
-            const int i = i0 + ii;
-            if (i < nb) {   // uniform over the workgroup
-                const v2d hr = s_h[ii & 1][0][lane], hi = s_h[ii & 1][1][lane];
-                if (i > 0) {
-                    const int e = (8 * wv - i) & 31;             // ring entry holding X[tb + 8 wv - i]
-                    wr[(8 - ii) % 8] = s_ring[e][0][lane]; wi[(8 - ii) % 8] = s_ring[e][1][lane];
-                }
-#pragma unroll
-                for (int j = 0; j < 8; j++) {
-                    const int idx = (j - ii + 8) % 8;            // window slot holding X[t0 + j - i]
-                    cmac2d(accr[j], acci[j], wr[idx], wi[idx], hr, hi);
-                    if constexpr (DCNY) {
-                        dc[j] = fma(wr[idx].x, hr.x, dc[j]);
-                        ny[j] = fma(wi[idx].x, hi.x, ny[j]);
-                    }
-                }
-                // publish the operands of step i+1, refill the queue slot with those of step i+1+D
-                BFIR_DUTY_STORE(i + 1, q[(ii + 1) % D]);
-                BFIR_DUTY_ADVANCE();
-                q[(ii + 1) % D] = BFIR_DUTY_LOAD();
-                __syncthreads();
-            }
-        }
-    }
-#undef BFIR_DUTY_ADVANCE
-#undef BFIR_DUTY_LOAD
-#undef BFIR_DUTY_STORE
-}
-
-template <int D>
-__global__ __launch_bounds__(256, 2) void k_mac_lds_d2(MacArgs a, int nbt, int nTQ)
-{
-    __shared__ __attribute__((aligned(16))) v2d s_ring[32][2][64];
-    __shared__ __attribute__((aligned(16))) v2d s_h[2][2][64];
-    static_assert(8 % D == 0, "prefetch depth must divide the unroll");
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
-    const int s = w / nTQ, tq = w - s * nTQ;
-    const int gc = s / nbt, bt = s - gc * nbt;
-    const int lane = threadIdx.x & 63;
-    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int g = bt * 32 + (lane >> 1), hh = lane & 1;              // group of 4 bins, which half of it
-    const int tb = tq * 32, t0 = tb + 8 * wv;
-    const long slot = a.N / 2;                                        // v2d elements per spectrum
-    // grouped layout: group g = doubles 8g .. 8g+7 = re0 re1 | re2 re3 | im0 im1 | im2 im3 as four v2d
-    const v2d *__restrict__ X = (const v2d *)((const double *)a.x + (long)gc * a.x_ch_stride) + 4 * g + hh;
-    const v2d *__restrict__ H = (const v2d *)((const double *)a.h + (long)gc * a.h_ch_stride) + 4 * g + hh;
-    const int nb = a.nblk[gc];
-    const int ring = a.ring;
-    const int sl_tb = (a.base_slot + tb) % ring;   // delay-line slot of block tb
-    v2d accr[8], acci[8], wr[8], wi[8];
-    double dc[8], ny[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        accr[j] = v2d{0, 0}; acci[j] = v2d{0, 0};
-        dc[j] = 0.0; ny[j] = 0.0;
-        int sj = sl_tb + 8 * wv + j; if (sj >= ring) sj -= ring;
-        wr[j] = X[sj * slot]; wi[j] = X[sj * slot + 2];
-        s_ring[8 * wv + j][0][lane] = wr[j]; s_ring[8 * wv + j][1][lane] = wi[j];
-    }
-    const bool duty_is_h = wv < 2;
-    const int plane = wv & 1;
-    const v2d *dbase = (duty_is_h ? H : X) + 2 * plane;
-    if (bt == 0)   // lane 0 of this tile holds bin 0: DC in the real slot, Nyquist in the imaginary one
-        mac_lds_steps_d2<D, true>(accr, acci, dc, ny, wr, wi, s_ring, s_h, dbase, slot, duty_is_h, nb, ring, sl_tb, lane, wv, plane);
-    else
-        mac_lds_steps_d2<D, false>(accr, acci, dc, ny, wr, wi, s_ring, s_h, dbase, slot, duty_is_h, nb, ring, sl_tb, lane, wv, plane);
-    double *__restrict__ Y = (double *)a.y + (long)gc * a.y_ch_stride;
-#pragma unroll
-    for (int j = 0; j < 8; j++) {
-        const int t = t0 + j;
-        if (t < a.n_t) {
-            if (g == 0 && hh == 0) { accr[j].x = dc[j]; acci[j].x = ny[j]; }
-            v2d *yo = (v2d *)(Y + (long)t * a.N) + 4 * g + hh;
-            yo[0] = accr[j]; yo[2] = acci[j];
-        }
-    }
-}
-
-// The same kernel with G partition steps per barrier.  k_mac_lds_d2 meets at a workgroup barrier after every
-// partition (64 double FMAs per lane, ~0.3 us): at two waves per SIMD the barrier wait is a third of its time.
-// Here the four duty waves publish the operands of G steps at a time (H_s into a 2G-deep buffer, X[tb - s] into
-// the ring: an entry is overwritten 8 steps after its last reader, so up to 4 steps ahead is safe) and the
-// workgroup meets once per G steps.  Same sums in the same order: bit-identical results.
 template <int G, int PF, bool DCNY>
 __device__ __forceinline__ void mac_lds_steps_d2g(v2d (&accr)[8], v2d (&acci)[8], double (&dc)[8], double (&ny)[8],
                                                   v2d (&wr)[8], v2d (&wi)[8], v2d (*s_ring)[2][64], v2d (*s_h)[2][64],
@@ -1709,17 +1579,10 @@ __global__ __launch_bounds__(256, 2) void k_mac_lds_d2g(MacArgs a, int nbt, int 
     }
 }
 
-template <int D> static void launch_mac_lds_d2(const MacArgs &a, hipStream_t s)
+template <int G, int PF> static void launch_mac_lds_d2g(const MacArgs &a, hipStream_t s)
 {
     const int nbt = a.N / 8 / 32;              // bin tiles of 32 groups (two lanes per group)
     const int nTQ = (a.n_t + 31) / 32;         // time tiles of 32 blocks
-    hipLaunchKernelGGL((k_mac_lds_d2<D>), dim3(nTQ * nbt * a.n_ch), dim3(256), 0, s, a, nbt, nTQ);
-}
-
-template <int G, int PF> static void launch_mac_lds_d2g(const MacArgs &a, hipStream_t s)
-{
-    const int nbt = a.N / 8 / 32;
-    const int nTQ = (a.n_t + 31) / 32;
     hipLaunchKernelGGL((k_mac_lds_d2g<G, PF>), dim3(nTQ * nbt * a.n_ch), dim3(256), 0, s, a, nbt, nTQ);
 }
 
@@ -1958,11 +1821,11 @@ template <int PB, int D> static void launch_mac_stream(const MacArgs &a_, hipStr
                            p0);
 }
 
-template <int D, bool PAIRS = false> static void launch_mac_lds(const MacArgs &a, hipStream_t s)
+template <int D> static void launch_mac_lds(const MacArgs &a, hipStream_t s)
 {
     const int nbt = a.N / 8 / 64;              // bin tiles of 64 groups
     const int nTQ = (a.n_t + 31) / 32;         // time tiles of 32 blocks
-    hipLaunchKernelGGL((k_mac_lds<D, PAIRS>), dim3(nTQ * nbt * a.n_ch), dim3(256), 0, s, a, nbt, nTQ);
+    hipLaunchKernelGGL((k_mac_lds<D>), dim3(nTQ * nbt * a.n_ch), dim3(256), 0, s, a, nbt, nTQ);
 }
 
 template <typename T, int TT, int WPE, int D> static void launch_mac_t(const MacArgs &a, hipStream_t s)
@@ -1973,124 +1836,6 @@ template <typename T, int TT, int WPE, int D> static void launch_mac_t(const Mac
     const int nTT = (a.n_t + TT - 1) / TT;
     const int W = nTT * nbt * a.n_ch;
     hipLaunchKernelGGL((k_mac<T, TT, WPE, D>), dim3(W), dim3(threads), 0, s, a, nbt, nTT, G);
-}
-
-// BFIR_MAC_VARIANT (tuning aid): pick another (time tile, waves/SIMD, prefetch depth)
-// instantiation of the fp32 MAC kernel.  All variants give bit-identical results.
-static int mac_variant()
-{
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("BFIR_MAC_VARIANT");
-        v = e ? atoi(e) : 0;
-        if (v < 0) v = 0;
-    }
-    return v;
-}
-
-// ---------------------------------------------------------------------------
-// k_mac_tstream: partition-streaming MAC out of registers (fp64; grouped layout)
-// ---------------------------------------------------------------------------
-// The transpose of k_mac_stream: a lane owns ONE bin and keeps the sums of TT consecutive output blocks (2 TT
-// values) plus a window of TT delay-line values (2 TT) in registers, and walks the PARTITIONS in order: step p
-// loads h[p] and the one new window value x[t0 - p] (8-byte loads, D steps ahead in a register queue) and feeds
-// all TT outputs, y[t0 + j] += x[t0 + j - p] h[p].  4 TT fused multiply-adds per 32 bytes loaded, no LDS, no
-// barrier -- the LDS-tiled fp64 kernels (k_mac_lds_d2g) spend half their time behind barriers and LDS latency
-// at the two waves per SIMD their 220 registers allow.  Price: the window is re-read by every time tile
-// ((TT + B - 1) / TT spectra per output block instead of (32 + B - 1) / 32) and so is h -- out of L2: the XCD map
-// keeps the time tiles of one (channel, 256-bin column) on one XCD.  Output y[t] receives p = 0 first, B-1
-// last, with the fma chain of every other MAC kernel: bit-identical sums.
-// Measured (profiles/r02_fp64_mac.txt): exactly as fast as the LDS-tiled kernel (0.151 vs 0.158 ms per 4096 blocks at
-// the plug-in's shape, 0.60 vs 0.57 at cfg5's) -- a wave issues DFMAs 31 % of its life and waits for its queue
-// 27 %; two waves per SIMD is all 208 registers allow, and a one-wave-per-SIMD build with 24 outputs and a
-// 12-deep queue in AGPRs is slower (0.68), 12 outputs per lane at three waves per SIMD the same (0.154-0.163 / 0.63).
-// Kept as BFIR_MAC64_VARIANT=12, not the default.
-template <typename T, bool ILV, int TT, int D, bool DCNY>
-__device__ __forceinline__ void mac_tstream_body(const MacArgs &a, int gc, int k, int t0)
-{
-    using V2 = typename Vec2<T>::type;
-    const int N = a.N, ring = a.ring;
-    const T *__restrict__ X = (const T *)a.x + (long)gc * a.x_ch_stride;
-    const T *__restrict__ H = (const T *)a.h + (long)gc * a.h_ch_stride;
-    T *__restrict__ Y = (T *)a.y + (long)gc * a.y_ch_stride;
-    const int nb = a.nblk[gc];
-    // (re, im) pairs (ILV: one load per value) or the reference's groups: 4 re then 4 im per 4 bins (two loads)
-    const int ore = ILV ? 2 * k : 8 * (k >> 2) + (k & 3), oim = ILV ? ore + 1 : ore + 4;
-    auto ld = [&](const T *base, T &re, T &im) {
-        if constexpr (ILV) { const V2 v = *(const V2 *)(base + ore); re = v.x; im = v.y; }
-        else { re = base[ore]; im = base[oim]; }
-    };
-    const int sl0 = (a.base_slot + t0) % ring;                    // delay-line slot of block t0
-    T wr[TT], wi[TT], ar[TT], ai[TT];
-#pragma unroll
-    for (int j = 0; j < TT; j++) {
-        int sj = sl0 + j; if (sj >= ring) sj -= ring;
-        ld(X + (long)sj * N, wr[j], wi[j]);
-        ar[j] = (T)0; ai[j] = (T)0;
-    }
-    // operand queue: step p needs h[p] and x[t0 - p] (p = 0: x[t0], already in the window; loaded anyway)
-    T qhr[D], qhi[D], qxr[D], qxi[D];
-    int ph = 0, sx = sl0;
-    auto fetch = [&](int d) {
-        const int pc = ph < nb ? ph : nb - 1;                     // clamped: in range, never used
-        ld(H + (long)pc * N, qhr[d], qhi[d]);
-        ld(X + (long)sx * N, qxr[d], qxi[d]);
-        ph += 1; sx -= 1; if (sx < 0) sx += ring;
-    };
-#pragma unroll
-    for (int d = 0; d < D; d++) fetch(d);
-    for (int p0 = 0; p0 < nb; p0 += TT) {
-        static_for<0, TT>([&](auto U_) {
-            constexpr int u = decltype(U_)::value;                // = p mod TT
-            if (p0 + u < nb) {                                    // uniform over the grid's channel
-                const T hr = qhr[u % D], hi = qhi[u % D], xr = qxr[u % D], xi = qxi[u % D];
-                fetch(u % D);
-                if (p0 + u > 0) { wr[(TT - u) % TT] = xr; wi[(TT - u) % TT] = xi; }   // block t0 - p takes the slot of t0 + TT - p
-                static_for<0, TT>([&](auto J_) {
-                    constexpr int j = decltype(J_)::value, idx = (j - u + TT) % TT;   // slot holding x[t0 + j - p]
-                    if constexpr (DCNY) {
-                        if (k == 0) {                             // bin 0: DC | Nyquist, two independent real sums
-                            ar[j] = fma(wr[idx], hr, ar[j]); ai[j] = fma(wi[idx], hi, ai[j]);
-                        } else {
-                            ar[j] = fma(wr[idx], hr, ar[j]); ar[j] = fma(-wi[idx], hi, ar[j]);
-                            ai[j] = fma(wr[idx], hi, ai[j]); ai[j] = fma(wi[idx], hr, ai[j]);
-                        }
-                    } else {
-                        ar[j] = fma(wr[idx], hr, ar[j]); ar[j] = fma(-wi[idx], hi, ar[j]);
-                        ai[j] = fma(wr[idx], hi, ai[j]); ai[j] = fma(wi[idx], hr, ai[j]);
-                    }
-                });
-            }
-        });
-    }
-#pragma unroll
-    for (int j = 0; j < TT; j++) {
-        const int t = t0 + j;
-        if (t < a.n_t) {
-            if constexpr (ILV) { V2 v; v.x = ar[j]; v.y = ai[j]; *(V2 *)(Y + (long)t * N + ore) = v; }
-            else { Y[(long)t * N + ore] = ar[j]; Y[(long)t * N + oim] = ai[j]; }
-        }
-    }
-}
-
-template <typename T, bool ILV, int TT, int D, int WPS>
-__global__ __launch_bounds__(256, WPS) void k_mac_tstream(MacArgs a, int ncol, int ntile)
-{
-    static_assert(TT % D == 0, "the queue slot of a step is its index mod D in every round");
-    // XCD-aware bijective remap: (channel, bin column) major, time tile minor
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
-    const int s = w / ntile, tile = w - s * ntile;
-    const int gc = s / ncol, col = s - gc * ncol;
-    const int k = col * 256 + (int)threadIdx.x;
-    if (col == 0) mac_tstream_body<T, ILV, TT, D, true>(a, gc, k, tile * TT);
-    else mac_tstream_body<T, ILV, TT, D, false>(a, gc, k, tile * TT);
-}
-
-template <typename T, bool ILV, int TT, int D, int WPS> static void launch_mac_tstream(const MacArgs &a, hipStream_t s)
-{
-    const int ncol = a.N / 2 / 256, ntile = (a.n_t + TT - 1) / TT;     // N >= 512
-    hipLaunchKernelGGL((k_mac_tstream<T, ILV, TT, D, WPS>), dim3(ncol * ntile * a.n_ch), dim3(256), 0, s, a, ncol, ntile);
 }
 
 // ---------------------------------------------------------------------------
@@ -2160,74 +1905,51 @@ static void launch_mac_small(const MacArgs &a, hipStream_t s)
     }
 }
 
+// The MAC dispatch, first match wins (measurements, and the kernels tried and removed: DESIGN.md §MAC, profiles/):
+//   1. at most BFIR_MAC_SMALL_MAX output blocks: k_mac_small
+//   2. the systolic kernel (mac_sys.hip, up to 256 partitions): fp64, and fp32 on pairs with 17-24 or 33-64 partitions
+//   3. fp32 on pairs: k_mac_lds (LDS-shared) past one register batch (B > 32, 32 blocks or more), else k_mac_stream
+//      in batches of up to 32 partitions
+//   4. fp32 grouped (N < 512): the register-tiled k_mac<float>
+//   5. fp64 grouped: k_mac_lds_d2g<2, 1> from 32 blocks, k_mac_lds_d<2> from 16, else the register-tiled k_mac<double>
+// fp64 on pairs has no kernel but the systolic one.  Switches, read per launch (the tests switch them in-process):
+// BFIR_NO_MAC_SMALL skips 1; BFIR_MAC_SYS=1 / 0 forces / forbids 2; BFIR_MAC_BATCHED forbids 2 and k_mac_lds.
 void launch_mac(const MacArgs &a, hipStream_t s)
 {
     if (a.n_t <= 0 || a.n_ch <= 0) return;
     const int tt = a.n_t;
-    if (tt <= BFIR_MAC_SMALL_MAX && !getenv("BFIR_NO_MAC_SMALL")) { launch_mac_small(a, s); return; }   // env: A/B and tests
-    {   // The forward-walking systolic kernel (mac_sys.hip: up to 256 partitions; fp32 on the pairs layout, fp64 on either):
-        // the default for fp64 (cfg5 +14 %, its MAC -27 % against the LDS-tiled kernel) and for fp32 with 33 to
-        // 64 partitions (+1..5 % against k_mac_lds; with eight lanes per bin, 65 to 128 partitions, it is 10 % SLOWER:
-        // 44.7 against 49.6 Gsamples/s at 8 channels x 128 partitions of 1024); with up to 32 partitions k_mac_stream stays
-        // ahead (0.49 against 0.59 ms per 4096 headline blocks: two lanes per bin double the vector-memory instructions
-        // per FMA, profiles/r03_mac_sys.txt) -- except at 17 to 24 partitions, where it pays for a register batch of 32 and two
-        // stages of twelve do not (MAC 0.49 -> 0.45 ms, 116.2 -> 118.3 Gsamples/s at the headline's shape with 24 partitions).
-        // BFIR_MAC_SYS=1 / 0 forces / forbids it; read per launch (tests switch it).
-        const char *ms = getenv("BFIR_MAC_SYS");
-        const bool want = ms ? atoi(ms) != 0 : (a.realsize == 8 || (a.B > 32 && a.B <= 64) || (a.B > 16 && a.B <= 24)) && !getenv("BFIR_MAC64_VARIANT") && mac_variant() == 0;
-        if (want && mac_sys_supported(a) && !getenv("BFIR_MAC_BATCHED")) { launch_mac_sys(a, s); return; }
-        // an fp64 engine on (re, im) pairs (engine.hip picks that layout only where this kernel serves it, and looks at the
-        // same switches when it does): no other fp64 MAC kernel reads pairs
-        if (a.realsize == 8 && a.interleaved) {
-            if (mac_sys_supported(a)) launch_mac_sys(a, s);
-            else fprintf(stderr, "bfir: fp64 engine on the pairs layout outside the systolic MAC's range (B = %d): launch skipped\n", a.B);
-            return;
-        }
+    if (tt <= BFIR_MAC_SMALL_MAX && !getenv("BFIR_NO_MAC_SMALL")) { launch_mac_small(a, s); return; }
+    const bool batched = getenv("BFIR_MAC_BATCHED") != nullptr;
+    // systolic: fp64 cfg5 +14 % (its MAC -27 %) against the LDS-tiled kernels; fp32 33-64 partitions +1..5 % against
+    // k_mac_lds, 17-24 116.2 -> 118.3 Gsamples/s against k_mac_stream, which stays ahead at up to 16 and at 25-32
+    // (profiles/r03_mac_sys.txt); 65-128 is 10 % slower
+    const char *ms = getenv("BFIR_MAC_SYS");
+    const bool want = ms ? atoi(ms) != 0 : (a.realsize == 8 || (a.B > 32 && a.B <= 64) || (a.B > 16 && a.B <= 24));
+    if (want && mac_sys_supported(a) && !batched) { launch_mac_sys(a, s); return; }
+    // an fp64 engine on (re, im) pairs (engine.hip picks that layout only where this kernel serves it, and looks at the
+    // same switches when it does): no other fp64 MAC kernel reads pairs
+    if (a.realsize == 8 && a.interleaved) {
+        if (mac_sys_supported(a)) launch_mac_sys(a, s);
+        else fprintf(stderr, "bfir: fp64 engine on the pairs layout outside the systolic MAC's range (B = %d): launch skipped\n", a.B);
+        return;
     }
-    if (a.realsize == 4) {
-        const int v = mac_variant();
-        // time-streaming kernel: PB partitions of a bin in registers per batch, whole 256-bin columns
-        const int pb = a.B <= 4 ? 4 : a.B <= 8 ? 8 : a.B <= 16 ? 16 : 32;
-        const bool batched_only = getenv("BFIR_MAC_BATCHED") != nullptr;   // tuning aid / test hook, read per launch
-        // (k_mac_tstream on the pair layout -- 24 or 32 outputs per lane -- was measured here: +1..5 % over the LDS kernel,
-        // profiles/r02_fp64_mac.txt; not worth a minute of build time per instantiation, so not kept)
-        if (a.interleaved && a.B > 32 && tt >= 32 && !batched_only) {
-            // more partitions than one register batch: the LDS-shared kernel on the pair layout beats
-            // re-reading X and Y once per batch of 32 (profiles/r01_other_configs.txt)
-            launch_mac_lds<8, true>(a, s);
-            return;
-        }
-        if (a.interleaved) {                          // the engine picked the pair layout (fp32, N >= 512)
-            if (pb == 4) launch_mac_stream<4, 4>(a, s);
-            else if (pb == 8) launch_mac_stream<8, 8>(a, s);
-            else if (pb == 16) launch_mac_stream<16, 8>(a, s);
-            else launch_mac_stream<32, 8>(a, s);
-            return;
-        }
-        const bool lds_ok = a.N >= 512 && tt >= 32;   // 64-group tiles, 32-block time tiles
-        if (lds_ok && (v == 0 || v == 8)) launch_mac_lds<8>(a, s);
-        else if (lds_ok && v == 6) launch_mac_lds<4>(a, s);
-        else if (lds_ok && v == 7) launch_mac_lds<2>(a, s);
-        else if (tt >= 8 && v == 1) launch_mac_t<float, 8, 2, 1>(a, s);
-        else if (tt >= 4 && v == 4) launch_mac_t<float, 4, 3, 2>(a, s);
-        else if (tt >= 8) launch_mac_t<float, 8, 2, 2>(a, s);   // measured best (profiles/r01_mac_variants.txt)
+    if (a.realsize == 4 && a.interleaved) {
+        // past one register batch, sharing the operands through LDS beats re-reading X and Y once per batch of 32
+        // (profiles/r01_other_configs.txt)
+        if (a.B > 32 && tt >= 32 && !batched) launch_mac_lds<8>(a, s);
+        else if (a.B <= 4) launch_mac_stream<4, 4>(a, s);
+        else if (a.B <= 8) launch_mac_stream<8, 8>(a, s);
+        else if (a.B <= 16) launch_mac_stream<16, 8>(a, s);
+        else launch_mac_stream<32, 8>(a, s);
+    } else if (a.realsize == 4) {
+        if (tt >= 8) launch_mac_t<float, 8, 2, 2>(a, s);   // measured best (profiles/r01_mac_variants.txt)
         else if (tt >= 4) launch_mac_t<float, 4, 3, 1>(a, s);
         else if (tt >= 2) launch_mac_t<float, 2, 4, 1>(a, s);
         else launch_mac_t<float, 1, 4, 1>(a, s);
     } else {
-        const int v64 = getenv("BFIR_MAC64_VARIANT") ? atoi(getenv("BFIR_MAC64_VARIANT")) : 0;   // tuning aid, read per launch
-        if (a.N >= 512 && tt >= 32 && v64 == 0) launch_mac_lds_d2g<2, 1>(a, s);  // two bins per lane, 32-block tiles, two partitions per barrier
-        else if (a.N >= 512 && tt >= 16 && v64 == 12) launch_mac_tstream<double, false, 16, 4, 2>(a, s);   // partition-streaming, registers only
-        else if (a.N >= 512 && tt >= 32 && v64 == 7) launch_mac_lds_d2<2>(a, s);      // ... a barrier per partition
-        else if (a.N >= 512 && tt >= 32 && v64 == 8) launch_mac_lds_d2g<4, 1>(a, s);  // ... four partitions per barrier
-        else if (a.N >= 512 && tt >= 32 && v64 == 9) launch_mac_lds_d2g<2, 2>(a, s);  // ... two, loads two groups ahead (no gain:
-                                                                                      // 0.564 vs 0.573 ms; four ahead 0.566; the loads are not what it waits for)
-        else if (a.N >= 512 && tt >= 32 && v64 == 4) launch_mac_lds_d2<4>(a, s);
-        else if (a.N >= 512 && tt >= 32 && v64 == 5) launch_mac_lds_d2<1>(a, s);
-        else if (a.N >= 512 && tt >= 16 && (v64 == 0 || v64 == 6)) launch_mac_lds_d<2>(a, s);
-        else if (a.N >= 512 && tt >= 16 && v64 == 2) launch_mac_lds_d<4>(a, s);
-        else if (a.N >= 512 && tt >= 16 && v64 == 3) launch_mac_lds_d<1>(a, s);
-        else if (tt >= 4) launch_mac_t<double, 4, 1, 1>(a, s);   // 1 wave/SIMD: the 2-wave build spills to scratch
+        if (a.N >= 512 && tt >= 32) launch_mac_lds_d2g<2, 1>(a, s);   // two bins per lane, two partitions per barrier
+        else if (a.N >= 512 && tt >= 16) launch_mac_lds_d<2>(a, s);
+        else if (tt >= 4) launch_mac_t<double, 4, 1, 1>(a, s);        // 1 wave/SIMD: the 2-wave build spills to scratch
         else if (tt >= 2) launch_mac_t<double, 2, 3, 1>(a, s);
         else launch_mac_t<double, 1, 4, 1>(a, s);
     }

@@ -357,21 +357,15 @@ bool mac_sys_supported(const MacArgs &a)
 // all the same (the stages of a bin are lanes of one wave), so the steps are kept at a quarter: PL = 12 between the powers of
 // two (the plug-in cuts whatever impulse file it is given into 1024-sample partitions, foo_dsp_bfir.cpp:275-276: any count
 // occurs).  fp64: prefetch depth 6 with 16 partitions per stage (160 registers, three waves per SIMD; measured best, cfg5
-// 39.7 against 39.2 with 4 and 39.4 with 8, the plug-in's shape 43.3 / 40.1 / 43.7, profiles/r03_fp64.txt; BFIR_SYS_D
-// overrides at 33 ... 64 partitions), 4 with 12 (128 registers: four waves).
+// 39.7 against 39.2 with 4 and 39.4 with 8, the plug-in's shape 43.3 / 40.1 / 43.7, profiles/r03_fp64.txt;
+// the depth 4 / 8 kernels are removed, see git history), 4 with 12 (128 registers: four waves).
 template <bool ILV> static void launch_sys_f64(const MacArgs &a, hipStream_t s)
 {
     if (a.B <= 16) launch_sys<double, ILV, 2, 8, 4>(a, s);
     else if (a.B <= 24) launch_sys<double, ILV, 2, 12, 4>(a, s);
     else if (a.B <= 32) launch_sys<double, ILV, 2, 16, 4>(a, s);
     else if (a.B <= 48) launch_sys<double, ILV, 4, 12, 4>(a, s);
-    else if (a.B <= 64) {
-        const char *de = getenv("BFIR_SYS_D");
-        const int d = de ? atoi(de) : 6;
-        if (d >= 8) launch_sys<double, ILV, 4, 16, 8>(a, s);
-        else if (d == 6) launch_sys<double, ILV, 4, 16, 6>(a, s);
-        else launch_sys<double, ILV, 4, 16, 4>(a, s);
-    }
+    else if (a.B <= 64) launch_sys<double, ILV, 4, 16, 6>(a, s);
     else if (a.B <= 96) launch_sys<double, ILV, 8, 12, 4>(a, s);
     else if (a.B <= 128) launch_sys<double, ILV, 8, 16, 6>(a, s);    // eight stages: 65 ... 128 partitions
     else if (a.B <= 192) launch_sys<double, ILV, 16, 12, 4>(a, s);   // sixteen stages, one DPP row per bin: 129 ... 256 partitions

@@ -491,21 +491,30 @@ def test_small_launch_mac_kernel_gives_the_bits_of_the_throughput_kernels(orc, b
     assert rel_err(outs[0], ref.run(x)[1]) <= TOL[s]
 
 
-@pytest.mark.parametrize("variant", ["7", "8", "9", "12"])
-def test_fp64_mac_variants_give_identical_bits(orc, bfir, variant):
-    """BFIR_MAC64_VARIANT (tuning aid, read per launch) selects other fp64 MAC kernels -- a barrier per partition,
-    four partitions per barrier, deeper prefetch, the register-only partition-streaming kernel: the same chain of
-    fused multiply-adds per bin, so the same bits as the default kernel."""
-    import os
-    L, B, C, nb = 1024, 37, 2, 72          # 72 blocks: two 32-block tiles and a ragged third (16-block tiles: 4 and a half)
+# the fp64 MAC kernels besides the default (the systolic kernel on (re, im) pairs) at L = 1024, B = 37, 72 blocks
+FP64_MACS = [
+    ("lds_d2g", {"BFIR_MAC_SYS": "0"}, 72),        # k_mac_lds_d2g: 32-block tiles, two and a ragged third
+    ("lds_d", {"BFIR_MAC_SYS": "0"}, 24),          # k_mac_lds_d<2>: 16 to 31 blocks per launch
+    ("k_mac", {"BFIR_MAC_SYS": "0"}, 8),           # the register-tiled k_mac<double>: 5 to 15 (up to 4: k_mac_small)
+    ("sys_grouped", {"BFIR_F64_PAIRS": "0"}, 72),  # the systolic kernel on the grouped layout
+]
+
+
+@pytest.mark.parametrize("env,chunk", [m[1:] for m in FP64_MACS], ids=[m[0] for m in FP64_MACS])
+def test_fp64_mac_variants_give_identical_bits(orc, bfir, env, chunk):
+    """Every fp64 MAC kernel runs the same chain of fused multiply-adds per bin in the same partition order, so each
+    gives the same bits as the default.  The switches are read at engine creation and per launch: the engine is made and
+    run inside the override."""
+    L, B, C, nb = 1024, 37, 2, 72
     rng = np.random.default_rng(12)
     h = orc.synth_ir(rng, C, B * L - 9, np.float64)
     x = orc.synth_audio(rng, nb * L, C, np.float64)
+    default = {"BFIR_MAC_SYS": None, "BFIR_MAC_BATCHED": None, "BFIR_F64_PAIRS": None}   # whatever the run's switches
     outs = []
-    for v in (None, variant):
-        with env_override(**({} if v is None else {"BFIR_MAC64_VARIANT": v})):
+    for sw, ch in ((default, nb), ({**default, **env}, chunk)):
+        with env_override(**sw):
             eng = bfir.Brutefir(L, B, 8, C)
-            eng.set_chunk(nb)
+            eng.set_chunk(ch)
             assert eng.set_coeff(h) == 0
             outs.append(eng.run(x)[1])
             eng.close()

@@ -1,8 +1,8 @@
 """k_mac_sys (csrc/mac_sys.hip): the forward-walking form of the partition sums, S adjacent lanes per bin.
 
 Every output is ONE fused multiply-add chain over the partitions in the reference's order (brutefir/brutefir.cpp:
-288-299, fftw_convolver.cpp:1464-1525 / 2160-2220), exactly the chain of the default MAC kernels (k_mac_stream,
-k_mac_lds on the pair layout, the fp64 LDS kernel) -- so it must agree with them BIT FOR BIT on every block, whatever
+288-299, fftw_convolver.cpp:1464-1525 / 2160-2220), exactly the chain of the other MAC kernels (k_mac_stream,
+k_mac_lds, the fp64 LDS kernels) -- so it must agree with them BIT FOR BIT on every block, whatever
 the launch geometry: run lengths that are no multiple of the slot group, runs shorter than the filter, the ring wrap
 inside a run (the stages pass it PL + 1 slots apart), partition counts below S PL (zero partitions), ragged last
 partitions, several engines, call-to-call continuation, two / four / eight / sixteen lanes per bin, fp32 (pairs layout) and fp64

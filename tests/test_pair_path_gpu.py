@@ -132,14 +132,15 @@ def test_more_partitions_than_one_register_batch(orc, bfir, L, B, C, nb, chunk):
     # chunking stays bit-exact across the batches
     eng2 = bfir.Brutefir(L, B, 4, C); eng2.set_chunk(nb); eng2.set_coeff(h)
     assert np.array_equal(eng2.run(x)[1], y)
-    # and the batched sums are the very sums of the grouped-layout MAC kernels (general path for both)
-    with env_override(BFIR_PAIR="0"):
-        a = bfir.Brutefir(L, B, 4, C)
-        with env_override(BFIR_MAC_VARIANT="8"):
-            b = bfir.Brutefir(L, B, 4, C)
-    for e in (a, b):
-        e.set_chunk(chunk); e.set_coeff(h)
-    assert np.array_equal(a.run(x)[1], b.run(x)[1])
+    # and the batched sums are the very sums of the default MAC kernel -- the systolic one for B = 40 / 33, k_mac_lds
+    # for B = 70 at chunk 32 -- on the same (general) path; BFIR_MAC_BATCHED is read per launch
+    outs = []
+    for batched in (None, "1"):
+        with env_override(BFIR_PAIR="0", BFIR_MAC_SYS=None, BFIR_MAC_BATCHED=batched):
+            e = bfir.Brutefir(L, B, 4, C); e.set_chunk(chunk); e.set_coeff(h)
+            outs.append(e.run(x)[1])
+            e.close()
+    assert np.array_equal(outs[0], outs[1])
 
 
 def test_automatic_chunk_equals_explicit_chunks(orc, bfir):
