@@ -66,7 +66,7 @@ def resource_usage():
 
 def _flags_changed():
     """The flags the objects in lib/ were built with are recorded beside them: a library built with
-    other flags (a -DBFIR_TRACE tuning build, an A/B variant) is stale for this build."""
+    other flags (BFIR_EXTRA_FLAGS, an A/B build) is stale for this build."""
     try:
         return open(FLAGS_FILE).read() != " ".join(FLAGS)
     except OSError:
@@ -108,32 +108,6 @@ def build(force=False, verbose=False):
     with open(FLAGS_FILE, "w") as f:
         f.write(" ".join(FLAGS))
     return LIB
-
-
-def build_variant(name, extra_flags, verbose=False, only=None):
-    """Tuning aid: a second build of the library with extra hipcc flags (-D experiment switches) into
-    lib/variant_<name>/ -> lib/libbfir_hip_<name>.so, leaving the product library alone.  Select it for
-    one process with BFIR_LIB_OVERRIDE (A/B timing of two builds inside one gpurun call).
-    only: recompile just these sources with the extra flags and link the product build's objects for the rest."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    vdir = os.path.join(LIBDIR, "variant_" + name)
-    os.makedirs(vdir, exist_ok=True)
-    flags = [f for f in FLAGS] + list(extra_flags)
-    objs, jobs = [], []
-    for src in SOURCES:
-        if only is not None and src not in only:
-            objs.append(os.path.join(LIBDIR, src.replace(".hip", ".o")))
-            continue
-        o = os.path.join(vdir, src.replace(".hip", ".o"))
-        jobs.append([hipcc] + flags + ["-c", os.path.join(CSRC, src), "-o", o])
-        objs.append(o)
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=4) as pool:
-        for r in pool.map(lambda c: subprocess.run(c, check=True), jobs):
-            pass
-    out = os.path.join(LIBDIR, "libbfir_hip_%s.so" % name)
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-o", out] + objs, check=True)
-    return out
 
 
 if __name__ == "__main__":

@@ -275,9 +275,9 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
     e->ilv = realsize == 4 && e->N >= 512;   // fp32: (re, im) pairs from N = 512 (whole 256-bin columns)
     {   // BFIR_PAIR=0 (tuning aid) keeps the planar staging kernels
         const char *pv = getenv("BFIR_PAIR");
-        // the persistent kernels only (BFIR_PAIR_PERSIST=0 keeps odd channel counts on the general path)
-        const char *pp = getenv("BFIR_PAIR_PERSIST"), *tv = getenv("BFIR_PAIR_TIME");
-        const bool tp_ok = !(pp && atoi(pp) != 1) && !(tv && atoi(tv) == 0);
+        // odd channel counts pair blocks in time (BFIR_PAIR_TIME=0 keeps them on the general path)
+        const char *tv = getenv("BFIR_PAIR_TIME");
+        const bool tp_ok = !(tv && atoi(tv) == 0);
         e->pair_tp = (channels % 2) == 1 && tp_ok;
         e->pair = e->ilv && in_format == 8 && out_format == 8 && ((channels % 2) == 0 || e->pair_tp) &&
                   pair_supported(filter_length) && !(pv && atoi(pv) == 0);

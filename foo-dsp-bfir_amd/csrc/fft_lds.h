@@ -29,28 +29,6 @@
 
 #include <type_traits>
 
-// -DBFIR_TRACE (tuning builds only, scripts/gpu_trace.sh): thread 0 of every workgroup stamps the
-// 100 MHz wall clock at phase boundaries into a device array read back by bfir_debug_read_trace.
-#ifdef BFIR_TRACE
-#define BFIR_TRACE_SLOTS 24
-#define BFIR_TRACE_WGS 4096
-static __device__ unsigned long long g_trace[3][BFIR_TRACE_WGS * BFIR_TRACE_SLOTS];
-#define BFIR_STAMP(kern, n)                                                                        \
-    do {                                                                                           \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                               \
-        if (threadIdx.x == 0 && blockIdx.x < BFIR_TRACE_WGS)                                       \
-            g_trace[kern][blockIdx.x * BFIR_TRACE_SLOTS + (n)] = wall_clock64();                   \
-        __builtin_amdgcn_sched_barrier(0);                                                         \
-    } while (0)
-#else
-#define BFIR_STAMP(kern, n) do { } while (0)
-#endif
-
-#ifndef BFIR_F64_EARLY_TW
-#define BFIR_F64_EARLY_TW(lg) ((lg) >= 12)
-#endif
-
 namespace bfir {
 
 // Force the values to exist in registers at this point of the program.  LLVM's sinking passes
@@ -267,13 +245,8 @@ template <typename T, int LOG2M, int SIGN> struct LdsFft {
     // access pattern of the passes then is "per-thread base + compile-time offset"
     // (no per-element address arithmetic); all of them are bank-conflict free
     // except the stride-R writes of the first pass (2-way).
-#ifdef BFIR_FFT_XOR_SWIZZLE   // A/B switch: conflict-free XOR layout, exactly M elements (5 workgroups per CU at M = 4096 fp32)
-    static constexpr int LDS_ELEMS = M;
-    __host__ __device__ __forceinline__ static constexpr int phys(int i) { return i ^ ((i >> 4) & 15); }
-#else
     static constexpr int LDS_ELEMS = M + M / 32;
     __host__ __device__ __forceinline__ static constexpr int phys(int i) { return i + (i >> 5); }
-#endif
 
     // logical index held in register slot e before pass 0
     __host__ __device__ __forceinline__ static constexpr int in_index(int tid, int e)
@@ -329,7 +302,7 @@ template <typename T, int LOG2M, int SIGN> struct LdsFft {
     __device__ __forceinline__ static void pass(T *re, T *im, V2 *lds, const V2 *__restrict__ tw, int tid)
     {
         V2 w[ntw<S>()];
-        if constexpr (sizeof(T) == 4 || BFIR_F64_EARLY_TW(LOG2M)) {
+        if constexpr (sizeof(T) == 4 || LOG2M >= 12) {
             load_twiddles<S>(w, tw, tid);
             exchange<S - 1>(re, im, lds, tid);
         } else {
@@ -516,16 +489,13 @@ template <typename T, int LOG2M, int SIGN> struct LdsFft {
     // Full transform of the P register points (in_index order in, out_index order out).
     __device__ __forceinline__ static void run(T *re, T *im, V2 *lds, const V2 *__restrict__ tw, int tid)
     {
-        constexpr int TK = SIGN < 0 ? 0 : 1;   // trace array: forward / inverse
         {
             V2 w0[1];
             butterflies<0>(re, im, w0);
         }
-        BFIR_STAMP(TK, 2);
-        if constexpr (NP > 1) { pass<1>(re, im, lds, tw, tid); BFIR_STAMP(TK, 4); }
-        if constexpr (NP > 2) { pass<2>(re, im, lds, tw, tid); BFIR_STAMP(TK, 6); }
-        if constexpr (NP > 3) { pass<3>(re, im, lds, tw, tid); BFIR_STAMP(TK, 8); }
-        (void)TK;
+        if constexpr (NP > 1) pass<1>(re, im, lds, tw, tid);
+        if constexpr (NP > 2) pass<2>(re, im, lds, tw, tid);
+        if constexpr (NP > 3) pass<3>(re, im, lds, tw, tid);
     }
 };
 

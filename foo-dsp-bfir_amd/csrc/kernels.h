@@ -140,31 +140,13 @@ struct MacArgs {
     int n_t, n_ch, N, realsize;
     int B = 0;                                     // partitions allocated per channel (max of nblk)
     int interleaved = 0;                           // layout of x, h and y, as in FwdArgs (fp32 streaming kernel only)
-#ifdef BFIR_EXPERIMENT_ALIAS
-    int y_alias = 1 << 30;                         // timing experiment: product spectrum t lives in slot t % y_alias
-#endif
 };
 // Cache policy of the two big streams, the delay line X and the product spectra Y (each written once and read
-// once, a gigabyte apart): bit 0 = stores nontemporal, bit 1 = loads nontemporal (-DBFIR_NT_X=n / -DBFIR_NT_Y=n;
-// persistent pair kernels and the streaming MAC).  All four on is the product setting: +4 % on the headline
-// pipeline (112.1 vs 107.5 Gsamples/s, same box; any three of them +1.5..3 %, profiles/r02_nt_policy.txt) --
-// the lines of the interleaved input / output frames, of which every workgroup uses a quarter, then
-// survive in L2 until the other three channel pairs have come by.  No effect on small launches.
-#ifndef BFIR_NT_X
-#define BFIR_NT_X 3
-#endif
-#ifndef BFIR_NT_Y
-#define BFIR_NT_Y 3
-#endif
-#ifdef BFIR_EXPERIMENT_ALIAS
-// Timing experiment (scripts/gpu_alias_exp.sh): BFIR_X_ALIAS / BFIR_Y_ALIAS fold the delay line / the product
-// spectra into that many slots, so that they stay in the caches.  Results are garbage; instruction streams
-// and launch geometry are those of the product build.  Never defined in the product library.
-#define BFIR_YSLOT(a, t) ((t) % (a).y_alias)
-inline int bfir_alias_env(const char *name) { const char *e = getenv(name); return e && atoi(e) > 0 ? atoi(e) : 0; }
-#else
-#define BFIR_YSLOT(a, t) (t)
-#endif
+// once, a gigabyte apart): the persistent pair kernels and the streaming MAC load and store both nontemporal.
+// That is +4 % on the headline pipeline against cached stores and loads (112.1 vs 107.5 Gsamples/s, same box;
+// any three of the four nontemporal +1.5..3 %, profiles/r02_nt_policy.txt) -- the lines of the interleaved
+// input / output frames, of which every workgroup uses a quarter, then survive in L2 until the other three
+// channel pairs have come by.  No effect on small launches.
 void launch_mac(const MacArgs &a, hipStream_t s);
 // mac_sys.hip: the forward-walking two-lanes-per-bin form of the fp32 pair-layout MAC (B <= 32)
 constexpr int BFIR_MAC_SYS_MAX_B = 256;   // partitions the systolic MAC takes (sixteen stages of sixteen)
@@ -222,9 +204,6 @@ struct InvPairArgs {
     int *bad_host = nullptr;                             // as in StageOutArgs
     long of_shard_stride = 0;
     int tp = 0;                                          // pairs in time, as in FwdPairArgs
-#ifdef BFIR_EXPERIMENT_ALIAS
-    int y_alias = 1 << 30;
-#endif
 };
 void launch_inv_pair(const FftPlan &plan, const InvPairArgs &a, hipStream_t s);
 

@@ -201,7 +201,6 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_fwd(FwdArgs a,
     T *__restrict__ dst =
         (T *)a.dst + (long)gc * a.dst_ch_stride + (long)((a.base_slot + t) % a.ring) * N;
 
-    BFIR_STAMP(0, 0);
     // z[m] = x[2m] + i x[2m+1] over the window [previous block | this block]
     T re[P], im[P];
     const T ls = (T)a.load_scale;
@@ -304,7 +303,6 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_fwd(FwdArgs a,
         }
     }
 
-    BFIR_STAMP(0, 1);
     F::run(re, im, lds, tw, tid);
 
     // Z in natural order to LDS so every thread can fetch Z[M-k]
@@ -330,7 +328,6 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_fwd(FwdArgs a,
         re[e] = xr * os; im[e] = xi * os;
     }
     pin_registers(re, im);   // every Z[M-k] read happens before the barrier
-    BFIR_STAMP(0, 9);
     __syncthreads();
     T *ldsr = (T *)lds;
 #pragma unroll
@@ -350,15 +347,14 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_fwd(FwdArgs a,
         const int idx = tid + j * NT;
         ((V4 *)dst)[idx] = ((const V4 *)ldsr)[idx];
     }
-    BFIR_STAMP(0, 10);
 }
 
 // ---------------------------------------------------------------------------
 // k_fwd_run: the forward kernel of fp64 engines in direct mode, one channel per workgroup, as a RUN of blocks
 // ---------------------------------------------------------------------------
 // A 4096-point double transform holds 66 KB of LDS: two workgroups of four waves per CU, and nothing hides the latency of
-// the frame loads in front of every transform (scripts/trace_phases_f64.py: 6.6 of a workgroup's 22.7 us in cfg5, the
-// frames being 8 bytes at a 16-byte stride).  Here a workgroup walks run_len consecutive blocks of ONE channel:
+// the frame loads in front of every transform (phase trace, profiles/r03_fp64.txt: 6.6 of a workgroup's 22.7 us in cfg5,
+// the frames being 8 bytes at a 16-byte stride).  Here a workgroup walks run_len consecutive blocks of ONE channel:
 //   * the window's first half is the block it transformed last -- kept in registers, never loaded again;
 //   * block t + 1 is fetched under the split and the stores of block t.  Vector-memory operations return in order, so a
 //     twiddle load issued behind that fetch would wait for it: the twiddles come from a handful of BASES instead, loaded once per
@@ -704,7 +700,6 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_inv(InvArgs a,
     T *__restrict__ dst =
         (T *)a.dst + (long)gc * a.dst_ch_stride + (long)t * (a.full_output ? N : M);
 
-    BFIR_STAMP(1, 0);
     T *ldsr = (T *)lds;
 #pragma unroll
     for (int j = 0; j < P / 2; j++) {
@@ -712,7 +707,6 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_inv(InvArgs a,
         ((V4 *)ldsr)[idx] = ((const V4 *)src)[idx];
     }
     __syncthreads();
-    BFIR_STAMP(1, 9);
 
     // Z_k = (X_k + conj X_{M-k}) + i conj(W^k) (X_k - conj X_{M-k})
     T re[P], im[P];
@@ -737,7 +731,6 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_inv(InvArgs a,
     }
     pin_registers(re, im);   // every read of the staged spectrum happens before run()'s first barrier
 
-    BFIR_STAMP(1, 1);
     F::run(re, im, lds, tw, tid);
 
     if constexpr (DIRECT) {
@@ -818,7 +811,6 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_inv(InvArgs a,
             *(V2 *)(dst + 2 * m) = v;
         }
     }
-    BFIR_STAMP(1, 10);
 }
 
 // ---------------------------------------------------------------------------
@@ -1620,25 +1612,18 @@ template <int D> static void launch_mac_lds_d(const MacArgs &a, hipStream_t s)
 // previous batch left in Y; those are fetched D blocks ahead like the spectra (yq, ty_next).
 __device__ __forceinline__ float2 mac_ld_x(const float2 *p)
 {
-#if BFIR_NT_X & 2
     typedef float f2v __attribute__((ext_vector_type(2)));
     const f2v v = __builtin_nontemporal_load((const f2v *)p);
     float2 r; r.x = v.x; r.y = v.y; return r;
-#else
-    return *p;
-#endif
 }
 __device__ __forceinline__ void mac_st_y(float2 *p, float2 v)
 {
-#if BFIR_NT_Y & 1
     typedef float f2v __attribute__((ext_vector_type(2)));
     f2v w; w.x = v.x; w.y = v.y;
     __builtin_nontemporal_store(w, (f2v *)p);
-#else
-    *p = v;
-#endif
 }
 
+// `a` is not read, but without it hipcc emits different code for k_mac_stream (it loads nblk through the scalar cache)
 template <int PB, int D, int MODE, bool ACC>
 __device__ __forceinline__ void mac_stream_group(float (&ar)[PB], float (&ai)[PB], const float (&hr)[PB],
                                                  const float (&hi)[PB], float2 (&q)[D], float2 (&yq)[ACC ? D : 1],
@@ -1682,7 +1667,7 @@ __device__ __forceinline__ void mac_stream_group(float (&ar)[PB], float (&ai)[PB
             const int ty = tg + 2 * PB - 2 - u;
             if (ty < n_t && store_lane) {
                 float2 v; v.x = ar[sl]; v.y = ai[sl];
-                mac_st_y(Yc + (long)BFIR_YSLOT(a, ty) * N2 + k, v);
+                mac_st_y(Yc + (long)ty * N2 + k, v);
             }
         }
     });
@@ -1744,7 +1729,6 @@ __global__ __launch_bounds__(256, ACC ? 2 : 3) void k_mac_stream(MacArgs a, int 
     const int ta = r * ngrp * PB;
     const int my_grp = min(ngrp, (a.n_t - ta + PB - 1) / PB);
     const int R = my_grp * PB;
-    BFIR_STAMP(2, 0);
 
     float2 q[D];
     // newest block of the range first; batch p0 pairs output t with spectrum t - p0 - p
@@ -1776,27 +1760,18 @@ __global__ __launch_bounds__(256, ACC ? 2 : 3) void k_mac_stream(MacArgs a, int 
     for (int p = 0; p < PB; p++) { ar[p] = 0.f; ai[p] = 0.f; }
     const bool store_lane = k != 0;
     int tg = ta + R - PB;
-    BFIR_STAMP(2, 1);
     mac_stream_group<PB, D, 0, ACC>(ar, ai, hr, hi, q, yq, Xc, Yc, k, N2, ring, sq, ty_next, tg, a.n_t, store_lane, a);
-    BFIR_STAMP(2, 2);
     for (int g = my_grp - 2; g >= 0; g--) {
         tg -= PB;
         mac_stream_group<PB, D, 1, ACC>(ar, ai, hr, hi, q, yq, Xc, Yc, k, N2, ring, sq, ty_next, tg, a.n_t, store_lane, a);
     }
-    BFIR_STAMP(2, 3);
     tg -= PB;
     mac_stream_group<PB, D, 2, ACC>(ar, ai, hr, hi, q, yq, Xc, Yc, k, N2, ring, sq, ty_next, tg, a.n_t, store_lane, a);
-    BFIR_STAMP(2, 4);
 }
 
 // ngrp: groups of PB blocks per wave (BFIR_MAC_RANGE overrides, in blocks)
-template <int PB, int D> static void launch_mac_stream(const MacArgs &a_, hipStream_t s)
+template <int PB, int D> static void launch_mac_stream(const MacArgs &a, hipStream_t s)
 {
-    MacArgs a = a_;
-#ifdef BFIR_EXPERIMENT_ALIAS
-    if (const int xa = bfir_alias_env("BFIR_X_ALIAS")) { a.ring = xa; a.base_slot %= xa; }
-    if (const int ya = bfir_alias_env("BFIR_Y_ALIAS")) a.y_alias = ya;
-#endif
     // read per launch (a getenv is nanoseconds next to a launch) so tests can switch it in-process
     const char *re_ = getenv("BFIR_MAC_RANGE");
     const int range_env = re_ ? atoi(re_) : 0;
@@ -2445,14 +2420,3 @@ void launch_cmul_stage(const void *b, const void *c, void *d, int n_fft, int mod
 }
 
 }  // namespace bfir
-
-#ifdef BFIR_TRACE
-// tuning builds only: copy the phase stamps of kernel `kern` (0 k_fwd, 1 k_inv, 2 k_mac_lds)
-extern "C" int bfir_debug_read_trace(int kern, unsigned long long *out, int n_wgs)
-{
-    if (kern < 0 || kern > 2 || n_wgs > BFIR_TRACE_WGS) return -1;
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), sizeof(unsigned long long) * n_wgs * BFIR_TRACE_SLOTS,
-                                    sizeof(unsigned long long) * kern * BFIR_TRACE_WGS * BFIR_TRACE_SLOTS,
-                                    hipMemcpyDeviceToHost);
-}
-#endif

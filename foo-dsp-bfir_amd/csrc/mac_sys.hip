@@ -35,13 +35,6 @@
 
 #include "fft_lds.h"
 
-// -DBFIR_SYS_EXP=bits (timing experiments only, results garbage): 1 no partial-sum hand-over, 2 no relay of x to the next
-// stage, 4 no stores, 8 no loads, 16 no negated operand (all FMAs in the short encoding), 32 no tail test per slot.
-// Never defined in the product library.
-#ifndef BFIR_SYS_EXP
-#define BFIR_SYS_EXP 0
-#endif
-
 namespace bfir {
 
 namespace {
@@ -155,62 +148,41 @@ template <int S> __device__ __forceinline__ double hand_t(double v)
 template <typename T, bool ILV, int S, int PL, int D>
 __device__ __forceinline__ void sys_group(Cx<T> (&W)[PL + D], const T (&hr)[PL], const T (&hi)[PL], T &hand_r, T &hand_i,
                                           __amdgpu_buffer_rsrc_t rx, __amdgpu_buffer_rsrc_t ry, unsigned &so, unsigned xstep,
-                                          unsigned xwrap, unsigned kv, unsigned kvs, int tau0, int t_lo,
-                                          bool store_lane, int rem, const MacArgs &a)
+                                          unsigned xwrap, unsigned kv, unsigned kvs, int tau0, int t_lo, int rem)
 {
     constexpr int G = PL + D;
     static_assert(D >= 2, "entry u + 1 and entry u + D are different registers");
     static_assert(G >= S - 1, "only a run's first group has slots without a finished output");
     static_for<0, G>([&](auto U) {
         constexpr int u = decltype(U)::value;
-#if !(BFIR_SYS_EXP & 32)
         if (u >= rem) return;                                    // wave-uniform
-#endif
-#if !(BFIR_SYS_EXP & 2)
         {   // stage j's x[newest - PL] -> stage j + 1's newest of the next slot; stage 0 keeps what it loaded
             W[(u + 1) % G].x = relay_t<S>(W[(u + 1) % G].x, W[(u + D) % G].x);
             W[(u + 1) % G].y = relay_t<S>(W[(u + 1) % G].y, W[(u + D) % G].y);
         }
-#endif
-#if !(BFIR_SYS_EXP & 8)
-        W[(u + D) % G] = sys_load<T, ILV, (BFIR_NT_X & 2) ? 2 : 0>(rx, kv, so);   // stage 0's x[tau + D], D slots ahead
-#else
-        W[(u + D) % G].x += (T)1;
-#endif
+        W[(u + D) % G] = sys_load<T, ILV, 2>(rx, kv, so);       // stage 0's x[tau + D], D slots ahead (nontemporal)
         so += xstep; so = so >= xwrap ? so - xwrap : so;         // scalar
         T ar = hand_r, ai = hand_i;                              // stage 0: zero; stage j: the partial sum from below
         static_for<0, PL>([&](auto P) {
             constexpr int p = decltype(P)::value;
             const Cx<T> w = W[(u - p + G) % G];                  // p slots old
             ar = fma_t(w.x, hr[p], ar); ai = fma_t(w.x, hi[p], ai);
-#if !(BFIR_SYS_EXP & 16)
             ar = fma_t(-w.y, hi[p], ar); ai = fma_t(w.y, hr[p], ai);
-#else
-            ar = fma_t(w.y, hi[p], ar); ai = fma_t(w.y, hr[p], ai);
-#endif
             // keep the two chains interleaved (an independent instruction between dependent ones); a scheduling
             // barrier, not an empty asm: behind inline asm the hazard recogniser pads with s_nop
             __builtin_amdgcn_sched_barrier(0);
         });
         // the top stage holds the finished y[tau - (S - 1)]
         const int ty = tau0 + u - (S - 1);
-#if !(BFIR_SYS_EXP & 4)
         // the lanes below the top stage (and bin 0) carry a byte offset beyond the end of every product-spectra buffer
         // (kvs): the buffer range check drops their stores -- cheaper than an exec-mask round trip per slot
         // ty < t_lo only in the first S - 1 slots of a run's first group (the chain is still filling); ty < t_hi by the slot
         // count of the run.  A compile-time test for all other slots: every scalar instruction of a slot costs issue time here
         if (u >= S - 1 || tau0 != t_lo) {
             Cx<T> v; v.x = ar; v.y = ai;
-            sys_store<T, ILV, (BFIR_NT_Y & 1) ? 2 : 0>(ry, kvs, (unsigned)BFIR_YSLOT(a, ty) * xstep, v);
+            sys_store<T, ILV, 2>(ry, kvs, (unsigned)ty * xstep, v);   // nontemporal
         }
-#else
-        if (ty == -12345 && store_lane) { Cx<T> v; v.x = ar; v.y = ai; sys_store<T, ILV, 0>(ry, kv, 0, v); }
-#endif
-#if !(BFIR_SYS_EXP & 1)
         hand_r = hand_t<S>(ar); hand_i = hand_t<S>(ai);
-#else
-        hand_r = ar; hand_i = ai;
-#endif
     });
 }
 
@@ -259,7 +231,7 @@ __global__ __launch_bounds__(256, (sys_min_waves<T, PL, D>())) void k_mac_sys(Ma
             }
         }
         if (t < a.n_t) {
-            T *yo = (T *)a.y + (long)gc * a.y_ch_stride + (long)BFIR_YSLOT(a, t) * N;
+            T *yo = (T *)a.y + (long)gc * a.y_ch_stride + (long)t * N;
             yo[0] = dc; yo[NYQ] = ny;
         }
         return;
@@ -280,11 +252,7 @@ __global__ __launch_bounds__(256, (sys_min_waves<T, PL, D>())) void k_mac_sys(Ma
     // bytes per spectrum / per ring
     const unsigned xstep = (unsigned)N * (unsigned)sizeof(T), xwrap = (unsigned)ring * xstep;
     const __amdgpu_buffer_rsrc_t rx = sys_rsrc((const T *)a.x + (long)gc * a.x_ch_stride, xwrap);
-#ifdef BFIR_EXPERIMENT_ALIAS
-    const __amdgpu_buffer_rsrc_t ry = sys_rsrc((T *)a.y + (long)gc * a.y_ch_stride, (unsigned)min(a.n_t, a.y_alias) * xstep);
-#else
     const __amdgpu_buffer_rsrc_t ry = sys_rsrc((T *)a.y + (long)gc * a.y_ch_stride, (unsigned)a.n_t * xstep);
-#endif
 
     T hr[PL], hi[PL];
 #pragma unroll
@@ -312,20 +280,15 @@ __global__ __launch_bounds__(256, (sys_min_waves<T, PL, D>())) void k_mac_sys(Ma
     const unsigned kvs = store_lane ? kv : 0x80000000u;        // out of range: mac_sys_supported keeps the buffers below 2 GiB
     int left = t_hi - t_lo + (S - 1);                           // slots: the last output leaves the top stage S - 1 slots later
     for (int tau = t_lo; left > 0; tau += G, left -= G)
-        sys_group<T, ILV, S, PL, D>(W, hr, hi, hand_r, hand_i, rx, ry, so, xstep, xwrap, kv, kvs, tau, t_lo, store_lane, left, a);
+        sys_group<T, ILV, S, PL, D>(W, hr, hi, hand_r, hand_i, rx, ry, so, xstep, xwrap, kv, kvs, tau, t_lo, left);
 }
 
 }  // namespace
 
 // runs per (channel, bin column): enough workgroups for the waves per SIMD the kernel is built for, in one round
 // (BFIR_MAC_RANGE overrides the run length, in blocks; BFIR_SYS_WGS the workgroups in flight)
-template <typename T, bool ILV, int S, int PL, int D> static void launch_sys(const MacArgs &a_, hipStream_t s)
+template <typename T, bool ILV, int S, int PL, int D> static void launch_sys(const MacArgs &a, hipStream_t s)
 {
-    MacArgs a = a_;
-#ifdef BFIR_EXPERIMENT_ALIAS
-    if (const int xa = bfir_alias_env("BFIR_X_ALIAS")) { a.ring = xa; a.base_slot %= xa; }
-    if (const int ya = bfir_alias_env("BFIR_Y_ALIAS")) a.y_alias = ya;
-#endif
     const int ncol = a.N / 2 / (256 / S);
     const char *re_ = getenv("BFIR_MAC_RANGE");
     int R = re_ ? atoi(re_) : 0;

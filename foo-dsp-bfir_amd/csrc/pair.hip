@@ -38,176 +38,11 @@ __device__ __forceinline__ int xcd_remap()
     return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
 }
 
-template <int LOG2N>
-__global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_fwd_pair(FwdPairArgs a, const float2 *__restrict__ tw)
-{
-    using F = LdsFft<float, LOG2N, -1>;
-    constexpr int N = F::M, NT = F::NT, P = F::P, L = N / 2;
-    __shared__ __attribute__((aligned(16))) float2 lds[F::LDS_ELEMS];
-#ifdef BFIR_PAIR_LDS_PAD   // occupancy experiment: extra LDS so that fewer workgroups fit a CU
-    __shared__ volatile float occ_pad[BFIR_PAIR_LDS_PAD / 4];
-    if (a.n_t < 0) { occ_pad[threadIdx.x] = 1.f; a.scale += occ_pad[threadIdx.x ^ 1]; }
-#endif
-
-    const int tid = threadIdx.x;
-    const int w = xcd_remap();
-    const int half_c = a.C / 2, pairs = a.n_eng * half_c;
-    const int t = w / pairs, pp = w - t * pairs;
-    const int g = pp / half_c, cp = pp - g * half_c;
-    const int C = a.C;
-    // frames of block t of engine g, channel pair cp
-    const float *__restrict__ cur = a.raw + (long)g * a.eng_stride + (a.frame_off + (long)t * L) * C + 2 * cp;
-    const float *__restrict__ old = (t == 0) ? a.prev + (long)g * a.hist_eng_stride + 2 * cp : cur - (long)L * C;
-
-    BFIR_STAMP(0, 0);
-    float re[P], im[P];
-#pragma unroll
-    for (int e = 0; e < P; e++) {
-        const int n = F::in_index(tid, e);
-        const float2 v = (n < L) ? *(const float2 *)(old + (long)n * C) : *(const float2 *)(cur + (long)(n - L) * C);
-        // the engine's history: raw frames of the last two blocks of the chunk
-        if (n >= L) {
-            if (t == a.n_t - 1) *(float2 *)(a.save_last + (long)g * a.hist_eng_stride + (long)(n - L) * C + 2 * cp) = v;
-            else if (t == a.n_t - 2) *(float2 *)(a.save_prev + (long)g * a.hist_eng_stride + (long)(n - L) * C + 2 * cp) = v;
-        } else if (a.n_t == 1) {
-            // one-block chunk: the other history block moves on unchanged
-            const long o = (long)g * a.hist_eng_stride + (long)n * C + 2 * cp;
-            *(float2 *)(a.save_prev + o) = *(const float2 *)(a.carry + o);
-        }
-        re[e] = v.x * a.scale; im[e] = v.y * a.scale;
-    }
-    BFIR_STAMP(0, 1);
-
-    F::run(re, im, lds, tw, tid);
-
-    // Z in natural order to LDS, then two-for-one split
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < P; e++) {
-        float2 v; v.x = re[e]; v.y = im[e];
-        lds[F::phys(F::out_index(tid, e))] = v;
-    }
-    __syncthreads();
-    const long slot = (long)((a.base_slot + t) % a.ring) * N;          // N floats per spectrum
-    float2 *__restrict__ da = (float2 *)(a.dst + (long)(g * C + 2 * cp) * a.dst_ch_stride + slot);
-    float2 *__restrict__ db = (float2 *)(a.dst + (long)(g * C + 2 * cp + 1) * a.dst_ch_stride + slot);
-#pragma unroll
-    for (int j = 0; j < P / 2; j++) {
-        const int k = tid + j * NT;                                    // bin 0 .. L-1
-        const float2 zk = lds[F::phys(k)];
-        const float2 zn = lds[F::phys((N - k) & (N - 1))];
-        float2 xa, xb;
-        xa.x = 0.5f * (zk.x + zn.x); xa.y = 0.5f * (zk.y - zn.y);
-        xb.x = 0.5f * (zk.y + zn.y); xb.y = -0.5f * (zk.x - zn.x);
-        if (k == 0) {                                                  // DC | Nyquist, both real
-            const float2 zh = lds[F::phys(L)];
-            xa.x = zk.x; xa.y = zh.x; xb.x = zk.y; xb.y = zh.y;
-        }
-        da[k] = xa; db[k] = xb;
-    }
-    BFIR_STAMP(0, 10);
-}
-
-template <int LOG2N>
-__global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_inv_pair(InvPairArgs a, const float2 *__restrict__ tw)
-{
-    using F = LdsFft<float, LOG2N, +1>;
-    constexpr int N = F::M, NT = F::NT, P = F::P, L = N / 2;
-    __shared__ __attribute__((aligned(16))) float2 lds[F::LDS_ELEMS];
-    __shared__ unsigned int red_max[NT / 64 > 0 ? NT / 64 : 1][2], red_cnt[NT / 64 > 0 ? NT / 64 : 1][2];
-#ifdef BFIR_PAIR_LDS_PAD
-    __shared__ volatile float occ_pad[BFIR_PAIR_LDS_PAD / 4];
-    if (a.n_t < 0) { occ_pad[threadIdx.x] = 1.f; a.scale += occ_pad[threadIdx.x ^ 1]; }
-#endif
-
-    const int tid = threadIdx.x;
-    const int w = xcd_remap();
-    const int half_c = a.C / 2, pairs = a.n_eng * half_c;
-    const int t = w / pairs, pp = w - t * pairs;
-    const int g = pp / half_c, cp = pp - g * half_c;
-    const int C = a.C;
-    const int gc = g * C + 2 * cp;
-
-    BFIR_STAMP(1, 0);
-    // both spectra into LDS: Ya at [0, L), Yb at [L, 2L)  (float2 units), 16 bytes per lane
-    {
-        const float4 *__restrict__ ya = (const float4 *)(a.y + (long)gc * a.y_ch_stride + (long)t * N);
-        const float4 *__restrict__ yb = (const float4 *)(a.y + (long)(gc + 1) * a.y_ch_stride + (long)t * N);
-        float4 *l4 = (float4 *)lds;
-#pragma unroll
-        for (int j = 0; j < P / 4; j++) {
-            const int idx = tid + j * NT;                              // < L/2 float4 per spectrum
-            l4[idx] = ya[idx];
-            l4[L / 2 + idx] = yb[idx];
-        }
-    }
-    __syncthreads();
-    BFIR_STAMP(1, 9);
-    // Z[k] = Ya[k] + i Yb[k], Hermitian-extended to the full circle
-    float re[P], im[P];
-#pragma unroll
-    for (int e = 0; e < P; e++) {
-        const int k = F::in_index(tid, e);
-        const int kk = (k <= L) ? k : N - k;
-        const float2 pa = lds[kk == L ? 0 : kk], pb = lds[L + (kk == L ? 0 : kk)];
-        float zr, zi;
-        if (k == 0)      { zr = pa.x; zi = pb.x; }                     // DC of both channels
-        else if (k == L) { zr = pa.y; zi = pb.y; }                     // Nyquist of both channels
-        else if (k < L)  { zr = pa.x - pb.y; zi = pa.y + pb.x; }
-        else             { zr = pa.x + pb.y; zi = pb.x - pa.y; }       // conj Ya + i conj Yb
-        re[e] = zr * a.scale; im[e] = zi * a.scale;
-    }
-    pin_registers(re, im);   // every read of the staged spectra happens before run()'s first barrier
-    BFIR_STAMP(1, 1);
-
-    F::run(re, im, lds, tw, tid);
-    BFIR_STAMP(1, 10);
-
-    // first L samples are the valid half (the taps sit in the upper half of their blocks)
-    float *__restrict__ out = a.raw + (long)g * a.eng_stride + (a.frame_off + (long)t * L) * C + 2 * cp;
-    const float rmax = a.max, rmin = -a.max;
-    unsigned int mx0 = 0u, mx1 = 0u, c0 = 0u, c1 = 0u;
-#pragma unroll
-    for (int e = 0; e < P; e++) {
-        const int n = F::out_index(tid, e);
-        if (n < L) {
-            float2 v; v.x = re[e]; v.y = im[e];
-            *(float2 *)(out + (long)n * C) = v;
-            // brutefir/real2raw.cpp:321-336: strict compares, NaN never counts
-            c0 += ((v.x < 0.f) ? (v.x < rmin) : (v.x > rmax)) ? 1u : 0u;
-            c1 += ((v.y < 0.f) ? (v.y < rmin) : (v.y > rmax)) ? 1u : 0u;
-            const unsigned int b0 = (v.x == v.x) ? __float_as_uint(fabsf(v.x)) : 0u;
-            const unsigned int b1 = (v.y == v.y) ? __float_as_uint(fabsf(v.y)) : 0u;
-            mx0 = b0 > mx0 ? b0 : mx0; mx1 = b1 > mx1 ? b1 : mx1;
-            // brutefir/brutefir.cpp:316-321: only sample 0 of each block is checked
-            if (n == 0 && !(isfinite(v.x) && isfinite(v.y))) flag_bad(a, t);
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned int m0 = __shfl_xor(mx0, o), m1 = __shfl_xor(mx1, o);
-        mx0 = m0 > mx0 ? m0 : mx0; mx1 = m1 > mx1 ? m1 : mx1;
-        c0 += __shfl_xor(c0, o); c1 += __shfl_xor(c1, o);
-    }
-    if ((tid & 63) == 0) { red_max[tid >> 6][0] = mx0; red_max[tid >> 6][1] = mx1; red_cnt[tid >> 6][0] = c0; red_cnt[tid >> 6][1] = c1; }
-    __syncthreads();
-    if (tid < 2) {
-        unsigned int m = 0u, n = 0u;
-        for (int wv = 0; wv < (NT + 63) / 64; wv++) { m = red_max[wv][tid] > m ? red_max[wv][tid] : m; n += red_cnt[wv][tid]; }
-        DevOverflow *of = of_shard(a.overflow, a.of_shard_stride) + (gc + tid);
-        if (n) atomicAdd(&of->n_overflows, n);
-        // filtered: the peak only ever grows, a stale read costs an extra atomic, never a wrong result
-        if ((unsigned long long)m > *(volatile unsigned long long *)&of->largest_bits)
-            atomicMax(&of->largest_bits, (unsigned long long)m);
-    }
-    BFIR_STAMP(1, 11);
-}
-
-
 // ---- persistent forward kernel -------------------------------------------------------------------
-// What k_fwd_pair waits for is memory, not arithmetic (profiles/r02_alias_and_bottleneck_experiments.txt:
-// 0.235 ms of VALU + LDS under 0.33 ms of exposed load / store / twiddle time per 4096 blocks).
-// Here ONE workgroup transforms a run of consecutive blocks of one channel pair:
+// A forward kernel that transforms one block per workgroup waits for memory, not arithmetic
+// (profiles/r02_alias_and_bottleneck_experiments.txt: 0.235 ms of VALU + LDS under 0.33 ms of exposed
+// load / store / twiddle time per 4096 blocks).  Here ONE workgroup transforms a run of consecutive blocks
+// of one channel pair:
 //   * every block is loaded once: the half-window "current block" of transform t is the "previous
 //     block" of transform t+1 and stays in registers (same thread: n -> n - L keeps the lane);
 //   * the next block is fetched right after the first butterflies of the current transform and is
@@ -216,10 +51,10 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_inv_pair(InvPairArgs a, c
 //   * twiddles never touch memory in steady state: the bases of the last pass live in registers, those
 //     of the passes before it in 9 KB of LDS, for the workgroup's life (LdsFft::butterflies_tb), so
 //     nothing queues behind the prefetch in vmcnt order.
-// Same arithmetic as k_fwd_pair except that a derived twiddle carries one more rounding.
+// Same arithmetic as one LdsFft::run per block except that a derived twiddle carries one more rounding.
 // Buffer addressing for the persistent kernels: a wave-uniform descriptor (4 SGPRs) + one 32-bit lane
 // offset + a scalar offset per access, instead of a 64-bit address pair in VGPRs per access (the
-// one-transform kernels spend a quarter of their vector instructions and ~20 registers on those).
+// one-block-per-workgroup kernels spent a quarter of their vector instructions and ~20 registers on those).
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void *p, unsigned bytes)
 {
@@ -287,20 +122,15 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void asm_prefetch2x4x4(u32x4 (&a)[4], u32x4 (&b)[4], unsigned voff, i32x4 ra, i32x4 rb, unsigned step)
 {
     const unsigned s1 = __builtin_amdgcn_readfirstlane(step), s2 = 2 * s1, s3 = 3 * s1;
-#if BFIR_NT_Y & 2
-#define BFIR_YLD_POLICY " nt"
-#else
-#define BFIR_YLD_POLICY ""
-#endif
     asm volatile("s_nop 4\n\t"
-                 "buffer_load_dwordx4 %0, %8, %9, 0 offen" BFIR_YLD_POLICY "\n\t"
-                 "buffer_load_dwordx4 %4, %8, %10, 0 offen" BFIR_YLD_POLICY "\n\t"
-                 "buffer_load_dwordx4 %1, %8, %9, %11 offen" BFIR_YLD_POLICY "\n\t"
-                 "buffer_load_dwordx4 %5, %8, %10, %11 offen" BFIR_YLD_POLICY "\n\t"
-                 "buffer_load_dwordx4 %2, %8, %9, %12 offen" BFIR_YLD_POLICY "\n\t"
-                 "buffer_load_dwordx4 %6, %8, %10, %12 offen" BFIR_YLD_POLICY "\n\t"
-                 "buffer_load_dwordx4 %3, %8, %9, %13 offen" BFIR_YLD_POLICY "\n\t"
-                 "buffer_load_dwordx4 %7, %8, %10, %13 offen" BFIR_YLD_POLICY
+                 "buffer_load_dwordx4 %0, %8, %9, 0 offen nt\n\t"
+                 "buffer_load_dwordx4 %4, %8, %10, 0 offen nt\n\t"
+                 "buffer_load_dwordx4 %1, %8, %9, %11 offen nt\n\t"
+                 "buffer_load_dwordx4 %5, %8, %10, %11 offen nt\n\t"
+                 "buffer_load_dwordx4 %2, %8, %9, %12 offen nt\n\t"
+                 "buffer_load_dwordx4 %6, %8, %10, %12 offen nt\n\t"
+                 "buffer_load_dwordx4 %3, %8, %9, %13 offen nt\n\t"
+                 "buffer_load_dwordx4 %7, %8, %10, %13 offen nt"
                  : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])
                  : "v"(voff), "s"(ra), "s"(rb), "s"(s1), "s"(s2), "s"(s3)
                  : "memory");
@@ -381,22 +211,11 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, 4) void k_fwd_pair_ps(FwdPairArg
     F::load_bases(B, ldsb, twb, tid);                                    // the first exchange's barrier publishes ldsb
 
     // frame n = tid + e NT of a block of frames sits at byte  blk + 4 (e NT C + tid C)  (+ 8 cp for the pair)
-#ifdef BFIR_EXPERIMENT_PLANAR_IO
-    // Timing experiment (profiles/r02_frame_io_experiment.txt): what would whole-line frame I/O be worth?  Each
-    // pair's L x 2 floats of a block are taken from / put to a contiguous eighth... quarter of the block's bytes
-    // (results garbage, byte counts and instruction streams those of the product kernel).
-    const float *__restrict__ raw = a.raw + (long)g * a.eng_stride + a.frame_off * C + (long)cp * L * 2;
-    const long hist = (long)g * a.hist_eng_stride + (long)cp * L * 2;
-    const unsigned blk_bytes = (unsigned)L * 2 * 4u;
-    const unsigned fo = (unsigned)tid * 2u * 4u;
-    const unsigned estep = (unsigned)NT * 2 * 4u;
-#else
     const float *__restrict__ raw = a.raw + (long)g * a.eng_stride + a.frame_off * C + 2 * cp;
     const long hist = (long)g * a.hist_eng_stride + 2 * cp;
     const unsigned blk_bytes = (unsigned)L * C * 4u;
     const unsigned fo = (unsigned)tid * (unsigned)C * 4u;                // lane offset into a block of frames
     const unsigned estep = (unsigned)NT * C * 4u;                        // bytes between a thread's consecutive points
-#endif
     static_assert(H == 8, "the prefetch statement moves eight points per thread");
     float2 cur[H];
     u32x2 nxt[H];                                                        // raw frames of the next block, as loaded
@@ -503,8 +322,8 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, 4) void k_fwd_pair_ps(FwdPairArg
                 xa.x = k0 ? 2.f * zk0.x : xa.x; xa.y = k0 ? 2.f * zh.x : xa.y;
                 xb.x = k0 ? 2.f * zk0.y : xb.x; xb.y = k0 ? 2.f * zh.y : xb.y;
             }
-            buf_store4<(BFIR_NT_X & 1) ? 2 : 0>(rxa, (unsigned)tz * 16u, (unsigned)(j * NT) * 16u, xa);
-            buf_store4<(BFIR_NT_X & 1) ? 2 : 0>(rxb, (unsigned)tz * 16u, (unsigned)(j * NT) * 16u, xb);
+            buf_store4<2>(rxa, (unsigned)tz * 16u, (unsigned)(j * NT) * 16u, xa);
+            buf_store4<2>(rxb, (unsigned)tz * 16u, (unsigned)(j * NT) * 16u, xb);
         }
         // the next transform's first exchange starts with a barrier, which also protects these LDS reads
     }
@@ -656,8 +475,8 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, 4) void k_fwd_tp_ps(FwdPairArgs 
                 xa.x = k0 ? 2.f * zk0.x : xa.x; xa.y = k0 ? 2.f * zh.x : xa.y;
                 xb.x = k0 ? 2.f * zk0.y : xb.x; xb.y = k0 ? 2.f * zh.y : xb.y;
             }
-            buf_store4<(BFIR_NT_X & 1) ? 2 : 0>(rxa, (unsigned)tz * 16u, (unsigned)(j * NT) * 16u, xa);
-            buf_store4<(BFIR_NT_X & 1) ? 2 : 0>(rxb, (unsigned)tz * 16u, (unsigned)(j * NT) * 16u, xb);
+            buf_store4<2>(rxa, (unsigned)tz * 16u, (unsigned)(j * NT) * 16u, xa);
+            buf_store4<2>(rxb, (unsigned)tz * 16u, (unsigned)(j * NT) * 16u, xb);
         }
     }
     // the last prefetch (zero-byte descriptors) is still in flight and will write nb / nc: see k_fwd_pair_ps
@@ -706,24 +525,18 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
     F::load_bases(B, ldsb, twb, tid);
 
     const float *__restrict__ ya0 = a.y + (long)gc * a.y_ch_stride;
-#ifdef BFIR_EXPERIMENT_PLANAR_IO
-    float *__restrict__ out0 = a.raw + (long)g * a.eng_stride + a.frame_off * C + (long)cp * L * 2;
-    const unsigned blk_bytes = (unsigned)L * 2 * 4u;
-    const unsigned cio = 2u;
-#else
     float *__restrict__ out0 = a.raw + (long)g * a.eng_stride + a.frame_off * C + 2 * cp;
     const unsigned blk_bytes = (unsigned)L * C * 4u;
     const unsigned cio = (unsigned)C;                                    // floats between a pair's consecutive frames
-#endif
     static_assert(Q == 4, "the prefetch statement moves four 16-byte pieces per thread and spectrum");
     u32x4 qa[Q], qb[Q];
     {
-        const __amdgpu_buffer_rsrc_t ra = make_rsrc(ya0 + (long)BFIR_YSLOT(a, t0) * N, (unsigned)N * 4u);
-        const __amdgpu_buffer_rsrc_t rb = make_rsrc(ya0 + a.y_ch_stride + (long)BFIR_YSLOT(a, t0) * N, (unsigned)N * 4u);
+        const __amdgpu_buffer_rsrc_t ra = make_rsrc(ya0 + (long)t0 * N, (unsigned)N * 4u);
+        const __amdgpu_buffer_rsrc_t rb = make_rsrc(ya0 + a.y_ch_stride + (long)t0 * N, (unsigned)N * 4u);
 #pragma unroll
         for (int j = 0; j < Q; j++) {
-            qa[j] = __builtin_amdgcn_raw_buffer_load_b128(ra, (unsigned)tid * 16u, (unsigned)(j * NT) * 16u, (BFIR_NT_Y & 2) ? 2 : 0);
-            qb[j] = __builtin_amdgcn_raw_buffer_load_b128(rb, (unsigned)tid * 16u, (unsigned)(j * NT) * 16u, (BFIR_NT_Y & 2) ? 2 : 0);
+            qa[j] = __builtin_amdgcn_raw_buffer_load_b128(ra, (unsigned)tid * 16u, (unsigned)(j * NT) * 16u, 2);
+            qb[j] = __builtin_amdgcn_raw_buffer_load_b128(rb, (unsigned)tid * 16u, (unsigned)(j * NT) * 16u, 2);
         }
         // consumed before the loop: inside it the compiler has no pending load of its own (see k_fwd_pair_ps)
 #pragma unroll
@@ -781,8 +594,8 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
                 // the next block's spectra, under the remaining passes; past the end of the run the descriptors
                 // have zero bytes and the loads return zeros (no branch in the loop, see k_fwd_pair_ps)
                 const unsigned nbytes = t + 1 < t1 ? (unsigned)N * 4u : 0u;
-                asm_prefetch2x4x4(qa, qb, (unsigned)tl * 16u, make_rsrc_words(ya0 + (long)BFIR_YSLOT(a, t + 1) * N, nbytes),
-                                  make_rsrc_words(ya0 + a.y_ch_stride + (long)BFIR_YSLOT(a, t + 1) * N, nbytes), (unsigned)NT * 16u);
+                asm_prefetch2x4x4(qa, qb, (unsigned)tl * 16u, make_rsrc_words(ya0 + (long)(t + 1) * N, nbytes),
+                                  make_rsrc_words(ya0 + a.y_ch_stride + (long)(t + 1) * N, nbytes), (unsigned)NT * 16u);
             }
         });
 
@@ -869,12 +682,12 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
     static_assert(Q == 4, "the prefetch statement moves four 16-byte pieces per thread and spectrum");
     u32x4 qa[Q], qb[Q];
     {
-        const __amdgpu_buffer_rsrc_t ra = make_rsrc(ya0 + (long)BFIR_YSLOT(a, t0) * N, (unsigned)N * 4u);
-        const __amdgpu_buffer_rsrc_t rb = make_rsrc(ya0 + (long)BFIR_YSLOT(a, t0 + 1) * N, t0 + 1 < t1 ? (unsigned)N * 4u : 0u);
+        const __amdgpu_buffer_rsrc_t ra = make_rsrc(ya0 + (long)t0 * N, (unsigned)N * 4u);
+        const __amdgpu_buffer_rsrc_t rb = make_rsrc(ya0 + (long)(t0 + 1) * N, t0 + 1 < t1 ? (unsigned)N * 4u : 0u);
 #pragma unroll
         for (int j = 0; j < Q; j++) {
-            qa[j] = __builtin_amdgcn_raw_buffer_load_b128(ra, (unsigned)tid * 16u, (unsigned)(j * NT) * 16u, (BFIR_NT_Y & 2) ? 2 : 0);
-            qb[j] = __builtin_amdgcn_raw_buffer_load_b128(rb, (unsigned)tid * 16u, (unsigned)(j * NT) * 16u, (BFIR_NT_Y & 2) ? 2 : 0);
+            qa[j] = __builtin_amdgcn_raw_buffer_load_b128(ra, (unsigned)tid * 16u, (unsigned)(j * NT) * 16u, 2);
+            qb[j] = __builtin_amdgcn_raw_buffer_load_b128(rb, (unsigned)tid * 16u, (unsigned)(j * NT) * 16u, 2);
         }
 #pragma unroll
         for (int j = 0; j < Q; j++) asm volatile("" : "+v"(qa[j]), "+v"(qb[j]));
@@ -923,8 +736,8 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
             F::template butterflies_tb<S>(re, im, B, ldsb, tl);
             if constexpr (S == 1) {
                 asm_prefetch2x4x4(qa, qb, (unsigned)tl * 16u,
-                                  make_rsrc_words(ya0 + (long)BFIR_YSLOT(a, t + 2) * N, t + 2 < t1 ? (unsigned)N * 4u : 0u),
-                                  make_rsrc_words(ya0 + (long)BFIR_YSLOT(a, t + 3) * N, t + 3 < t1 ? (unsigned)N * 4u : 0u), (unsigned)NT * 16u);
+                                  make_rsrc_words(ya0 + (long)(t + 2) * N, t + 2 < t1 ? (unsigned)N * 4u : 0u),
+                                  make_rsrc_words(ya0 + (long)(t + 3) * N, t + 3 < t1 ? (unsigned)N * 4u : 0u), (unsigned)NT * 16u);
             }
         });
 
@@ -988,8 +801,7 @@ bool pair_supported(int filter_length)
 // 16 blocks) but the engine runs forward, MAC and inverse of neighbouring chunks concurrently, and a
 // kernel made of a few hundred long-lived workgroups holds every CU slot until it ends, so the other
 // two cannot slip in: the pipeline is fastest with SHORT runs (profiles/r02_pair_run_sweep.txt:
-// 108 Gsamples/s at 4 blocks per workgroup against 95 at 32).  BFIR_PAIR_RUN_FWD / _INV override (tuning aid);
-// BFIR_PAIR_PERSIST=0 keeps the one-transform-per-workgroup kernels.
+// 108 Gsamples/s at 4 blocks per workgroup against 95 at 32).  BFIR_PAIR_RUN_FWD / _INV override (tuning aid).
 static int pair_run_len(int n_t, int pairs, bool inverse)
 {
     if (const char *e = getenv(inverse ? "BFIR_PAIR_RUN_INV" : "BFIR_PAIR_RUN_FWD")) return std::max(1, atoi(e));
@@ -999,12 +811,8 @@ static int pair_run_len(int n_t, int pairs, bool inverse)
     return std::min(fill, 4);
 }
 
-void launch_fwd_pair(const FftPlan &plan, const FwdPairArgs &a_, hipStream_t s)
+void launch_fwd_pair(const FftPlan &plan, const FwdPairArgs &a, hipStream_t s)
 {
-    FwdPairArgs a = a_;
-#ifdef BFIR_EXPERIMENT_ALIAS
-    if (const int xa = bfir_alias_env("BFIR_X_ALIAS")) { a.ring = xa; a.base_slot %= xa; }
-#endif
     if (a.tp) {                                            // pairs in time: one unit per channel, runs of an even number of blocks
         const int units = a.n_eng * a.C;
         if (a.n_t <= 0 || units <= 0 || !plan.twb) return;
@@ -1018,32 +826,18 @@ void launch_fwd_pair(const FftPlan &plan, const FwdPairArgs &a_, hipStream_t s)
         }
         return;
     }
-    const int items = a.n_t * a.n_eng * (a.C / 2);
-    if (items <= 0) return;
-    const char *pe = getenv("BFIR_PAIR_PERSIST");
-    if (!(pe && atoi(pe) == 0) && plan.twb) {
-        const int pairs = a.n_eng * (a.C / 2);
-        const int len = pair_run_len(a.n_t, pairs, false), runs = (a.n_t + len - 1) / len;
-        switch (plan.log2m) {
-#define F(lg) case lg: hipLaunchKernelGGL((k_fwd_pair_ps<lg>), dim3(runs * pairs), dim3(FftCfg<lg>::NT), 0, s, a, (const float2 *)plan.twb, len); break;
-            BFIR_FOR_PAIR_LOG2N(F)
-#undef F
-        }
-        return;
-    }
+    const int pairs = a.n_eng * (a.C / 2);
+    if (a.n_t <= 0 || pairs <= 0 || !plan.twb) return;
+    const int len = pair_run_len(a.n_t, pairs, false), runs = (a.n_t + len - 1) / len;
     switch (plan.log2m) {
-#define F(lg) case lg: hipLaunchKernelGGL((k_fwd_pair<lg>), dim3(items), dim3(FftCfg<lg>::NT), 0, s, a, (const float2 *)plan.tw); break;
+#define F(lg) case lg: hipLaunchKernelGGL((k_fwd_pair_ps<lg>), dim3(runs * pairs), dim3(FftCfg<lg>::NT), 0, s, a, (const float2 *)plan.twb, len); break;
         BFIR_FOR_PAIR_LOG2N(F)
 #undef F
     }
 }
 
-void launch_inv_pair(const FftPlan &plan, const InvPairArgs &a_, hipStream_t s)
+void launch_inv_pair(const FftPlan &plan, const InvPairArgs &a, hipStream_t s)
 {
-    InvPairArgs a = a_;
-#ifdef BFIR_EXPERIMENT_ALIAS
-    if (const int ya = bfir_alias_env("BFIR_Y_ALIAS")) a.y_alias = ya;
-#endif
     if (a.tp) {                                            // pairs in time (k_inv_tp_ps)
         const int units = a.n_eng * a.C;
         if (a.n_t <= 0 || units <= 0 || !plan.twb) return;
@@ -1055,35 +849,14 @@ void launch_inv_pair(const FftPlan &plan, const InvPairArgs &a_, hipStream_t s)
         }
         return;
     }
-    const int items = a.n_t * a.n_eng * (a.C / 2);
-    if (items <= 0) return;
-    const char *pe = getenv("BFIR_PAIR_PERSIST");
-    if (!(pe && (atoi(pe) == 0 || atoi(pe) == 2)) && plan.twb) {        // 2: persistent forward kernel only (A/B)
-        const int pairs = a.n_eng * (a.C / 2);
-        const int len = pair_run_len(a.n_t, pairs, true), runs = (a.n_t + len - 1) / len;
-        switch (plan.log2m) {
-#define F(lg) case lg: hipLaunchKernelGGL((k_inv_pair_ps<lg>), dim3(runs * pairs), dim3(FftCfg<lg>::NT), 0, s, a, (const float2 *)plan.twb, len); break;
-            BFIR_FOR_PAIR_LOG2N(F)
-#undef F
-        }
-        return;
-    }
+    const int pairs = a.n_eng * (a.C / 2);
+    if (a.n_t <= 0 || pairs <= 0 || !plan.twb) return;
+    const int len = pair_run_len(a.n_t, pairs, true), runs = (a.n_t + len - 1) / len;
     switch (plan.log2m) {
-#define F(lg) case lg: hipLaunchKernelGGL((k_inv_pair<lg>), dim3(items), dim3(FftCfg<lg>::NT), 0, s, a, (const float2 *)plan.tw); break;
+#define F(lg) case lg: hipLaunchKernelGGL((k_inv_pair_ps<lg>), dim3(runs * pairs), dim3(FftCfg<lg>::NT), 0, s, a, (const float2 *)plan.twb, len); break;
         BFIR_FOR_PAIR_LOG2N(F)
 #undef F
     }
 }
 
 }  // namespace bfir
-
-#ifdef BFIR_TRACE
-// tuning builds only: phase stamps of this file's kernels (0 k_fwd_pair, 1 k_inv_pair)
-extern "C" int bfir_debug_read_trace_pair(int kern, unsigned long long *out, int n_wgs)
-{
-    if (kern < 0 || kern > 1 || n_wgs > BFIR_TRACE_WGS) return -1;
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), sizeof(unsigned long long) * n_wgs * BFIR_TRACE_SLOTS,
-                                    sizeof(unsigned long long) * kern * BFIR_TRACE_WGS * BFIR_TRACE_SLOTS,
-                                    hipMemcpyDeviceToHost);
-}
-#endif

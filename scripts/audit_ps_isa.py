@@ -13,7 +13,7 @@ stores issued after the prefetch.  That is only right while, in the code hipcc a
   4. there is exactly one prefetch statement, one counted wait and one closing vmcnt(0) wait per kernel.
 
 hipcc cross-compiles without a GPU, so this runs in the CPU test suite (tests/test_isa_audit.py) and fails the build
-when a compiler or flag change breaks an assumption.  BFIR_PAIR_PERSIST=0 is the fallback at run time.
+when a compiler or flag change breaks an assumption.  BFIR_PAIR=0 (the planar staging kernels) is the fallback at run time.
 
     python scripts/audit_ps_isa.py [pair.s]      (without an argument: compiles csrc/pair.hip to assembly first)
 """

@@ -70,7 +70,6 @@ run plugin_fp32 --workload plugin_2ch_65536tap_L1024_fp32 --blocks 65536
 run plugin_8ch_B64 --workload plugin_8ch_65536tap_L1024_fp32 --blocks 32768
 run plugin_8ch_B128 --workload plugin_8ch_131072tap_L1024_fp32 --blocks 32768
 BFIR_PAIR=0 run cfg3_staging_path --workload cfg3_8ch_131072tap_L4096_fp32 --blocks 32768
-BFIR_PAIR_PERSIST=0 run cfg3_r01_fft_kernels --workload cfg3_8ch_131072tap_L4096_fp32 --blocks 32768
 echo "== plug-in shape + host path" | tee -a $OUT/progress.log
 for g in 0.01 0.0005; do timeout -k 10 300 python scripts/plugin_shape.py $g 2>&1 | grep realsize; done | tee $OUT/plugin_shape.txt
 timeout -k 10 300 python scripts/host_path.py 2>&1 | grep -v amdgpu.ids | tee $OUT/host_path.txt

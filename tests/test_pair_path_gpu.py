@@ -185,7 +185,7 @@ def test_time_paired_path_matches_oracle_and_planar_path(orc, bfir, L, B, C, nb,
 def test_time_paired_path_is_the_default_for_odd_channel_counts(orc, bfir):
     """BFIR_PAIR_TIME=0 keeps such engines on the general path; the two agree to rounding, and differ in the last
     bits (which is how this test knows the fast path ran)."""
-    if any(os.environ.get(k) for k in ("BFIR_PAIR", "BFIR_PAIR_PERSIST", "BFIR_PAIR_TIME")):
+    if any(os.environ.get(k) for k in ("BFIR_PAIR", "BFIR_PAIR_TIME")):
         pytest.skip("a path-selecting switch is set for the whole run (scripts/gpu_env_matrix.sh)")
     L, B, C, nb = 1024, 4, 3, 16
     h, x = _data(orc, C, B * L - 5, nb * L, seed=77)
