@@ -375,8 +375,11 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
     }
     if (alloc_work(e, 1) != BFIR_OK) return fail(BFIR_ERR_HIP);
     if (hipDeviceSynchronize() != hipSuccess) return fail(BFIR_ERR_HIP);
-    bfir_logf("bfir engine: %d x %d channels, partition %d, %d blocks, realsize %d on device %d.",
-              n_engines, channels, filter_length, filter_blocks, realsize, device);
+    // which family the engine runs on (tests read it; per-launch variants such as CPW = 2 depend on alignment and are not here)
+    bfir_logf("bfir engine: %d x %d channels, partition %d, %d blocks, realsize %d on device %d. path=%s layout=%s run=%s",
+              n_engines, channels, filter_length, filter_blocks, realsize, device,
+              e->pair_tp ? "time-pair" : e->pair ? "pair" : e->direct ? "direct" : "staging", e->ilv ? "pairs" : "grouped",
+              realsize == 8 && e->direct && run64_supported(filter_length, realsize) ? "on" : "off");
     return e;
 }
 
