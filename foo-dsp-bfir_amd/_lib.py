@@ -53,6 +53,7 @@ SIGNATURES = {
     "bfir_version": (C.c_char_p, []),
     "bfir_engine_create": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_create_batch": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
+    "bfir_engine_create_matrix": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_destroy": (None, [_vp]),
     "bfir_engine_is_initialized": (_ci, [_vp]),
     "bfir_engine_set_coeff": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _ci, _cd]),
@@ -66,6 +67,8 @@ SIGNATURES = {
     "bfir_engine_set_profiling": (_ci, [_vp, _ci]),
     "bfir_engine_get_profile": (_ci, [_vp, _ci, C.POINTER(_cd), C.POINTER(_cl)]),
     "bfir_engine_read_coeff": (_ci, [_vp, _ci, _ci, _vp]),
+    "bfir_engine_set_coeff_matrix": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd]),
+    "bfir_engine_read_coeff_matrix": (_ci, [_vp, _ci, _ci, _ci, _vp]),
     "bfir_convolver_create": (_vp, [_ci, _ci, _ci, _pi]),
     "bfir_convolver_destroy": (None, [_vp]),
     "bfir_convolver_cbufsize": (_ci, [_vp]),

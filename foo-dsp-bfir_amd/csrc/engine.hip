@@ -9,7 +9,9 @@
 //   tin   2 x [GC][chunk*L] planar time input, double buffered (input_timecbuf)
 //   tout  [GC][chunk*L]     planar time output
 //   saved 2 x [GC][L]      history blocks kept across reset / reallocation
-// GC = n_eng * C global channels.  A run of n blocks is cut into chunks of at
+// GC = n_eng * C global channels.  A matrix engine (bfir_engine_create_matrix: one engine, C = n_in inputs, Co = n_out
+// outputs, one filter per (output, input) pair) keeps the input side -- X, tails, saved -- for its C inputs and the output
+// side -- Y, the overflow statistics, the output frames -- for its Co outputs; H is [Co][C][B][N], the MAC k_mac_matrix.  A run of n blocks is cut into chunks of at
 // most `chunk` blocks; each chunk is five launches, the first two on a side
 // stream so that they overlap the last three of the chunk before.
 #include <hip/hip_runtime.h>
@@ -95,6 +97,8 @@ struct BlockRef {
 struct bfir_engine {
     int device = 0;
     int L = 0, N = 0, B = 0, s = 0, C = 0, n_eng = 1, GC = 0;
+    bool matrix = false;            // n_in -> n_out with one filter per pair (matrix.hip); diagonal: output c = input c * h_c
+    int Co = 0, GCo = 0;            // output channels per engine / in all: C and GC, or a matrix engine's n_out
     int in_bytes = 0, out_bytes = 0, in_fmt = 0, out_fmt = 0;
     double in_scale = 1.0, out_scale = 1.0, of_max = 1.0;
     FftPlan plan;
@@ -131,6 +135,10 @@ struct bfir_engine {
     bool pair = false;
     // ... with an odd channel count (or one channel) the pairs are blocks t, t + 1 of ONE channel (k_fwd_tp_ps / k_inv_tp_ps)
     bool pair_tp = false;
+    // matrix engine that may take the pair path (both counts even); it does while every input feeds some output
+    // (bfir_engine_set_coeff_matrix): a channel pair is ONE transform, so a NaN in an input no filter reads would reach
+    // the spectra of its partner
+    bool pair_cap = false;
     // direct path: any other engine whose frames are FLOAT_LE / FLOAT64_LE in and out (fp64 arithmetic, odd
     // channel counts, partitions outside the pair kernels' range): k_fwd reads the raw frames itself and
     // k_inv writes them, one channel per transform; same history bookkeeping as the pair path (tails of raw
@@ -212,12 +220,12 @@ static int alloc_work(bfir_engine *e, int chunk)
     if (e->X) { int rc = materialise_history(e); if (rc != BFIR_OK) return rc; }
     void *X = nullptr, *Y0 = nullptr, *Y1 = nullptr, *tin0 = nullptr, *tin1 = nullptr, *tout = nullptr;
     HIP_TRY(hipMalloc(&X, (size_t)e->GC * ring * cb));
-    HIP_TRY(hipMalloc(&Y0, (size_t)e->GC * chunk * cb));
-    HIP_TRY(hipMalloc(&Y1, (size_t)e->GC * chunk * cb));
+    HIP_TRY(hipMalloc(&Y0, (size_t)e->GCo * chunk * cb));
+    HIP_TRY(hipMalloc(&Y1, (size_t)e->GCo * chunk * cb));
     if (!e->pair && !e->direct) {   // the pair and direct paths have no planar time buffers
         HIP_TRY(hipMalloc(&tin0, (size_t)e->GC * chunk * e->L * e->s));
         HIP_TRY(hipMalloc(&tin1, (size_t)e->GC * chunk * e->L * e->s));
-        HIP_TRY(hipMalloc(&tout, (size_t)e->GC * chunk * e->L * e->s));
+        HIP_TRY(hipMalloc(&tout, (size_t)e->GCo * chunk * e->L * e->s));
     }
     HIP_TRY(hipMemset(X, 0, (size_t)e->GC * ring * cb));
     if (e->X) {
@@ -237,17 +245,17 @@ static int alloc_work(bfir_engine *e, int chunk)
     return BFIR_OK;
 }
 
-extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_length, int filter_blocks,
-                                                 int realsize, int channels, int in_format,
-                                                 int out_format, int sampling_rate, int apply_dither,
-                                                 int device, int *err)
+// matrix: `channels` inputs, `channels_out` outputs, one engine (bfir_engine_create_matrix); else channels_out == channels
+static bfir_engine *engine_create(int n_engines, int filter_length, int filter_blocks, int realsize, int channels,
+                                  int channels_out, bool matrix, int in_format, int out_format, int sampling_rate,
+                                  int apply_dither, int device, int *err)
 {
     int dummy;
     if (!err) err = &dummy;
     *err = BFIR_OK;
     // brutefir.cpp:652 (channel limit), fftw_convolver.cpp:64-74 (realsize, length)
-    if (channels < 1 || channels > BFIR_MAXCHANNELS) {
-        bfir_logf("Number of channels (%d) exceeds limit (%d).", channels, BFIR_MAXCHANNELS);
+    if (channels < 1 || channels > BFIR_MAXCHANNELS || channels_out < 1 || channels_out > BFIR_MAXCHANNELS) {
+        bfir_logf("Number of channels (%d) exceeds limit (%d).", std::max(channels, channels_out), BFIR_MAXCHANNELS);
         *err = BFIR_ERR_ARG; return nullptr;
     }
     if (realsize != 4 && realsize != 8) { bfir_logf("Invalid real size %d.", realsize); *err = BFIR_ERR_ARG; return nullptr; }
@@ -265,6 +273,7 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
     e->device = device;
     e->L = filter_length; e->N = 2 * filter_length; e->B = filter_blocks; e->s = realsize;
     e->C = channels; e->n_eng = n_engines; e->GC = n_engines * channels;
+    e->matrix = matrix; e->Co = channels_out; e->GCo = n_engines * channels_out;
     e->in_bytes = fmt_bytes(in_format); e->out_bytes = fmt_bytes(out_format);
     e->in_fmt = in_format; e->out_fmt = out_format;
     // setup_input: normalised scale 1/2^(bits-1); setup_output: full scale; overflow max
@@ -282,6 +291,13 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
         e->pair = e->ilv && in_format == 8 && out_format == 8 && ((channels % 2) == 0 || e->pair_tp) &&
                   pair_supported(filter_length) && !(pv && atoi(pv) == 0);
         e->pair_tp = e->pair_tp && e->pair;
+        if (matrix) {
+            // channel pairs on both sides or direct mode: time pairs transform blocks t, t + 1 together, so where a launch
+            // starts would change the bits of its blocks (a matrix engine's outputs do not depend on the chunking)
+            e->pair = e->pair && channels % 2 == 0 && channels_out % 2 == 0;
+            e->pair_tp = false;
+            e->pair_cap = e->pair;
+        }
         const char *dv = getenv("BFIR_DIRECT");
         // worth it where a channel's samples are 8 bytes apart or wider units: FLOAT64 frames (any C), or one
         // channel (contiguous samples), or float frames with an even channel count (the reference plug-in's own shape:
@@ -297,6 +313,7 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
         const bool wide = (e->in_bytes == 8 && e->out_bytes == 8) || channels == 1 || stereo || run64_supported(filter_length, realsize);
         e->direct = !e->pair && fmt_is_native(in_format) && fmt_is_native(out_format) && !(pv && atoi(pv) == 0) &&
                     (dv ? atoi(dv) != 0 : wide);
+        if (matrix) e->direct = !e->pair;   // a matrix engine has no staging path: float frames only, direct where not paired
         // fp64 engines whose transforms the run kernels take keep their spectra -- delay line, filter partitions, products --
         // as (re, im) PAIRS like the fp32 engines, not in the reference's groups of four: one 16-byte access per bin in the
         // MAC instead of two of 8, the forward kernel's spectrum straight from registers (no LDS staging), conflict-free reads
@@ -316,7 +333,7 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
     // three of them side by side only get into each other's way: the plug-in's shape 42.8 -> 45.9 Gsamples/s, 8 channels 42.5 ->
     // 44.6, cfg5 43.1 either way (profiles/r03_fp64.txt).  The fp32 headline gains 10 % from the three-stream schedule.
     else if (realsize == 8) { e->pipe3 = false; e->serial = true; }
-    e->nblk.assign(e->GC, 0);
+    e->nblk.assign(matrix ? (size_t)e->Co * e->C : (size_t)e->GC, 0);   // matrix: [o C + i]
     e->eng_init.assign(n_engines, 0);
     int rc = fft_plan_create(&e->plan, filter_length, realsize);
     if (rc != 0) { *err = (rc == -1) ? BFIR_ERR_UNSUPPORTED : BFIR_ERR_HIP; delete e; return nullptr; }
@@ -341,20 +358,21 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
     for (hipEvent_t *ev : events)
         if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return fail(BFIR_ERR_HIP);
     const size_t cb = cbuf_bytes(e), Ls = (size_t)e->L * e->s;
-    if (hipMalloc(&e->H, (size_t)e->GC * e->B * cb) != hipSuccess ||
+    const size_t n_filters = matrix ? (size_t)e->Co * e->C : (size_t)e->GC;
+    if (hipMalloc(&e->H, n_filters * e->B * cb) != hipSuccess ||
         hipMalloc(&e->saved[0], (size_t)e->GC * Ls) != hipSuccess ||
         hipMalloc(&e->saved[1], (size_t)e->GC * Ls) != hipSuccess ||
         hipMalloc((void **)&e->d_nblk, sizeof(int) * e->GC) != hipSuccess ||
-        hipMalloc((void **)&e->d_of, sizeof(DevOverflow) * e->GC * BFIR_OF_SHARDS) != hipSuccess ||
+        hipMalloc((void **)&e->d_of, sizeof(DevOverflow) * e->GCo * BFIR_OF_SHARDS) != hipSuccess ||
         hipMalloc((void **)&e->d_bad, sizeof(int)) != hipSuccess)
         return fail(BFIR_ERR_HIP);
-    (void)hipMemset(e->H, 0, (size_t)e->GC * e->B * cb);
+    (void)hipMemset(e->H, 0, n_filters * e->B * cb);
     for (int i = 0; i < 2; i++) {   // input_timecbuf starts zeroed (brutefir.cpp:769)
         (void)hipMemset(e->saved[i], 0, (size_t)e->GC * Ls);
         e->hist[i].ptr = e->saved[i]; e->hist[i].ch_stride = e->L;
     }
     (void)hipMemset(e->d_nblk, 0, sizeof(int) * e->GC);
-    (void)hipMemset(e->d_of, 0, sizeof(DevOverflow) * e->GC * BFIR_OF_SHARDS);
+    (void)hipMemset(e->d_of, 0, sizeof(DevOverflow) * e->GCo * BFIR_OF_SHARDS);
     (void)hipMemset(e->d_bad, 0x7f, sizeof(int));
     if (apply_dither && !fmt_info(out_format).isfloat) {
         // dither::dither(n_channels, sampling_rate, realsize, max_dither_table_size = 0, filter_length, state)
@@ -376,11 +394,43 @@ extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_lengt
     if (alloc_work(e, 1) != BFIR_OK) return fail(BFIR_ERR_HIP);
     if (hipDeviceSynchronize() != hipSuccess) return fail(BFIR_ERR_HIP);
     // which family the engine runs on (tests read it; per-launch variants such as CPW = 2 depend on alignment and are not here)
+    if (matrix) {
+        // path=pair can give way to direct mode while an input feeds no output (bfir_engine_set_coeff_matrix logs it)
+        bfir_logf("bfir engine: matrix %d -> %d, partition %d, %d blocks, realsize %d on device %d. path=%s layout=%s run=%s",
+                  channels, channels_out, filter_length, filter_blocks, realsize, device, e->pair ? "pair" : "direct",
+                  e->ilv ? "pairs" : "grouped",
+                  realsize == 8 && e->direct && run64_supported(filter_length, realsize) ? "on" : "off");
+        return e;
+    }
     bfir_logf("bfir engine: %d x %d channels, partition %d, %d blocks, realsize %d on device %d. path=%s layout=%s run=%s",
               n_engines, channels, filter_length, filter_blocks, realsize, device,
               e->pair_tp ? "time-pair" : e->pair ? "pair" : e->direct ? "direct" : "staging", e->ilv ? "pairs" : "grouped",
               realsize == 8 && e->direct && run64_supported(filter_length, realsize) ? "on" : "off");
     return e;
+}
+
+extern "C" bfir_engine *bfir_engine_create_batch(int n_engines, int filter_length, int filter_blocks,
+                                                 int realsize, int channels, int in_format,
+                                                 int out_format, int sampling_rate, int apply_dither,
+                                                 int device, int *err)
+{
+    return engine_create(n_engines, filter_length, filter_blocks, realsize, channels, channels, false, in_format, out_format,
+                         sampling_rate, apply_dither, device, err);
+}
+
+extern "C" bfir_engine *bfir_engine_create_matrix(int filter_length, int filter_blocks, int realsize, int n_inputs,
+                                                  int n_outputs, int in_format, int out_format, int device, int *err)
+{
+    int dummy;
+    if (!err) err = &dummy;
+    if (n_inputs < 1 || n_inputs > BFIR_MAXCHANNELS || n_outputs < 1 || n_outputs > BFIR_MAXCHANNELS) {
+        bfir_logf("Number of channels (%d -> %d) exceeds limit (%d).", n_inputs, n_outputs, BFIR_MAXCHANNELS);
+        *err = BFIR_ERR_ARG; return nullptr;
+    }
+    // float frames only (no staging kernels, no dither)
+    if (!fmt_is_native(in_format) || !fmt_is_native(out_format)) { *err = BFIR_ERR_UNSUPPORTED; return nullptr; }
+    return engine_create(1, filter_length, filter_blocks, realsize, n_inputs, n_outputs, true, in_format, out_format, 44100, 0,
+                         device, err);
 }
 
 extern "C" bfir_engine *bfir_engine_create(int filter_length, int filter_blocks, int realsize,
@@ -432,6 +482,7 @@ extern "C" int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const 
 {
     if (!e || engine_index < 0 || engine_index >= e->n_eng || !coeffs || length < 0 || coeff_blocks < 1)
         return BFIR_ERR_ARG;
+    if (e->matrix) return BFIR_ERR_UNSUPPORTED;                 // bfir_engine_set_coeff_matrix
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     e->eng_init[engine_index] = 0;                              // free_coeff(), brutefir.cpp:188
@@ -495,13 +546,82 @@ extern "C" int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, 
     return bfir_engine_set_coeff_at(e, 0, coeffs, n_coeffs, length, coeff_blocks, scale);
 }
 
-extern "C" int bfir_engine_read_coeff(bfir_engine *e, int channel, int block, void *dst)
+// the same for the n_out x n_in filters of a matrix engine: coeffs[o n_in + i], NULL = no path from input i to output o
+extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *coeffs, int length, int coeff_blocks,
+                                            double scale)
 {
-    if (!e || channel < 0 || channel >= e->GC || block < 0 || block >= e->B || !dst) return BFIR_ERR_ARG;
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->matrix) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    e->eng_init[0] = 0;
+    const int P = e->Co * e->C;                                 // filters, [o][i]
+    const int nb = std::min(coeff_blocks, e->B);
+    const size_t taps_pad = (size_t)nb * e->L;
+    const size_t cb = cbuf_bytes(e);
+    const size_t cnt = std::min((size_t)length, taps_pad);
+    std::vector<char> host((size_t)P * taps_pad * e->s, 0);
+    for (int n = 0; n < P; n++) {
+        if (!coeffs[n]) continue;
+        bool finite = true;
+        if (e->s == 4) {
+            const float *src = (const float *)coeffs[n];
+            const float sc = (float)scale;
+            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite((double)(src[i] * sc));
+        } else {
+            const double *src = (const double *)coeffs[n];
+            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite(src[i] * scale);
+        }
+        if (!finite) {
+            bfir_logf("NaN or Inf value among coefficients.");
+            bfir_logf("Error preprocessing coefficient %d (output %d, input %d)", n, n / e->C, n % e->C);
+            return BFIR_ERR_COEFF;
+        }
+        memcpy(host.data() + (size_t)n * taps_pad * e->s, coeffs[n], cnt * e->s);
+    }
+    void *d_taps = nullptr;
+    HIP_TRY(hipMalloc(&d_taps, host.size()));
+    HIP_TRY(hipMemcpyAsync(d_taps, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(e->H, 0, (size_t)P * e->B * cb, e->stream));
+    FwdArgs fa;                                                 // as set_coeff_at, one "channel" per filter
+    fa.src = d_taps; fa.src_ch_stride = (long)taps_pad;
+    fa.prev = nullptr; fa.prev_ch_stride = 0;
+    fa.dst = e->H; fa.dst_ch_stride = (long)e->B * e->N;
+    fa.ring = e->B; fa.base_slot = 0;
+    fa.n_t = nb; fa.n_ch = P;
+    fa.load_scale = scale;
+    fa.out_scale = 1.0 / (double)e->N;
+    fa.zero_first_half = 1;
+    fa.interleaved = e->ilv;
+    launch_fwd(e->plan, fa, e->stream);
+    for (int n = 0; n < P; n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
+    if (e->pair_cap) {   // same delay-line layout and history bookkeeping on both paths: the next chunk just takes the other
+        bool every_input_read = true;
+        for (int i = 0; i < e->C; i++) {
+            bool read = false;
+            for (int o = 0; o < e->Co; o++) read = read || e->nblk[o * e->C + i] > 0;
+            every_input_read = every_input_read && read;
+        }
+        if (e->pair != every_input_read)
+            bfir_logf("bfir matrix engine: %s: path=%s from the next block on.",
+                      every_input_read ? "every input feeds an output" : "an input feeds no output", every_input_read ? "pair" : "direct");
+        e->pair = every_input_read; e->direct = !e->pair;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipFree(d_taps));
+    HIP_TRY(hipGetLastError());
+    e->eng_init[0] = 1;
+    return BFIR_OK;
+}
+
+// partition spectrum `block` of filter `f` (H row) to host, in the reference's grouped layout
+static int read_spectrum(bfir_engine *e, int f, int block, void *dst)
+{
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t cb = cbuf_bytes(e);
-    HIP_TRY(hipMemcpy(dst, (char *)e->H + ((size_t)channel * e->B + block) * cb, cb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dst, (char *)e->H + ((size_t)f * e->B + block) * cb, cb, hipMemcpyDeviceToHost));
     if (e->ilv) {   // hand out the reference's grouped layout (fftw_convolver.cpp:883-907)
         auto regroup = [&](auto *o) {
             using R = typename std::remove_pointer<decltype(o)>::type;
@@ -514,6 +634,21 @@ extern "C" int bfir_engine_read_coeff(bfir_engine *e, int channel, int block, vo
         if (e->s == 4) regroup((float *)dst); else regroup((double *)dst);
     }
     return BFIR_OK;
+}
+
+extern "C" int bfir_engine_read_coeff(bfir_engine *e, int channel, int block, void *dst)
+{
+    if (!e || channel < 0 || channel >= e->GC || block < 0 || block >= e->B || !dst) return BFIR_ERR_ARG;
+    if (e->matrix) return BFIR_ERR_UNSUPPORTED;                 // bfir_engine_read_coeff_matrix
+    return read_spectrum(e, channel, block, dst);
+}
+
+extern "C" int bfir_engine_read_coeff_matrix(bfir_engine *e, int output, int input, int block, void *dst)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->matrix) return BFIR_ERR_UNSUPPORTED;
+    if (output < 0 || output >= e->Co || input < 0 || input >= e->C || block < 0 || block >= e->B || !dst) return BFIR_ERR_ARG;
+    return read_spectrum(e, output * e->C + input, block, dst);
 }
 
 // ---------------------------------------------------------------------------
@@ -596,6 +731,29 @@ extern "C" int bfir_engine_get_profile(bfir_engine *e, int kernel, double *total
 //   s_front : fwd_pair(k)             raw frames -> delay-line spectra of two channels per transform
 //   s_mac   : mac(k)
 //   st      : inv_pair(k)             product spectra -> raw frames + overflow statistics
+// The MAC of a matrix engine's chunk (both paths): k_mac_matrix over the engine's delay line and filters.
+static MatArgs matrix_mac_args(const bfir_engine *e, int base_slot, void *Y, int tc)
+{
+    MatArgs a;
+    a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
+    a.h = e->H; a.h_pair_stride = (long)e->B * e->N;
+    for (int j = 0; j < BFIR_MAT_MAX * BFIR_MAT_MAX; j++) a.nblk[j] = j < (int)e->nblk.size() ? e->nblk[j] : 0;
+    a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
+    a.n_t = tc; a.n_in = e->C; a.n_out = e->Co; a.N = e->N; a.realsize = e->s;
+    a.interleaved = e->ilv;
+    return a;
+}
+
+// a chunk the matrix MAC cannot take is refused before anything is queued (never skipped)
+static int matrix_chunk_ok(const bfir_engine *e, int tc)
+{
+    if (e->matrix && !mac_matrix_supported(matrix_mac_args(e, 0, nullptr, tc))) {
+        bfir_logf("bfir engine: %d blocks per launch are past the matrix MAC's grid.", tc);
+        return BFIR_ERR_UNSUPPORTED;
+    }
+    return BFIR_OK;
+}
+
 static int run_chunk_pair(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride,
                           long frame_off, int tc, int block_base, hipStream_t st, hipEvent_t input_ready)
 {
@@ -635,6 +793,9 @@ static int run_chunk_pair(bfir_engine *e, const void *d_in, long in_stride, void
     void *Y = e->Yb[e->pipe3 ? par : 0];
     {
         ProfScope ps(e, BFIR_K_MAC, sm);
+        if (e->matrix) {
+            if (launch_mac_matrix(matrix_mac_args(e, base_slot, Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
+        } else {
         MacArgs a;
         a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
         a.h = e->H; a.h_ch_stride = (long)e->B * e->N;
@@ -643,6 +804,7 @@ static int run_chunk_pair(bfir_engine *e, const void *d_in, long in_stride, void
         a.n_t = tc; a.n_ch = e->GC; a.N = e->N; a.realsize = e->s; a.B = e->B;
         a.interleaved = 1;
         launch_mac(a, sm);
+        }
     }
     if (!il) {
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
@@ -653,9 +815,9 @@ static int run_chunk_pair(bfir_engine *e, const void *d_in, long in_stride, void
         InvPairArgs a;
         a.y = (const float *)Y; a.y_ch_stride = (long)e->chunk * e->N;
         a.raw = (float *)d_out; a.eng_stride = out_stride / 4; a.frame_off = frame_off;
-        a.C = e->C; a.n_eng = e->n_eng; a.n_t = tc;
+        a.C = e->Co; a.n_eng = e->n_eng; a.n_t = tc;
         a.scale = (float)e->out_scale; a.max = (float)e->of_max;
-        a.overflow = e->d_of; a.of_shard_stride = e->GC; a.bad_block = e->d_bad; a.block_base = block_base; a.bad_host = e->bad_host_cur;
+        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = block_base; a.bad_host = e->bad_host_cur;
         a.tp = e->pair_tp;
         launch_inv_pair(e->plan2, a, st);
     }
@@ -708,6 +870,9 @@ static int run_chunk_direct(bfir_engine *e, const void *d_in, long in_stride, vo
     void *Y = e->Yb[e->pipe3 ? par : 0];
     {
         ProfScope ps(e, BFIR_K_MAC, sm);
+        if (e->matrix) {
+            if (launch_mac_matrix(matrix_mac_args(e, base_slot, Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
+        } else {
         MacArgs a;
         a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
         a.h = e->H; a.h_ch_stride = (long)e->B * e->N;
@@ -716,6 +881,7 @@ static int run_chunk_direct(bfir_engine *e, const void *d_in, long in_stride, vo
         a.n_t = tc; a.n_ch = e->GC; a.N = e->N; a.realsize = e->s; a.B = e->B;
         a.interleaved = e->ilv;
         launch_mac(a, sm);
+        }
     }
     if (!il) {
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
@@ -726,10 +892,10 @@ static int run_chunk_direct(bfir_engine *e, const void *d_in, long in_stride, vo
         InvArgs a;
         a.src = Y; a.src_ch_stride = (long)e->chunk * e->N;
         a.dst = nullptr; a.dst_ch_stride = 0;
-        a.n_t = tc; a.n_ch = e->GC;
+        a.n_t = tc; a.n_ch = e->GCo;
         a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
-        a.raw_bytes = e->out_bytes; a.raw = d_out; a.raw_eng_stride = out_stride / e->out_bytes; a.frame_off = frame_off; a.C = e->C;
-        a.max = e->of_max; a.overflow = e->d_of; a.of_shard_stride = e->GC; a.bad_block = e->d_bad; a.block_base = block_base; a.bad_host = e->bad_host_cur;
+        a.raw_bytes = e->out_bytes; a.raw = d_out; a.raw_eng_stride = out_stride / e->out_bytes; a.frame_off = frame_off; a.C = e->Co;
+        a.max = e->of_max; a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = block_base; a.bad_host = e->bad_host_cur;
         launch_inv(e->plan, a, st);
     }
     if (e->pipe3 && !il) HIP_TRY(hipEventRecord(e->ev_inv[par], st));
@@ -742,6 +908,10 @@ static int run_chunk_direct(bfir_engine *e, const void *d_in, long in_stride, vo
 static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride,
                      long frame_off, int tc, int block_base, hipStream_t st, hipEvent_t input_ready)
 {
+    if (e->matrix) {   // pair or direct path (engine_create)
+        const int rc = matrix_chunk_ok(e, tc);
+        if (rc != BFIR_OK) return rc;
+    }
     if (e->pair) return run_chunk_pair(e, d_in, in_stride, d_out, out_stride, frame_off, tc, block_base, st, input_ready);
     if (e->direct) return run_chunk_direct(e, d_in, in_stride, d_out, out_stride, frame_off, tc, block_base, st, input_ready);
     const int par = (int)(e->chunk_seq & 1);
@@ -852,6 +1022,14 @@ static int ensure_chunk(bfir_engine *e, int n_blocks)
         long want = (8L * 4096 * 4096) / ((long)e->GC * e->L);
         want = std::max(4096L, std::min(32768L, want));
         limit = (int)std::max(16L, std::min(want, (slots - e->B) / 2));
+        if (e->matrix) {
+            // the input ring and the output products separately: each Yb of n_out spectra per block within 4 GiB too,
+            // and the work per launch counted by the wider side
+            const int wide = std::max(e->C, e->Co);
+            const long yslots = (long)((4ull << 30) / ((size_t)e->Co * cbuf_bytes(e)));
+            want = std::max(4096L, std::min(32768L, (8L * 4096 * 4096) / ((long)wide * e->L)));
+            limit = (int)std::max(16L, std::min(std::min(want, (slots - e->B) / 2), yslots));
+        }
     }
     // HP-TPDF dither is a recursion over a channel's samples (dither.hip: one lane walks them in order), so a
     // launch's length is its run time: bound it (64 blocks: the serial walk stays in the milliseconds and the
@@ -954,7 +1132,7 @@ static int ensure_staging(bfir_engine *e, int min_blocks = 0)
 {
     const int hc = std::max(host_chunk(e), min_blocks);
     const size_t bin = (size_t)e->n_eng * hc * e->L * e->C * e->in_bytes;
-    const size_t bout = (size_t)e->n_eng * hc * e->L * e->C * e->out_bytes;
+    const size_t bout = (size_t)e->n_eng * hc * e->L * e->Co * e->out_bytes;
     if (e->stage_bytes_in >= bin && e->stage_bytes_out >= bout) return BFIR_OK;
     for (int i = 0; i < 2; i++) {
         if (e->pin_in[i]) (void)hipHostFree(e->pin_in[i]);
@@ -994,14 +1172,15 @@ static int run_small(bfir_engine *e, const void *inbuf, void *outbuf, int n_bloc
     if (e->async_pending) { HIP_TRY(hipDeviceSynchronize()); e->async_pending = false; }
     if (!e->h_bad) { HIP_TRY(hipHostMalloc((void **)&e->h_bad, sizeof(int) * kSmallRun, hipHostMallocDefault)); }
     for (int t = 0; t < kSmallRun; t++) e->h_bad[t] = 0;
-    const size_t per_in = (size_t)n_blocks * e->L * e->C * e->in_bytes, per_out = (size_t)n_blocks * e->L * e->C * e->out_bytes;
+    const size_t per_in = (size_t)n_blocks * e->L * e->C * e->in_bytes, per_out = (size_t)n_blocks * e->L * e->Co * e->out_bytes;
     memcpy(e->pin_in[0], inbuf, per_in * e->n_eng);       // engine after engine, n_blocks * L frames each: same layout
     // Frames wider than what one workgroup of the fused FFT kernels consumes (a channel pair or one channel of
     // many): every workgroup would pull its 8 bytes of each frame across the host link on its own (measured:
     // 26 us per FFT kernel for one block of the 8-channel headline shape, against 8 us for stereo frames).
     // Those engines get the block into HBM and out of it by a copy kernel moving whole lines: two more
     // launches, ~35 us less per call.
-    const bool bounce = (e->pair || e->direct) && (size_t)e->C * e->in_bytes > 8 && !getenv("BFIR_NO_BOUNCE");
+    const bool bounce = (e->pair || e->direct) && ((size_t)e->C * e->in_bytes > 8 || (e->matrix && (size_t)e->Co * e->out_bytes > 8)) &&
+                        !getenv("BFIR_NO_BOUNCE");
     const void *src = e->pin_in[0];
     void *dst = e->pin_out[0];
     if (bounce) {
@@ -1054,7 +1233,7 @@ extern "C" int bfir_engine_run(bfir_engine *e, const void *inbuf, void *outbuf, 
     if (rc != BFIR_OK) return rc;
     rc = ensure_staging(e);
     if (rc != BFIR_OK) return rc;
-    const size_t fin = (size_t)e->C * e->in_bytes, fout = (size_t)e->C * e->out_bytes;  // bytes per frame
+    const size_t fin = (size_t)e->C * e->in_bytes, fout = (size_t)e->Co * e->out_bytes;  // bytes per frame
     const size_t eng_in = (size_t)n_blocks * e->L * fin, eng_out = (size_t)n_blocks * e->L * fout;
     const int hc = host_chunk(e);
     const int nchunks = (n_blocks + hc - 1) / hc;
@@ -1113,7 +1292,7 @@ extern "C" void bfir_engine_reset(bfir_engine *e)
     // zeroed ring reproduces; the time-domain history is NOT cleared, so both
     // input_timecbuf halves are kept (copied out of the work buffers).
     (void)materialise_history(e);
-    (void)hipMemset(e->d_of, 0, sizeof(DevOverflow) * e->GC * BFIR_OF_SHARDS);
+    (void)hipMemset(e->d_of, 0, sizeof(DevOverflow) * e->GCo * BFIR_OF_SHARDS);
     // block t < B-1 of the new run still reads slots (t - i) mod ring, i > t: the B-1 slots at the top of
     // every channel's ring.  Only those need to read as zero; the rest is rewritten before it is read.
     if (e->B > 1) {
@@ -1128,16 +1307,16 @@ extern "C" void bfir_engine_reset(bfir_engine *e)
 
 extern "C" int bfir_engine_get_overflow(bfir_engine *e, int channel, bfir_overflow *of)
 {
-    if (!e || !of || channel < 0 || channel >= e->GC) return BFIR_ERR_ARG;
+    if (!e || !of || channel < 0 || channel >= e->GCo) return BFIR_ERR_ARG;   // an output of a matrix engine
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     // the copies of the counters (kernels.h, BFIR_OF_SHARDS): counts add up, peaks are maxima (the bit patterns of
     // non-negative floats order like integers); the dither kernel keeps its running state in copy 0
-    std::vector<DevOverflow> all((size_t)e->GC * BFIR_OF_SHARDS);
+    std::vector<DevOverflow> all((size_t)e->GCo * BFIR_OF_SHARDS);
     HIP_TRY(hipMemcpy(all.data(), e->d_of, all.size() * sizeof(DevOverflow), hipMemcpyDeviceToHost));
     DevOverflow d = all[channel];
     for (int sh = 1; sh < BFIR_OF_SHARDS; sh++) {
-        const DevOverflow &o = all[(size_t)sh * e->GC + channel];
+        const DevOverflow &o = all[(size_t)sh * e->GCo + channel];
         d.n_overflows += o.n_overflows;
         d.intlargest = std::max(d.intlargest, o.intlargest);
         d.largest_bits = std::max(d.largest_bits, o.largest_bits);

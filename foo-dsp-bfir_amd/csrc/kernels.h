@@ -153,6 +153,22 @@ constexpr int BFIR_MAC_SYS_MAX_B = 256;   // partitions the systolic MAC takes (
 bool mac_sys_supported(const MacArgs &a);
 void launch_mac_sys(const MacArgs &a, hipStream_t s);
 
+// matrix.hip: the partition sums of a matrix engine (n_in inputs -> n_out outputs, one filter per pair),
+//   Y[o][t] = sum_{i < n_in} sum_{p < nblk[o][i]} X[i][slot(t - p)] * H[o][i][p],
+// inputs in order, partitions in order within an input: the fma chain of every other MAC here.  nblk = 0: no path (skipped).
+constexpr int BFIR_MAT_MAX = 8;            // inputs / outputs of a matrix engine (BFIR_MAXCHANNELS)
+constexpr int BFIR_MAT_SMALL_MAX = 4;      // output blocks per launch up to which the one-block-per-lane form runs
+struct MatArgs {
+    const void *x; long x_ch_stride; int ring, base_slot;     // delay line [n_in][ring][N]
+    const void *h; long h_pair_stride;                       // [n_out][n_in][B][N]: pair (o, i) at (o n_in + i) h_pair_stride
+    int nblk[BFIR_MAT_MAX * BFIR_MAT_MAX];                   // [o n_in + i]: partitions of h_{o,i}, by value (kernel argument)
+    void *y; long y_ch_stride;                               // [n_out][n_t][N]
+    int n_t, n_in, n_out, N, realsize;
+    int interleaved;                                         // layout of x, h and y, as in FwdArgs
+};
+bool mac_matrix_supported(const MatArgs &a);               // the grid of the launch fits
+int launch_mac_matrix(const MatArgs &a, hipStream_t s);    // 0, or -1 if !mac_matrix_supported(a) (nothing launched)
+
 // a11 + a12: inverse real FFT of Y[gc][t] (grouped layout, times in_scale),
 // first L samples to dst + gc*dst_ch_stride + t*L.
 struct InvArgs {

@@ -1,0 +1,220 @@
+// matrix.hip -- k_mac_matrix: the partition sums of a matrix engine (n_in inputs -> n_out outputs, one filter per pair).
+//
+//     Y[o][t](k) = sum_{i < n_in} sum_{p < nblk[o][i]} X[i][slot(t - p)](k) H[o][i][p](k)
+//
+// per bin k, inputs in index order, partitions p = 0 .. nb - 1 within an input: ONE fma chain per (output, bin, block) with
+// the four fmas of k_mac_small / cmac4 per term.  With a single filter in an output's row the chain is the diagonal MAC's,
+// bit for bit.  A pair with nblk = 0 (a NULL filter) is skipped, never multiplied by zero: a NaN in an input no filter reads
+// reaches no output.
+//
+// One lane owns one bin, a tile of TT consecutive output blocks and the accumulators of NO outputs (2 NO TT registers).  Per
+// input it walks the partitions in order with a window of TT delay-line spectra in registers, X[t0 + j - p] for j < TT: step
+// p loads ONE new spectrum (X[t0 - p], in place of the one nobody needs any more) and the NO filter spectra H[o][i][p], then
+// does NO x TT complex MACs -- every X load feeds NO TT of them, every H load TT.  Operands are fetched one step ahead.
+// Bin 0 (DC | Nyquist: two independent real sums) is carried by the wave that holds it (DCNY), with a select per term.
+// Every (output, bin, block) of the launch is stored exactly once, outputs without any filter as zeros: Y needs no clearing.
+// Offsets into X, H and Y are 64-bit; the grid is the only limit (mac_matrix_supported).
+#include "kernels.h"
+
+#include <algorithm>
+#include <climits>
+
+#include "fft_lds.h"
+
+namespace bfir {
+
+namespace {
+
+// one complex multiply-add of k_mac_small's order; DCNY: lane k == 0 keeps two real sums instead
+template <bool DCNY, typename T>
+__device__ __forceinline__ void mat_cmac(T &ar, T &ai, T xr, T xi, T hr, T hi, bool k0)
+{
+    const T r1 = fma(xr, hr, ar);
+    const T r2 = fma(-xi, hi, r1);
+    const T i2 = fma(xi, hr, fma(xr, hi, ai));
+    if constexpr (DCNY) {
+        const T ny = fma(xi, hi, ai);
+        ar = k0 ? r1 : r2; ai = k0 ? ny : i2;
+    } else {
+        ar = r2; ai = i2;
+    }
+}
+
+template <typename T, bool ILV>
+__device__ __forceinline__ void mat_ld(const T *__restrict__ s, int ore, int oim, T &re, T &im)
+{
+    if constexpr (ILV) {
+        using V2 = typename Vec2<T>::type;
+        const V2 v = *(const V2 *)(s + ore);
+        re = v.x; im = v.y;
+    } else {
+        re = s[ore]; im = s[oim];
+    }
+}
+
+template <typename T, bool ILV, int NO, int TT, bool DCNY>
+__device__ __forceinline__ void mat_tile(const MatArgs &a, int o0, int t0, int ore, int oim, bool k0,
+                                         T (&ar)[NO][TT], T (&ai)[NO][TT])
+{
+    const long N = a.N;
+    const int ring = a.ring;
+    const int sl = (a.base_slot + t0) % ring;                    // delay-line slot of block t0
+    for (int i = 0; i < a.n_in; i++) {
+        int nb[NO], nbm = 0, om = 0;
+#pragma unroll
+        for (int o = 0; o < NO; o++) {
+            nb[o] = o0 + o < a.n_out ? a.nblk[(o0 + o) * a.n_in + i] : 0;
+            if (nb[o] > nbm) { nbm = nb[o]; om = o; }
+        }
+        if (nbm == 0) continue;                                  // no filter of this tile reads input i
+        const T *__restrict__ Xi = (const T *)a.x + (long)i * a.x_ch_stride;
+        // filter spectra of (o, i); a pair without a filter is pointed at one with nbm partitions (loaded, never used)
+        const T *__restrict__ Hp[NO];
+#pragma unroll
+        for (int o = 0; o < NO; o++)
+            Hp[o] = (const T *)a.h + ((long)(o0 + (nb[o] > 0 ? o : om)) * a.n_in + i) * a.h_pair_stride;
+        // window: slot (j - p) mod TT holds X[t0 + j - p].  In the last tile of a launch the blocks t0 + j >= n_t are slots
+        // the NEXT chunk's forward transform may be writing at this moment (ring = 2 chunk + B keeps the read in bounds):
+        // their values only reach accumulators that are never stored, so that race is harmless and needs no wait
+        T wr[TT], wi[TT];
+#pragma unroll
+        for (int j = 0; j < TT; j++) {
+            int sj = sl + j; if (sj >= ring) sj -= ring;
+            mat_ld<T, ILV>(Xi + (long)sj * N, ore, oim, wr[j], wi[j]);
+        }
+        T qxr = (T)0, qxi = (T)0, qhr[NO], qhi[NO];              // operands of the next step (step 0 takes no new X)
+#pragma unroll
+        for (int o = 0; o < NO; o++) mat_ld<T, ILV>(Hp[o], ore, oim, qhr[o], qhi[o]);
+        for (int p0 = 0; p0 < nbm; p0 += TT) {
+#pragma unroll
+            for (int ii = 0; ii < TT; ii++) {
+                const int p = p0 + ii;
+                if (p < nbm) {                                   // wave-uniform
+                    if (p > 0) { wr[(TT - ii) % TT] = qxr; wi[(TT - ii) % TT] = qxi; }
+                    // prefetch step p + 1 (clamped to the last step: in range, not used); each H register pair is
+                    // reloaded as soon as its output's MACs have read it, so H costs 2 NO registers, not 4 NO
+                    const int pn = p + 1 < nbm ? p + 1 : p;
+                    int sn = sl - pn; if (sn < 0) sn += ring;       // X[t0 - pn] enters the window at step pn
+                    mat_ld<T, ILV>(Xi + (long)sn * N, ore, oim, qxr, qxi);
+#pragma unroll
+                    for (int o = 0; o < NO; o++) {
+                        if (p < nb[o]) {                         // wave-uniform: pairs without this partition are skipped
+#pragma unroll
+                            for (int j = 0; j < TT; j++) {
+                                const int idx = (j - ii + TT) % TT;
+                                mat_cmac<DCNY>(ar[o][j], ai[o][j], wr[idx], wi[idx], qhr[o], qhi[o], k0);
+                            }
+                        }
+                        const int po = pn < nb[o] ? pn : (nb[o] > 0 ? nb[o] - 1 : pn);
+                        mat_ld<T, ILV>(Hp[o] + (long)po * N, ore, oim, qhr[o], qhi[o]);
+                    }
+                }
+            }
+        }
+    }
+}
+
+}  // namespace
+
+// grid: x = (bin tile, time tile), XCD-aware as k_mac (each XCD a contiguous range, bin tile major, so its L2 holds the
+// slice of H and X of its bins); y = output tile of NO outputs
+template <typename T, bool ILV, int NO, int TT>
+__global__ __launch_bounds__(256, 4) void k_mac_matrix(MatArgs a, int nbt, int nTT)
+{
+    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
+    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    const int bt = w / nTT, tt = w - bt * nTT;
+    const int k = bt * blockDim.x + threadIdx.x;                 // bin
+    const int N2 = a.N / 2;
+    if (k >= N2) return;
+    const int t0 = tt * TT, o0 = blockIdx.y * NO;
+    const int ore = ILV ? 2 * k : 8 * (k >> 2) + (k & 3), oim = ILV ? ore + 1 : ore + 4;
+    T ar[NO][TT], ai[NO][TT];
+#pragma unroll
+    for (int o = 0; o < NO; o++)
+#pragma unroll
+        for (int j = 0; j < TT; j++) { ar[o][j] = (T)0; ai[o][j] = (T)0; }
+    const bool wave0 = __builtin_amdgcn_readfirstlane((int)(bt == 0 && threadIdx.x < 64)) != 0;
+    if (wave0) mat_tile<T, ILV, NO, TT, true>(a, o0, t0, ore, oim, k == 0, ar, ai);
+    else mat_tile<T, ILV, NO, TT, false>(a, o0, t0, ore, oim, false, ar, ai);
+#pragma unroll
+    for (int o = 0; o < NO; o++) {
+        if (o0 + o >= a.n_out) break;
+        T *__restrict__ Y = (T *)a.y + (long)(o0 + o) * a.y_ch_stride;
+#pragma unroll
+        for (int j = 0; j < TT; j++) {
+            if (t0 + j < a.n_t) {
+                T *yo = Y + (long)(t0 + j) * a.N;
+                if constexpr (ILV) {
+                    using V2 = typename Vec2<T>::type;
+                    V2 v; v.x = ar[o][j]; v.y = ai[o][j];
+                    *(V2 *)(yo + ore) = v;
+                } else {
+                    yo[ore] = ar[o][j]; yo[oim] = ai[o][j];
+                }
+            }
+        }
+    }
+}
+
+// Output tile NO: the output count rounded up to a power of two, at most 4 (fp32) / 2 (fp64), more outputs in several tiles
+// (grid y); time tile TT: 1 for the latency path (a handful of blocks), else 8 (fp32; fp64 one output) or 4 (fp64): 64
+// accumulator registers.  Larger tiles (fp32 8 x 4, fp64 4 x 4) pass the 128 registers of four waves per SIMD and spill.
+static int mat_no(const MatArgs &a) { const int cap = a.realsize == 4 ? 4 : 2; int no = 1; while (no < a.n_out && no < cap) no *= 2; return no; }
+static int mat_tt(const MatArgs &a, int no)
+{
+    if (a.n_t <= BFIR_MAT_SMALL_MAX) return 1;
+    return a.realsize == 4 ? 8 : (no == 1 ? 8 : 4);
+}
+
+bool mac_matrix_supported(const MatArgs &a)
+{
+    if (a.n_in < 1 || a.n_in > BFIR_MAT_MAX || a.n_out < 1 || a.n_out > BFIR_MAT_MAX || a.n_t < 0) return false;
+    if (a.N < 2 || (a.realsize != 4 && a.realsize != 8)) return false;
+    const int no = mat_no(a), tt = mat_tt(a, no);
+    const long threads = std::min(256, std::max(64, a.N / 2));   // as launch_mac_matrix_t
+    const long nbt = (a.N / 2 + threads - 1) / threads, nTT = ((long)a.n_t + tt - 1) / tt;
+    return nbt * nTT <= INT_MAX && nbt * nTT * threads <= (long)UINT32_MAX;   // workgroup ids in int, threads per dimension
+}
+
+template <typename T, bool ILV, int NO> static void launch_mac_matrix_t(const MatArgs &a, int tt, hipStream_t s)
+{
+    const int threads = std::min(256, std::max(64, a.N / 2));
+    const int nbt = (a.N / 2 + threads - 1) / threads;
+    const int n_ot = (a.n_out + NO - 1) / NO;
+    if (tt == 1) {
+        hipLaunchKernelGGL((k_mac_matrix<T, ILV, NO, 1>), dim3(nbt * a.n_t, n_ot), dim3(threads), 0, s, a, nbt, a.n_t);
+    } else {
+        constexpr int TTB = sizeof(T) == 4 ? 8 : (NO == 1 ? 8 : 4);
+        const int nTT = (a.n_t + TTB - 1) / TTB;
+        hipLaunchKernelGGL((k_mac_matrix<T, ILV, NO, TTB>), dim3(nbt * nTT, n_ot), dim3(threads), 0, s, a, nbt, nTT);
+    }
+}
+
+template <typename T, bool ILV> static void launch_mac_matrix_l(const MatArgs &a, int no, int tt, hipStream_t s)
+{
+    switch (no) {
+    case 1: launch_mac_matrix_t<T, ILV, 1>(a, tt, s); break;
+    case 2: launch_mac_matrix_t<T, ILV, 2>(a, tt, s); break;
+    default:
+        if constexpr (sizeof(T) == 4) launch_mac_matrix_t<T, ILV, 4>(a, tt, s);
+        break;
+    }
+}
+
+int launch_mac_matrix(const MatArgs &a, hipStream_t s)
+{
+    if (!mac_matrix_supported(a)) return -1;
+    if (a.n_t == 0) return 0;
+    const int no = mat_no(a), tt = mat_tt(a, no);
+    if (a.realsize == 4) {
+        if (a.interleaved) launch_mac_matrix_l<float, true>(a, no, tt, s);
+        else launch_mac_matrix_l<float, false>(a, no, tt, s);
+    } else {
+        if (a.interleaved) launch_mac_matrix_l<double, true>(a, no, tt, s);
+        else launch_mac_matrix_l<double, false>(a, no, tt, s);
+    }
+    return 0;
+}
+
+}  // namespace bfir

@@ -177,3 +177,63 @@ class Brutefir:
         if rc != 0:
             raise BfirError(rc, "bfir_engine_read_coeff")
         return dst
+
+
+class BrutefirMatrix(Brutefir):
+    """n_in inputs -> n_out outputs with one filter per (output, input) pair (bfir_engine_create_matrix):
+    y_o = sum_i h_{o,i} * x_i.  Frames are FLOAT_LE or FLOAT64_LE; the default is the working precision's.
+
+    run / run_device / sync / reset / set_chunk / set_profiling / profile / close are Brutefir's; overflow(o) is
+    output o's."""
+
+    def __init__(self, filter_length, filter_blocks, realsize, n_in, n_out, in_format=None, out_format=None, device=0):
+        dflt = SAMPLE_FORMAT_FLOAT_LE if realsize == 4 else SAMPLE_FORMAT_FLOAT64_LE
+        self.L, self.B, self.s = filter_length, filter_blocks, realsize
+        self.n_in, self.n_out = n_in, n_out
+        self.C = n_in
+        self.in_format = dflt if in_format is None else in_format
+        self.out_format = dflt if out_format is None else out_format
+        self.n_engines, self.device = 1, device
+        self._lib = _lib.load()
+        err = C.c_int(0)
+        self._h = self._lib.bfir_engine_create_matrix(filter_length, filter_blocks, realsize, n_in, n_out,
+                                                      self.in_format, self.out_format, device, C.byref(err))
+        if not self._h:
+            raise BfirError(err.value, "bfir_engine_create_matrix")
+
+    def set_coeff(self, rows, length=None, coeff_blocks=None, scale=1.0):
+        """rows[o][i]: taps of h_{o,i} (working precision) or None = no path from input i to output o.
+        Returns 0 or ERR_COEFF (a NaN / Inf tap)."""
+        assert len(rows) == self.n_out and all(len(r) == self.n_in for r in rows)
+        rd = _real_dtype(self.s)
+        arrs = [None if h is None else np.ascontiguousarray(h, dtype=rd) for r in rows for h in r]
+        given = [a for a in arrs if a is not None]
+        length = (given[0].size if given else 0) if length is None else length
+        coeff_blocks = self.B if coeff_blocks is None else coeff_blocks
+        ptrs = (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
+        return self._lib.bfir_engine_set_coeff_matrix(self._h, ptrs, length, coeff_blocks, float(scale))
+
+    def run(self, inbuf, outbuf=None):
+        """inbuf: [n_blocks*L, n_in] frames in the input format.  Returns (rc, outbuf [n_blocks*L, n_out])."""
+        x = np.ascontiguousarray(inbuf, dtype=_FMT_DTYPES[self.in_format])
+        frames = x.shape[0]
+        assert x.ndim == 2 and x.shape[1] == self.n_in and frames % self.L == 0
+        if outbuf is None:
+            outbuf = raw_frames(self.out_format, (frames, self.n_out))
+        assert outbuf.shape == (frames, self.n_out) and outbuf.dtype == _FMT_DTYPES[self.out_format]
+        rc = self._lib.bfir_engine_run(self._h, x.ctypes.data, outbuf.ctypes.data, frames // self.L)
+        return rc, outbuf
+
+    def check_overflows(self):
+        ofs = [self.overflow(o) for o in range(self.n_out)]
+        if not any(o.n_overflows for o in ofs):
+            return []
+        return [(n, o.n_overflows, float("-inf") if o.largest == 0.0 else 20.0 * np.log10(o.largest / o.max))
+                for n, o in enumerate(ofs)]
+
+    def coeff_block(self, output, input, block):
+        dst = np.zeros(2 * self.L, dtype=_real_dtype(self.s))
+        rc = self._lib.bfir_engine_read_coeff_matrix(self._h, output, input, block, dst.ctypes.data)
+        if rc != 0:
+            raise BfirError(rc, "bfir_engine_read_coeff_matrix")
+        return dst

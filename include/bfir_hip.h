@@ -118,6 +118,15 @@ bfir_engine *bfir_engine_create_batch(int n_engines, int filter_length, int filt
                                       int realsize, int channels, int in_format, int out_format,
                                       int sampling_rate, int apply_dither, int device, int *err);
 
+/* n_inputs -> n_outputs, one filter per (output, input) pair: output o is the sum over the inputs i of input i
+ * convolved with h_{o,i} (a BruteFIR filter graph folded into one matrix).  1 <= n_inputs, n_outputs <=
+ * BFIR_MAXCHANNELS.  Frames: n_inputs-channel frames in, n_outputs-channel frames out, FLOAT_LE or FLOAT64_LE each
+ * (other formats: BFIR_ERR_UNSUPPORTED).  No dither (float outputs only), one engine (no batch).  Every other
+ * bfir_engine_* entry point works on it; get_overflow's `channel` is an output.  bfir_engine_set_coeff, _set_coeff_at
+ * and _read_coeff return BFIR_ERR_UNSUPPORTED on a matrix engine, the two matrix calls below the same on others. */
+bfir_engine *bfir_engine_create_matrix(int filter_length, int filter_blocks, int realsize, int n_inputs,
+                                       int n_outputs, int in_format, int out_format, int device, int *err);
+
 void bfir_engine_destroy(bfir_engine *e);
 
 /* brutefir::is_initialized */
@@ -131,6 +140,12 @@ int bfir_engine_is_initialized(const bfir_engine *e);
  * Returns 0, or BFIR_ERR_COEFF on a NaN/Inf tap. */
 int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length,
                           int coeff_blocks, double scale);
+/* coeffs[o * n_inputs + i]: taps of h_{o,i} in working precision, or NULL = no path from input i to output o
+ * (skipped, not multiplied by zero).  length / coeff_blocks / scale as bfir_engine_set_coeff.  A NaN/Inf tap:
+ * BFIR_ERR_COEFF and the engine is uninitialised.  Mid-stream the delay line is kept and the next block uses the
+ * new filters. */
+int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *coeffs, int length, int coeff_blocks,
+                                 double scale);
 /* the same for engine `engine_index` of a batch */
 int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const void *const *coeffs,
                              int n_coeffs, int length, int coeff_blocks, double scale);
@@ -173,6 +188,8 @@ int bfir_engine_get_profile(bfir_engine *e, int kernel, double *total_ms, int64_
 
 /* copy partition spectrum `block` of global channel `channel` to host (n_fft reals) */
 int bfir_engine_read_coeff(bfir_engine *e, int channel, int block, void *dst);
+/* partition spectrum `block` of h_{output,input} of a matrix engine, grouped layout, as bfir_engine_read_coeff */
+int bfir_engine_read_coeff_matrix(bfir_engine *e, int output, int input, int block, void *dst);
 
 /* ------------------------------------------------------------------ */
 /* stage level: fftw_convolver methods on host buffers                 */
