@@ -11,9 +11,12 @@
 //   saved 2 x [GC][L]      history blocks kept across reset / reallocation
 // GC = n_eng * C global channels.  A matrix engine (bfir_engine_create_matrix: one engine, C = n_in inputs, Co = n_out
 // outputs, one filter per (output, input) pair) keeps the input side -- X, tails, saved -- for its C inputs and the output
-// side -- Y, the overflow statistics, the output frames -- for its Co outputs; H is [Co][C][B][N], the MAC k_mac_matrix.  A run of n blocks is cut into chunks of at
-// most `chunk` blocks; each chunk is five launches, the first two on a side
-// stream so that they overlap the last three of the chunk before.
+// side -- Y, the overflow statistics, the output frames -- for its Co outputs; H is [Co][C][B][N], the MAC k_mac_matrix.
+// A run of n blocks is cut into chunks of at most `chunk` blocks.  A chunk is front (fwd; stage_in before it on the
+// staging path), MAC and back (inv; stage_out after it on the staging path), software-pipelined over three streams.
+// What is written once here, because every path shares it: the path an engine takes (choose_path), the filter
+// loader (load_filters) and the chunk schedule (run_chunk: streams, events, the MAC; queue_fwd / queue_inv and the
+// two staging launches are what differs per path).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -193,10 +196,9 @@ static int materialise_history(bfir_engine *e)
     return BFIR_OK;
 }
 
-static void free_work(bfir_engine *e)
+// the pinned + device staging buffers of the host-pointer path (ensure_staging)
+static void free_staging(bfir_engine *e)
 {
-    void **bufs[] = {&e->X, &e->Yb[0], &e->Yb[1], &e->tin[0], &e->tin[1], &e->tout};
-    for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
     for (int i = 0; i < 2; i++) {
         if (e->pin_in[i]) (void)hipHostFree(e->pin_in[i]);
         if (e->pin_out[i]) (void)hipHostFree(e->pin_out[i]);
@@ -205,6 +207,13 @@ static void free_work(bfir_engine *e)
         e->pin_in[i] = e->pin_out[i] = e->dev_in[i] = e->dev_out[i] = nullptr;
     }
     e->stage_bytes_in = e->stage_bytes_out = 0;
+}
+
+static void free_work(bfir_engine *e)
+{
+    void **bufs[] = {&e->X, &e->Yb[0], &e->Yb[1], &e->tin[0], &e->tin[1], &e->tout};
+    for (void **b : bufs) { if (*b) (void)hipFree(*b); *b = nullptr; }
+    free_staging(e);
     e->chunk = e->ring = 0;
     if (e->h_bad) { (void)hipHostFree(e->h_bad); e->h_bad = nullptr; }
 }
@@ -245,6 +254,76 @@ static int alloc_work(bfir_engine *e, int chunk)
     return BFIR_OK;
 }
 
+// Which kernels the engine runs on and how a chunk is scheduled: ilv (spectrum layout), pair / pair_tp / pair_cap,
+// direct, pipe3, serial.  Every switch is read HERE, once per engine, at creation.
+static void choose_path(bfir_engine *e)
+{
+    e->ilv = e->s == 4 && e->N >= 512;   // fp32: (re, im) pairs from N = 512 (whole 256-bin columns)
+    // BFIR_PAIR=0 (tuning aid) keeps the planar staging kernels
+    const char *pv = getenv("BFIR_PAIR");
+    // odd channel counts pair blocks in time (BFIR_PAIR_TIME=0 keeps them on the general path)
+    const char *tv = getenv("BFIR_PAIR_TIME");
+    const bool tp_ok = !(tv && atoi(tv) == 0);
+    e->pair_tp = (e->C % 2) == 1 && tp_ok;
+    e->pair = e->ilv && e->in_fmt == 8 && e->out_fmt == 8 && ((e->C % 2) == 0 || e->pair_tp) &&
+              pair_supported(e->L) && !(pv && atoi(pv) == 0);
+    e->pair_tp = e->pair_tp && e->pair;
+    if (e->matrix) {
+        // channel pairs on both sides or direct mode: time pairs transform blocks t, t + 1 together, so where a launch
+        // starts would change the bits of its blocks (a matrix engine's outputs do not depend on the chunking)
+        e->pair = e->pair && e->C % 2 == 0 && e->Co % 2 == 0;
+        e->pair_tp = false;
+        e->pair_cap = e->pair;
+    }
+    const char *dv = getenv("BFIR_DIRECT");
+    // worth it where a channel's samples are 8 bytes apart or wider units: FLOAT64 frames (any C), or one
+    // channel (contiguous samples), or float frames with an even channel count (the reference plug-in's own shape:
+    // fp64 arithmetic, float32 frames), which k_fwd / k_inv move a channel PAIR at a time with both channels in one
+    // workgroup (stereo: two whole frames per lane; wider frames since round 3: 33.5 -> ~40 Gsamples/s at 4-8 channels).  Other 4-byte samples at a stride
+    // (float frames, C > 2) are faster through the staging kernels (profiles/r02_other_configs.txt: one
+    // channel per workgroup ran the plug-in's shape at 11.4 instead of 20.6 Gsamples/s).  BFIR_DIRECT=1
+    // forces it (tests).
+    const bool stereo = e->in_bytes == 4 && e->out_bytes == 4 && (e->C % 2) == 0 && !e->ilv &&
+                        direct_stereo_supported(e->L, e->s);
+    // ... and, since round 3, any float / double frames of an fp64 engine whose transform the run kernels take (k_fwd_run /
+    // k_inv_run hide the strided loads under the transform: 3 / 5 channels of float32 frames 33 -> 41-42 Gsamples/s)
+    const bool wide = (e->in_bytes == 8 && e->out_bytes == 8) || e->C == 1 || stereo || run64_supported(e->L, e->s);
+    e->direct = !e->pair && fmt_is_native(e->in_fmt) && fmt_is_native(e->out_fmt) && !(pv && atoi(pv) == 0) &&
+                (dv ? atoi(dv) != 0 : wide);
+    if (e->matrix) e->direct = !e->pair;   // a matrix engine has no staging path: float frames only, direct where not paired
+    // fp64 engines whose transforms the run kernels take keep their spectra -- delay line, filter partitions, products --
+    // as (re, im) PAIRS like the fp32 engines, not in the reference's groups of four: one 16-byte access per bin in the
+    // MAC instead of two of 8, the forward kernel's spectrum straight from registers (no LDS staging), conflict-free reads
+    // in the inverse.  Only where every kernel on the engine's way reads pairs: direct mode, the systolic MAC (up to 256
+    // partitions) -- so the switches that pick other kernels keep the groups (all read HERE, at creation, for such engines).
+    // BFIR_F64_PAIRS=0: off (A/B).  Same arithmetic either way: the same bits.
+    {
+        const char *fp = getenv("BFIR_F64_PAIRS"), *ms = getenv("BFIR_MAC_SYS");
+        const bool other_mac = (ms && atoi(ms) == 0) || getenv("BFIR_MAC_BATCHED");
+        if (e->s == 8 && e->direct && pairs64_supported(e->L, e->s) && e->B <= BFIR_MAC_SYS_MAX_B && !other_mac &&
+            !(fp && atoi(fp) == 0))
+            e->ilv = true;
+    }
+    if (const char *pm = getenv("BFIR_PIPE")) { e->pipe3 = atoi(pm) >= 3; e->serial = atoi(pm) == 1; }
+    // fp64 engines: one stream.  Their kernels are bound by issue and latency, not by memory, each fills the GPU by itself, and
+    // three of them side by side only get into each other's way: the plug-in's shape 42.8 -> 45.9 Gsamples/s, 8 channels 42.5 ->
+    // 44.6, cfg5 43.1 either way (profiles/r03_fp64.txt).  The fp32 headline gains 10 % from the three-stream schedule.
+    else if (e->s == 8) { e->pipe3 = false; e->serial = true; }
+}
+
+// which family the engine runs on (tests read it; per-launch variants such as CPW = 2 depend on alignment and are not here)
+static void log_creation(const bfir_engine *e)
+{
+    char shape[64];
+    // a matrix engine's path=pair can give way to direct mode while an input feeds no output (bfir_engine_set_coeff_matrix logs it)
+    if (e->matrix) snprintf(shape, sizeof(shape), "matrix %d -> %d", e->C, e->Co);
+    else snprintf(shape, sizeof(shape), "%d x %d channels", e->n_eng, e->C);
+    bfir_logf("bfir engine: %s, partition %d, %d blocks, realsize %d on device %d. path=%s layout=%s run=%s",
+              shape, e->L, e->B, e->s, e->device,
+              e->pair_tp ? "time-pair" : e->pair ? "pair" : e->direct ? "direct" : "staging", e->ilv ? "pairs" : "grouped",
+              e->s == 8 && e->direct && run64_supported(e->L, e->s) ? "on" : "off");
+}
+
 // matrix: `channels` inputs, `channels_out` outputs, one engine (bfir_engine_create_matrix); else channels_out == channels
 static bfir_engine *engine_create(int n_engines, int filter_length, int filter_blocks, int realsize, int channels,
                                   int channels_out, bool matrix, int in_format, int out_format, int sampling_rate,
@@ -281,58 +360,7 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
     e->in_scale = fmt_info(in_format).isfloat ? 1.0 : 1.0 / fmt_full_scale(in_format);
     e->out_scale = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format);
     e->of_max = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format) - 1.0;
-    e->ilv = realsize == 4 && e->N >= 512;   // fp32: (re, im) pairs from N = 512 (whole 256-bin columns)
-    {   // BFIR_PAIR=0 (tuning aid) keeps the planar staging kernels
-        const char *pv = getenv("BFIR_PAIR");
-        // odd channel counts pair blocks in time (BFIR_PAIR_TIME=0 keeps them on the general path)
-        const char *tv = getenv("BFIR_PAIR_TIME");
-        const bool tp_ok = !(tv && atoi(tv) == 0);
-        e->pair_tp = (channels % 2) == 1 && tp_ok;
-        e->pair = e->ilv && in_format == 8 && out_format == 8 && ((channels % 2) == 0 || e->pair_tp) &&
-                  pair_supported(filter_length) && !(pv && atoi(pv) == 0);
-        e->pair_tp = e->pair_tp && e->pair;
-        if (matrix) {
-            // channel pairs on both sides or direct mode: time pairs transform blocks t, t + 1 together, so where a launch
-            // starts would change the bits of its blocks (a matrix engine's outputs do not depend on the chunking)
-            e->pair = e->pair && channels % 2 == 0 && channels_out % 2 == 0;
-            e->pair_tp = false;
-            e->pair_cap = e->pair;
-        }
-        const char *dv = getenv("BFIR_DIRECT");
-        // worth it where a channel's samples are 8 bytes apart or wider units: FLOAT64 frames (any C), or one
-        // channel (contiguous samples), or float frames with an even channel count (the reference plug-in's own shape:
-        // fp64 arithmetic, float32 frames), which k_fwd / k_inv move a channel PAIR at a time with both channels in one
-        // workgroup (stereo: two whole frames per lane; wider frames since round 3: 33.5 -> ~40 Gsamples/s at 4-8 channels).  Other 4-byte samples at a stride
-        // (float frames, C > 2) are faster through the staging kernels (profiles/r02_other_configs.txt: one
-        // channel per workgroup ran the plug-in's shape at 11.4 instead of 20.6 Gsamples/s).  BFIR_DIRECT=1
-        // forces it (tests).
-        const bool stereo = e->in_bytes == 4 && e->out_bytes == 4 && (channels % 2) == 0 && !e->ilv &&
-                            direct_stereo_supported(filter_length, realsize);
-        // ... and, since round 3, any float / double frames of an fp64 engine whose transform the run kernels take (k_fwd_run /
-        // k_inv_run hide the strided loads under the transform: 3 / 5 channels of float32 frames 33 -> 41-42 Gsamples/s)
-        const bool wide = (e->in_bytes == 8 && e->out_bytes == 8) || channels == 1 || stereo || run64_supported(filter_length, realsize);
-        e->direct = !e->pair && fmt_is_native(in_format) && fmt_is_native(out_format) && !(pv && atoi(pv) == 0) &&
-                    (dv ? atoi(dv) != 0 : wide);
-        if (matrix) e->direct = !e->pair;   // a matrix engine has no staging path: float frames only, direct where not paired
-        // fp64 engines whose transforms the run kernels take keep their spectra -- delay line, filter partitions, products --
-        // as (re, im) PAIRS like the fp32 engines, not in the reference's groups of four: one 16-byte access per bin in the
-        // MAC instead of two of 8, the forward kernel's spectrum straight from registers (no LDS staging), conflict-free reads
-        // in the inverse.  Only where every kernel on the engine's way reads pairs: direct mode, the systolic MAC (up to 256
-        // partitions) -- so the switches that pick other kernels keep the groups (all read HERE, at creation, for such engines).
-        // BFIR_F64_PAIRS=0: off (A/B).  Same arithmetic either way: the same bits.
-        {
-            const char *fp = getenv("BFIR_F64_PAIRS"), *ms = getenv("BFIR_MAC_SYS");
-            const bool other_mac = (ms && atoi(ms) == 0) || getenv("BFIR_MAC_BATCHED");
-            if (realsize == 8 && e->direct && pairs64_supported(filter_length, realsize) && filter_blocks <= BFIR_MAC_SYS_MAX_B && !other_mac &&
-                !(fp && atoi(fp) == 0))
-                e->ilv = true;
-        }
-    }
-    if (const char *pm = getenv("BFIR_PIPE")) { e->pipe3 = atoi(pm) >= 3; e->serial = atoi(pm) == 1; }
-    // fp64 engines: one stream.  Their kernels are bound by issue and latency, not by memory, each fills the GPU by itself, and
-    // three of them side by side only get into each other's way: the plug-in's shape 42.8 -> 45.9 Gsamples/s, 8 channels 42.5 ->
-    // 44.6, cfg5 43.1 either way (profiles/r03_fp64.txt).  The fp32 headline gains 10 % from the three-stream schedule.
-    else if (realsize == 8) { e->pipe3 = false; e->serial = true; }
+    choose_path(e);
     e->nblk.assign(matrix ? (size_t)e->Co * e->C : (size_t)e->GC, 0);   // matrix: [o C + i]
     e->eng_init.assign(n_engines, 0);
     int rc = fft_plan_create(&e->plan, filter_length, realsize);
@@ -393,19 +421,7 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
     }
     if (alloc_work(e, 1) != BFIR_OK) return fail(BFIR_ERR_HIP);
     if (hipDeviceSynchronize() != hipSuccess) return fail(BFIR_ERR_HIP);
-    // which family the engine runs on (tests read it; per-launch variants such as CPW = 2 depend on alignment and are not here)
-    if (matrix) {
-        // path=pair can give way to direct mode while an input feeds no output (bfir_engine_set_coeff_matrix logs it)
-        bfir_logf("bfir engine: matrix %d -> %d, partition %d, %d blocks, realsize %d on device %d. path=%s layout=%s run=%s",
-                  channels, channels_out, filter_length, filter_blocks, realsize, device, e->pair ? "pair" : "direct",
-                  e->ilv ? "pairs" : "grouped",
-                  realsize == 8 && e->direct && run64_supported(filter_length, realsize) ? "on" : "off");
-        return e;
-    }
-    bfir_logf("bfir engine: %d x %d channels, partition %d, %d blocks, realsize %d on device %d. path=%s layout=%s run=%s",
-              n_engines, channels, filter_length, filter_blocks, realsize, device,
-              e->pair_tp ? "time-pair" : e->pair ? "pair" : e->direct ? "direct" : "staging", e->ilv ? "pairs" : "grouped",
-              realsize == 8 && e->direct && run64_supported(filter_length, realsize) ? "on" : "off");
+    log_creation(e);
     return e;
 }
 
@@ -476,7 +492,61 @@ extern "C" int bfir_engine_set_chunk(bfir_engine *e, int blocks_per_launch)
     return BFIR_OK;
 }
 
-// coeff::preprocess_coeff + convolver_coeffs2cbuf for the C channels of one engine.
+// coeff::preprocess_coeff + convolver_coeffs2cbuf for n_rows filters, rows row0 .. of H: coeffs[n] (n < n_coeffs <= n_rows)
+// goes to row row0 + n, nb partitions each.  A NULL entry is an error (null_ok = false) or an all-zero filter, as are the
+// rows past n_coeffs.  Nothing is uploaded before every filter has passed the finite check.
+static int load_filters(bfir_engine *e, int row0, int n_rows, const void *const *coeffs, int n_coeffs, int length, int nb,
+                        double scale, bool null_ok)
+{
+    const size_t taps_pad = (size_t)nb * e->L;
+    const size_t cb = cbuf_bytes(e);
+    const size_t cnt = std::min((size_t)length, taps_pad);
+    // zero padded impulse per filter; a block past the end is all zero
+    // (coeff.cpp:315-339), taps are scaled in working precision (fftw_convolver.cpp:491,507)
+    std::vector<char> host((size_t)n_rows * taps_pad * e->s, 0);
+    for (int n = 0; n < n_coeffs; n++) {
+        if (!coeffs[n]) { if (null_ok) continue; return BFIR_ERR_ARG; }
+        bool finite = true;
+        if (e->s == 4) {
+            const float *src = (const float *)coeffs[n];
+            const float sc = (float)scale;
+            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite((double)(src[i] * sc));
+        } else {
+            const double *src = (const double *)coeffs[n];
+            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite(src[i] * scale);
+        }
+        if (!finite) {
+            bfir_logf("NaN or Inf value among coefficients.");
+            if (e->matrix) bfir_logf("Error preprocessing coefficient %d (output %d, input %d)", n, n / e->C, n % e->C);
+            else bfir_logf("Error preprocessing coefficient %d", n);
+            return BFIR_ERR_COEFF;
+        }
+        memcpy(host.data() + (size_t)n * taps_pad * e->s, coeffs[n], cnt * e->s);
+    }
+    void *d_taps = nullptr;
+    void *rows = (char *)e->H + (size_t)row0 * e->B * cb;
+    HIP_TRY(hipMalloc(&d_taps, host.size()));
+    HIP_TRY(hipMemcpyAsync(d_taps, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
+    HIP_TRY(hipMemsetAsync(rows, 0, (size_t)n_rows * e->B * cb, e->stream));
+    FwdArgs fa;                                                 // one "channel" per filter
+    // window of block b = [L zeros | taps b*L .. b*L+L)
+    fa.src = d_taps; fa.src_ch_stride = (long)taps_pad;
+    fa.prev = nullptr; fa.prev_ch_stride = 0;
+    fa.dst = rows; fa.dst_ch_stride = (long)e->B * e->N;
+    fa.ring = e->B; fa.base_slot = 0;
+    fa.n_t = nb; fa.n_ch = n_rows;
+    fa.load_scale = scale;
+    fa.out_scale = 1.0 / (double)e->N;                          // fftw_convolver.cpp:520
+    fa.zero_first_half = 1;
+    fa.interleaved = e->ilv;
+    launch_fwd(e->plan, fa, e->stream);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipFree(d_taps));
+    HIP_TRY(hipGetLastError());
+    return BFIR_OK;
+}
+
+// the C channels of one engine
 extern "C" int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const void *const *coeffs,
                                         int n_coeffs, int length, int coeff_blocks, double scale)
 {
@@ -488,54 +558,11 @@ extern "C" int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const 
     e->eng_init[engine_index] = 0;                              // free_coeff(), brutefir.cpp:188
     if (n_coeffs > e->C) n_coeffs = e->C;                       // brutefir.cpp:190-193
     const int nb = std::min(coeff_blocks, e->B);                // run() never looks past B blocks
-    const size_t taps_pad = (size_t)nb * e->L;
-    const size_t cb = cbuf_bytes(e);
     const int gc0 = engine_index * e->C;
-    // zero padded impulse per channel; a block past the end is all zero
-    // (coeff.cpp:315-339), taps are scaled in working precision (fftw_convolver.cpp:491,507)
-    std::vector<char> host((size_t)e->C * taps_pad * e->s, 0);
-    for (int n = 0; n < n_coeffs; n++) {
-        if (!coeffs[n]) return BFIR_ERR_ARG;
-        const size_t cnt = std::min((size_t)length, taps_pad);
-        bool finite = true;
-        if (e->s == 4) {
-            const float *src = (const float *)coeffs[n];
-            const float sc = (float)scale;
-            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite((double)(src[i] * sc));
-        } else {
-            const double *src = (const double *)coeffs[n];
-            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite(src[i] * scale);
-        }
-        if (!finite) {
-            bfir_logf("NaN or Inf value among coefficients.");
-            bfir_logf("Error preprocessing coefficient %d", n);
-            return BFIR_ERR_COEFF;
-        }
-        memcpy(host.data() + (size_t)n * taps_pad * e->s, coeffs[n], cnt * e->s);
-    }
-    void *d_taps = nullptr;
-    HIP_TRY(hipMalloc(&d_taps, host.size()));
-    HIP_TRY(hipMemcpyAsync(d_taps, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemsetAsync((char *)e->H + (size_t)gc0 * e->B * cb, 0, (size_t)e->C * e->B * cb, e->stream));
-    FwdArgs fa;
-    // window of block b = [L zeros | taps b*L .. b*L+L)
-    fa.src = d_taps; fa.src_ch_stride = (long)taps_pad;
-    fa.prev = nullptr; fa.prev_ch_stride = 0;
-    fa.dst = (char *)e->H + (size_t)gc0 * e->B * cb;
-    fa.dst_ch_stride = (long)e->B * e->N;
-    fa.ring = e->B; fa.base_slot = 0;
-    fa.n_t = nb; fa.n_ch = e->C;
-    fa.load_scale = scale;
-    fa.out_scale = 1.0 / (double)e->N;                          // fftw_convolver.cpp:520
-    fa.zero_first_half = 1;
-    fa.interleaved = e->ilv;
-    launch_fwd(e->plan, fa, e->stream);
+    const int rc = load_filters(e, gc0, e->C, coeffs, n_coeffs, length, nb, scale, false);
+    if (rc != BFIR_OK) return rc;
     for (int n = 0; n < e->C; n++) e->nblk[gc0 + n] = nb;
-    HIP_TRY(hipMemcpyAsync(e->d_nblk + gc0, e->nblk.data() + gc0, sizeof(int) * e->C,
-                           hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipFree(d_taps));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(e->d_nblk + gc0, e->nblk.data() + gc0, sizeof(int) * e->C, hipMemcpyHostToDevice));
     e->eng_init[engine_index] = 1;
     return BFIR_OK;
 }
@@ -546,7 +573,7 @@ extern "C" int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, 
     return bfir_engine_set_coeff_at(e, 0, coeffs, n_coeffs, length, coeff_blocks, scale);
 }
 
-// the same for the n_out x n_in filters of a matrix engine: coeffs[o n_in + i], NULL = no path from input i to output o
+// the n_out x n_in filters of a matrix engine: coeffs[o n_in + i], NULL = no path from input i to output o
 extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *coeffs, int length, int coeff_blocks,
                                             double scale)
 {
@@ -558,43 +585,8 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
     e->eng_init[0] = 0;
     const int P = e->Co * e->C;                                 // filters, [o][i]
     const int nb = std::min(coeff_blocks, e->B);
-    const size_t taps_pad = (size_t)nb * e->L;
-    const size_t cb = cbuf_bytes(e);
-    const size_t cnt = std::min((size_t)length, taps_pad);
-    std::vector<char> host((size_t)P * taps_pad * e->s, 0);
-    for (int n = 0; n < P; n++) {
-        if (!coeffs[n]) continue;
-        bool finite = true;
-        if (e->s == 4) {
-            const float *src = (const float *)coeffs[n];
-            const float sc = (float)scale;
-            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite((double)(src[i] * sc));
-        } else {
-            const double *src = (const double *)coeffs[n];
-            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite(src[i] * scale);
-        }
-        if (!finite) {
-            bfir_logf("NaN or Inf value among coefficients.");
-            bfir_logf("Error preprocessing coefficient %d (output %d, input %d)", n, n / e->C, n % e->C);
-            return BFIR_ERR_COEFF;
-        }
-        memcpy(host.data() + (size_t)n * taps_pad * e->s, coeffs[n], cnt * e->s);
-    }
-    void *d_taps = nullptr;
-    HIP_TRY(hipMalloc(&d_taps, host.size()));
-    HIP_TRY(hipMemcpyAsync(d_taps, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
-    HIP_TRY(hipMemsetAsync(e->H, 0, (size_t)P * e->B * cb, e->stream));
-    FwdArgs fa;                                                 // as set_coeff_at, one "channel" per filter
-    fa.src = d_taps; fa.src_ch_stride = (long)taps_pad;
-    fa.prev = nullptr; fa.prev_ch_stride = 0;
-    fa.dst = e->H; fa.dst_ch_stride = (long)e->B * e->N;
-    fa.ring = e->B; fa.base_slot = 0;
-    fa.n_t = nb; fa.n_ch = P;
-    fa.load_scale = scale;
-    fa.out_scale = 1.0 / (double)e->N;
-    fa.zero_first_half = 1;
-    fa.interleaved = e->ilv;
-    launch_fwd(e->plan, fa, e->stream);
+    const int rc = load_filters(e, 0, P, coeffs, P, length, nb, scale, true);
+    if (rc != BFIR_OK) return rc;
     for (int n = 0; n < P; n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
     if (e->pair_cap) {   // same delay-line layout and history bookkeeping on both paths: the next chunk just takes the other
         bool every_input_read = true;
@@ -608,9 +600,6 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
                       every_input_read ? "every input feeds an output" : "an input feeds no output", every_input_read ? "pair" : "direct");
         e->pair = every_input_read; e->direct = !e->pair;
     }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipFree(d_taps));
-    HIP_TRY(hipGetLastError());
     e->eng_init[0] = 1;
     return BFIR_OK;
 }
@@ -719,19 +708,48 @@ extern "C" int bfir_engine_get_profile(bfir_engine *e, int kernel, double *total
 // Queue one chunk of tc blocks (frames frame_off .. of every engine's raw
 // buffer).  `st` is the caller's stream: the input must be ready on it when
 // this is called, and the output is complete on it when its work is.
-//   s_front : stage_in(k) -> fwd(k)                      (k = chunk sequence number)
+//   s_front : front(k)                (k = chunk sequence number)
 //   s_mac   : mac(k)                  waits fwd(k) and inv(k-2) (owner of Yb[k&1])
-//   st      : inv(k) -> stage_out(k)  waits mac(k)
+//   st      : back(k)                 waits mac(k)
 // fwd(k) writes delay-line slots that mac(k-2) may still read (ring = 2*chunk+B),
 // and stage_in(k) rewrites the time buffer fwd(k-2) read; both are ordered by
 // events / stream order.  So fwd(k+1), mac(k) and inv/stage_out(k-1) share the
 // GPU: none of the kernels saturates VALU or HBM alone (load-latency phases,
 // profiles/r01_phase_trace.txt), together they fill each other's gaps.
-// The same chunk on the pair path: no staging kernels, no planar time buffers.
-//   s_front : fwd_pair(k)             raw frames -> delay-line spectra of two channels per transform
-//   s_mac   : mac(k)
-//   st      : inv_pair(k)             product spectra -> raw frames + overflow statistics
-// The MAC of a matrix engine's chunk (both paths): k_mac_matrix over the engine's delay line and filters.
+// Front and back are what the engine's path makes them:
+//   staging : stage_in -> fwd         inv -> stage_out     planar time buffers tin / tout between them
+//   pair    : fwd_pair                inv_pair             raw frames <-> spectra of two channels per transform (pair.hip)
+//   direct  : fwd                     inv                  k_fwd / k_inv in direct mode (kernels.h), one channel per transform
+// Pair and direct have no planar time buffers; their inverse writes the raw frames and the overflow statistics itself.
+enum class Path { Staging, Pair, Direct };
+// a matrix engine may change between pair and direct when its filters are set (bfir_engine_set_coeff_matrix)
+static Path chunk_path(const bfir_engine *e) { return e->pair ? Path::Pair : e->direct ? Path::Direct : Path::Staging; }
+
+// One chunk as its launches see it
+struct Chunk {
+    const void *d_in; long in_stride; void *d_out; long out_stride;   // the caller's frames; engine strides in bytes
+    long frame_off; int tc, block_base;
+    int par;         // chunk parity: which tin / tails set / Yb / events are this chunk's
+    int base_slot;   // delay-line slot of its first block
+    // input_timecbuf bookkeeping: block j of the chunk lands in buffer !(curbuf ^ (j & 1)); this is the last block's
+    int idx_last;
+    void *Y;         // product spectra
+};
+
+// The MAC of a diagonal engine's chunk ...
+static MacArgs mac_args(const bfir_engine *e, int base_slot, void *Y, int tc)
+{
+    MacArgs a;
+    a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
+    a.h = e->H; a.h_ch_stride = (long)e->B * e->N;
+    a.nblk = e->d_nblk;
+    a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
+    a.n_t = tc; a.n_ch = e->GC; a.N = e->N; a.realsize = e->s; a.B = e->B;
+    a.interleaved = e->ilv;   // the pair path implies it
+    return a;
+}
+
+// ... and of a matrix engine's: k_mac_matrix over the engine's delay line and filters.
 static MatArgs matrix_mac_args(const bfir_engine *e, int base_slot, void *Y, int tc)
 {
     MatArgs a;
@@ -754,255 +772,174 @@ static int matrix_chunk_ok(const bfir_engine *e, int tc)
     return BFIR_OK;
 }
 
-static int run_chunk_pair(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride,
-                          long frame_off, int tc, int block_base, hipStream_t st, hipEvent_t input_ready)
+// what the path's kernels ask of the caller's frame buffers (the staging kernels: nothing)
+static int chunk_aligned(const bfir_engine *e, Path p, const Chunk &c)
 {
-    if (((uintptr_t)d_in | (uintptr_t)d_out | (uintptr_t)in_stride | (uintptr_t)out_stride) & (e->pair_tp ? 3 : 7)) {
+    if (p == Path::Pair &&
+        (((uintptr_t)c.d_in | (uintptr_t)c.d_out | (uintptr_t)c.in_stride | (uintptr_t)c.out_stride) & (e->pair_tp ? 3 : 7))) {
         bfir_logf("bfir engine: frame buffers of the float fast path must be 8-byte aligned (4 with an odd channel count).");
         return BFIR_ERR_ARG;
     }
-    const int par = (int)(e->chunk_seq & 1);
-    const int base_slot = (int)(e->blockcounter % (unsigned long long)e->ring);
-    const bool il = e->inline_launch;                                     // one stream, stream order is the only order
-    hipStream_t sf = (e->serial || il) ? st : e->s_front;
-    hipStream_t sm = (e->pipe3 && !il) ? e->s_mac : st;
-    if (input_ready) HIP_TRY(hipStreamWaitEvent(sf, input_ready, 0));
-    if (!il && e->chunk_seq >= 2) HIP_TRY(hipStreamWaitEvent(sf, e->ev_mac[par], 0));   // mac(k-2) is done with the ring
-    // input_timecbuf bookkeeping as in run_chunk: block j of the chunk lands in buffer !(curbuf ^ (j & 1))
-    const int idx_last = 1 ^ e->curbuf ^ ((tc - 1) & 1);
-    {
-        ProfScope ps(e, BFIR_K_FWD, sf);
-        FwdPairArgs a;
-        a.raw = (const float *)d_in; a.eng_stride = in_stride / 4; a.frame_off = frame_off;
-        a.C = e->C; a.n_eng = e->n_eng; a.n_t = tc;
-        a.prev = e->hist_raw[e->curbuf];
-        a.save_last = e->tails[par][idx_last]; a.save_prev = e->tails[par][1 ^ idx_last];
-        a.carry = e->hist_raw[1 ^ idx_last];
-        a.hist_eng_stride = (long)e->L * e->C;
-        a.dst = (float *)e->X; a.dst_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
-        a.scale = (float)e->in_scale;
-        a.tp = e->pair_tp;
-        launch_fwd_pair(e->plan2, a, sf);
-    }
-    e->hist_raw[0] = e->tails[par][0]; e->hist_raw[1] = e->tails[par][1];
-    if (!il) {
-        HIP_TRY(hipEventRecord(e->ev_fwd[par], sf));
-        HIP_TRY(hipStreamWaitEvent(sm, e->ev_fwd[par], 0));
-        if (e->pipe3 && e->chunk_seq >= 2) HIP_TRY(hipStreamWaitEvent(sm, e->ev_inv[par], 0));   // inv(k-2) has read Yb[par]
-    }
-    void *Y = e->Yb[e->pipe3 ? par : 0];
-    {
-        ProfScope ps(e, BFIR_K_MAC, sm);
-        if (e->matrix) {
-            if (launch_mac_matrix(matrix_mac_args(e, base_slot, Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
-        } else {
-        MacArgs a;
-        a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
-        a.h = e->H; a.h_ch_stride = (long)e->B * e->N;
-        a.nblk = e->d_nblk;
-        a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
-        a.n_t = tc; a.n_ch = e->GC; a.N = e->N; a.realsize = e->s; a.B = e->B;
-        a.interleaved = 1;
-        launch_mac(a, sm);
-        }
-    }
-    if (!il) {
-        HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
-        if (e->pipe3) HIP_TRY(hipStreamWaitEvent(st, e->ev_mac[par], 0));
-    }
-    {
-        ProfScope ps(e, BFIR_K_INV, st);
-        InvPairArgs a;
-        a.y = (const float *)Y; a.y_ch_stride = (long)e->chunk * e->N;
-        a.raw = (float *)d_out; a.eng_stride = out_stride / 4; a.frame_off = frame_off;
-        a.C = e->Co; a.n_eng = e->n_eng; a.n_t = tc;
-        a.scale = (float)e->out_scale; a.max = (float)e->of_max;
-        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = block_base; a.bad_host = e->bad_host_cur;
-        a.tp = e->pair_tp;
-        launch_inv_pair(e->plan2, a, st);
-    }
-    if (e->pipe3 && !il) HIP_TRY(hipEventRecord(e->ev_inv[par], st));
-    e->curbuf ^= (tc & 1);
-    e->blockcounter += (unsigned long long)tc;
-    e->chunk_seq += 1;
-    return BFIR_OK;
-}
-
-// The same chunk on the direct path: k_fwd / k_inv of the general path in direct mode (kernels.h).
-//   s_front : fwd(k)   raw frames -> delay-line spectrum, one channel per transform
-//   s_mac   : mac(k)
-//   st      : inv(k)   product spectrum -> raw frames + overflow statistics
-static int run_chunk_direct(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride,
-                            long frame_off, int tc, int block_base, hipStream_t st, hipEvent_t input_ready)
-{
-    if (((uintptr_t)d_in | (uintptr_t)in_stride) % e->in_bytes || ((uintptr_t)d_out | (uintptr_t)out_stride) % e->out_bytes) {
+    if (p == Path::Direct && (((uintptr_t)c.d_in | (uintptr_t)c.in_stride) % e->in_bytes ||
+                              ((uintptr_t)c.d_out | (uintptr_t)c.out_stride) % e->out_bytes)) {
         bfir_logf("bfir engine: frame buffers must be aligned to their sample size.");
         return BFIR_ERR_ARG;
     }
-    const int par = (int)(e->chunk_seq & 1);
-    const int base_slot = (int)(e->blockcounter % (unsigned long long)e->ring);
-    const bool il = e->inline_launch;
-    hipStream_t sf = (e->serial || il) ? st : e->s_front;
-    hipStream_t sm = (e->pipe3 && !il) ? e->s_mac : st;
-    if (input_ready) HIP_TRY(hipStreamWaitEvent(sf, input_ready, 0));
-    if (!il && e->chunk_seq >= 2) HIP_TRY(hipStreamWaitEvent(sf, e->ev_mac[par], 0));   // mac(k-2) is done with the ring
-    const int idx_last = 1 ^ e->curbuf ^ ((tc - 1) & 1);
-    {
-        ProfScope ps(e, BFIR_K_FWD, sf);
-        FwdArgs a;
-        a.src = nullptr; a.src_ch_stride = 0; a.prev = nullptr; a.prev_ch_stride = 0;
-        a.dst = e->X; a.dst_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
-        a.n_t = tc; a.n_ch = e->GC;
-        a.load_scale = 1.0; a.out_scale = e->in_scale; a.zero_first_half = 0; a.interleaved = e->ilv;
-        a.raw_bytes = e->in_bytes; a.raw = d_in; a.raw_eng_stride = in_stride / e->in_bytes; a.frame_off = frame_off; a.C = e->C;
-        a.prev_raw = e->hist_raw[e->curbuf];
-        a.save_last = e->tails[par][idx_last]; a.save_prev = e->tails[par][1 ^ idx_last];
-        a.carry = e->hist_raw[1 ^ idx_last];
-        a.hist_eng_stride = (long)e->L * e->C;
-        launch_fwd(e->plan, a, sf);
-    }
-    e->hist_raw[0] = e->tails[par][0]; e->hist_raw[1] = e->tails[par][1];
-    if (!il) {
-        HIP_TRY(hipEventRecord(e->ev_fwd[par], sf));
-        HIP_TRY(hipStreamWaitEvent(sm, e->ev_fwd[par], 0));
-        if (e->pipe3 && e->chunk_seq >= 2) HIP_TRY(hipStreamWaitEvent(sm, e->ev_inv[par], 0));   // inv(k-2) has read Yb[par]
-    }
-    void *Y = e->Yb[e->pipe3 ? par : 0];
-    {
-        ProfScope ps(e, BFIR_K_MAC, sm);
-        if (e->matrix) {
-            if (launch_mac_matrix(matrix_mac_args(e, base_slot, Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
-        } else {
-        MacArgs a;
-        a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
-        a.h = e->H; a.h_ch_stride = (long)e->B * e->N;
-        a.nblk = e->d_nblk;
-        a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
-        a.n_t = tc; a.n_ch = e->GC; a.N = e->N; a.realsize = e->s; a.B = e->B;
-        a.interleaved = e->ilv;
-        launch_mac(a, sm);
-        }
-    }
-    if (!il) {
-        HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
-        if (e->pipe3) HIP_TRY(hipStreamWaitEvent(st, e->ev_mac[par], 0));
-    }
-    {
-        ProfScope ps(e, BFIR_K_INV, st);
-        InvArgs a;
-        a.src = Y; a.src_ch_stride = (long)e->chunk * e->N;
-        a.dst = nullptr; a.dst_ch_stride = 0;
-        a.n_t = tc; a.n_ch = e->GCo;
-        a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
-        a.raw_bytes = e->out_bytes; a.raw = d_out; a.raw_eng_stride = out_stride / e->out_bytes; a.frame_off = frame_off; a.C = e->Co;
-        a.max = e->of_max; a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = block_base; a.bad_host = e->bad_host_cur;
-        launch_inv(e->plan, a, st);
-    }
-    if (e->pipe3 && !il) HIP_TRY(hipEventRecord(e->ev_inv[par], st));
-    e->curbuf ^= (tc & 1);
-    e->blockcounter += (unsigned long long)tc;
-    e->chunk_seq += 1;
     return BFIR_OK;
 }
 
+// staging path, ahead of the forward transform: raw frames -> planar time buffer tin[par]
+static void queue_stage_in(bfir_engine *e, const Chunk &c, hipStream_t sf)
+{
+    ProfScope ps(e, BFIR_K_STAGE_IN, sf);
+    StageInArgs a;
+    a.raw = c.d_in; a.eng_stride_bytes = c.in_stride; a.frame_off = c.frame_off;
+    a.n_eng = e->n_eng; a.C = e->C; a.raw_bytes = e->in_bytes; a.spacing = e->C; a.fmt = e->in_fmt;
+    a.n_frames = (long)c.tc * e->L;
+    a.dst = e->tin[c.par]; a.dst_ch_stride = (long)e->chunk * e->L; a.dst_off = 0;
+    a.realsize = e->s;
+    launch_stage_in(a, sf);
+}
+
+// The chunk's blocks -> delay-line spectra.  Pair and direct keep the raw frames of the chunk's last two blocks in
+// tails[par] as the time history of the next chunk (the staging path: queue_stage_out).
+static void queue_fwd(bfir_engine *e, Path p, const Chunk &c, hipStream_t sf)
+{
+    ProfScope ps(e, BFIR_K_FWD, sf);
+    if (p == Path::Pair) {
+        FwdPairArgs a;
+        a.raw = (const float *)c.d_in; a.eng_stride = c.in_stride / 4; a.frame_off = c.frame_off;
+        a.C = e->C; a.n_eng = e->n_eng; a.n_t = c.tc;
+        a.prev = e->hist_raw[e->curbuf];
+        a.save_last = e->tails[c.par][c.idx_last]; a.save_prev = e->tails[c.par][1 ^ c.idx_last];
+        a.carry = e->hist_raw[1 ^ c.idx_last];
+        a.hist_eng_stride = (long)e->L * e->C;
+        a.dst = (float *)e->X; a.dst_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = c.base_slot;
+        a.scale = (float)e->in_scale;
+        a.tp = e->pair_tp;
+        launch_fwd_pair(e->plan2, a, sf);
+    } else {
+        FwdArgs a;
+        a.dst = e->X; a.dst_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = c.base_slot;
+        a.n_t = c.tc; a.n_ch = e->GC;
+        a.load_scale = 1.0; a.out_scale = e->in_scale; a.zero_first_half = 0; a.interleaved = e->ilv;
+        if (p == Path::Direct) {
+            a.src = nullptr; a.src_ch_stride = 0; a.prev = nullptr; a.prev_ch_stride = 0;
+            a.raw_bytes = e->in_bytes; a.raw = c.d_in; a.raw_eng_stride = c.in_stride / e->in_bytes; a.frame_off = c.frame_off; a.C = e->C;
+            a.prev_raw = e->hist_raw[e->curbuf];
+            a.save_last = e->tails[c.par][c.idx_last]; a.save_prev = e->tails[c.par][1 ^ c.idx_last];
+            a.carry = e->hist_raw[1 ^ c.idx_last];
+            a.hist_eng_stride = (long)e->L * e->C;
+        } else {
+            a.src = e->tin[c.par]; a.src_ch_stride = (long)e->chunk * e->L;
+            // the block before this chunk, as the reference sees it: first half of
+            // input_timecbuf[n][curbuf] (fftw_convolver.cpp:184 left it there one call earlier)
+            a.prev = e->hist[e->curbuf].ptr; a.prev_ch_stride = e->hist[e->curbuf].ch_stride;
+        }
+        launch_fwd(e->plan, a, sf);
+    }
+    if (p != Path::Staging) { e->hist_raw[0] = e->tails[c.par][0]; e->hist_raw[1] = e->tails[c.par][1]; }
+}
+
+// Product spectra -> the chunk's output blocks: raw frames + overflow statistics (pair, direct) or planar tout (staging).
+// The output side counts by Co / GCo where a matrix engine can get (never the staging path).
+static void queue_inv(bfir_engine *e, Path p, const Chunk &c, hipStream_t st)
+{
+    ProfScope ps(e, BFIR_K_INV, st);
+    if (p == Path::Pair) {
+        InvPairArgs a;
+        a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
+        a.raw = (float *)c.d_out; a.eng_stride = c.out_stride / 4; a.frame_off = c.frame_off;
+        a.C = e->Co; a.n_eng = e->n_eng; a.n_t = c.tc;
+        a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+        a.tp = e->pair_tp;
+        launch_inv_pair(e->plan2, a, st);
+        return;
+    }
+    InvArgs a;
+    a.src = c.Y; a.src_ch_stride = (long)e->chunk * e->N;
+    a.n_t = c.tc;
+    a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
+    if (p == Path::Direct) {
+        a.dst = nullptr; a.dst_ch_stride = 0; a.n_ch = e->GCo;
+        a.raw_bytes = e->out_bytes; a.raw = c.d_out; a.raw_eng_stride = c.out_stride / e->out_bytes; a.frame_off = c.frame_off; a.C = e->Co;
+        a.max = e->of_max; a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+    } else {
+        a.dst = e->tout; a.dst_ch_stride = (long)e->chunk * e->L; a.n_ch = e->GC;
+    }
+    launch_inv(e->plan, a, st);
+}
+
+// staging path, after the inverse transform: planar tout -> raw frames + overflow statistics (+ dither)
+static void queue_stage_out(bfir_engine *e, const Chunk &c, hipStream_t st)
+{
+    const long t_stride = (long)e->chunk * e->L;
+    {
+        ProfScope ps(e, BFIR_K_STAGE_OUT, st);
+        StageOutArgs a;
+        a.raw = c.d_out; a.eng_stride_bytes = c.out_stride; a.frame_off = c.frame_off;
+        a.n_eng = e->n_eng; a.C = e->C; a.raw_bytes = e->out_bytes; a.spacing = e->C; a.fmt = e->out_fmt;
+        a.n_frames = (long)c.tc * e->L;
+        a.src = e->tout; a.src_ch_stride = t_stride;
+        a.realsize = e->s; a.L = e->L; a.max = e->of_max;
+        a.overflow = e->d_of; a.of_shard_stride = e->GC; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+        a.dither_tab = e->d_dither_tab; a.dither_size = e->dither_size; a.dither_state = e->d_dither_state;
+        launch_stage_out(a, st);
+    }
+    // The staging path's time history, once the chunk is queued: only the references move; the samples stay where
+    // stage_in put them (this time buffer is not rewritten before chunk k+2, by which time both references
+    // have moved on).
+    const size_t Ls = (size_t)e->L * e->s;
+    char *tin = (char *)e->tin[c.par];
+    if (c.tc >= 2) { e->hist[1 ^ c.idx_last].ptr = tin + (size_t)(c.tc - 2) * Ls; e->hist[1 ^ c.idx_last].ch_stride = t_stride; }
+    e->hist[c.idx_last].ptr = tin + (size_t)(c.tc - 1) * Ls; e->hist[c.idx_last].ch_stride = t_stride;
+}
+
+// The schedule, the same on every path.  On the latency path (inline_launch) everything is on st and stream order is
+// the only order: no event at all.
 static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride,
                      long frame_off, int tc, int block_base, hipStream_t st, hipEvent_t input_ready)
 {
-    if (e->matrix) {   // pair or direct path (engine_create)
-        const int rc = matrix_chunk_ok(e, tc);
-        if (rc != BFIR_OK) return rc;
-    }
-    if (e->pair) return run_chunk_pair(e, d_in, in_stride, d_out, out_stride, frame_off, tc, block_base, st, input_ready);
-    if (e->direct) return run_chunk_direct(e, d_in, in_stride, d_out, out_stride, frame_off, tc, block_base, st, input_ready);
+    int rc = matrix_chunk_ok(e, tc);
+    if (rc != BFIR_OK) return rc;
+    const Path p = chunk_path(e);
     const int par = (int)(e->chunk_seq & 1);
-    const long t_stride = (long)e->chunk * e->L;
-    void *tin = e->tin[par];
-    const int base_slot = (int)(e->blockcounter % (unsigned long long)e->ring);
-    const bool il = e->inline_launch;                                     // one stream, stream order is the only order
+    Chunk c;
+    c.d_in = d_in; c.in_stride = in_stride; c.d_out = d_out; c.out_stride = out_stride;
+    c.frame_off = frame_off; c.tc = tc; c.block_base = block_base;
+    c.par = par;
+    c.base_slot = (int)(e->blockcounter % (unsigned long long)e->ring);
+    c.idx_last = 1 ^ e->curbuf ^ ((tc - 1) & 1);
+    c.Y = e->Yb[e->pipe3 ? par : 0];
+    rc = chunk_aligned(e, p, c);
+    if (rc != BFIR_OK) return rc;
+    const bool il = e->inline_launch;
     hipStream_t sf = (e->serial || il) ? st : e->s_front;
+    hipStream_t sm = (e->pipe3 && !il) ? e->s_mac : st;
 
     // the front only waits for the input, never for the back of the chunk before
     if (input_ready) HIP_TRY(hipStreamWaitEvent(sf, input_ready, 0));
-    {
-        ProfScope ps(e, BFIR_K_STAGE_IN, sf);
-        StageInArgs a;
-        a.raw = d_in; a.eng_stride_bytes = in_stride; a.frame_off = frame_off;
-        a.n_eng = e->n_eng; a.C = e->C; a.raw_bytes = e->in_bytes; a.spacing = e->C; a.fmt = e->in_fmt;
-        a.n_frames = (long)tc * e->L;
-        a.dst = tin; a.dst_ch_stride = t_stride; a.dst_off = 0;
-        a.realsize = e->s;
-        launch_stage_in(a, sf);
-    }
+    if (p == Path::Staging) queue_stage_in(e, c, sf);   // does not touch the ring: ahead of the wait, it may overlap mac(k-2)
     if (!il && e->chunk_seq >= 2) HIP_TRY(hipStreamWaitEvent(sf, e->ev_mac[par], 0));   // mac(k-2) is done with the ring
-    {
-        ProfScope ps(e, BFIR_K_FWD, sf);
-        FwdArgs a;
-        a.src = tin; a.src_ch_stride = t_stride;
-        // the block before this chunk, as the reference sees it: first half of
-        // input_timecbuf[n][curbuf] (fftw_convolver.cpp:184 left it there one call earlier)
-        a.prev = e->hist[e->curbuf].ptr; a.prev_ch_stride = e->hist[e->curbuf].ch_stride;
-        a.dst = e->X; a.dst_ch_stride = (long)e->ring * e->N;
-        a.ring = e->ring; a.base_slot = base_slot;
-        a.n_t = tc; a.n_ch = e->GC;
-        a.load_scale = 1.0; a.out_scale = e->in_scale;
-        a.zero_first_half = 0;
-        a.interleaved = e->ilv;
-        launch_fwd(e->plan, a, sf);
-    }
-    hipStream_t sm = (e->pipe3 && !il) ? e->s_mac : st;
+    queue_fwd(e, p, c, sf);
     if (!il) {
         HIP_TRY(hipEventRecord(e->ev_fwd[par], sf));
         HIP_TRY(hipStreamWaitEvent(sm, e->ev_fwd[par], 0));
         if (e->pipe3 && e->chunk_seq >= 2) HIP_TRY(hipStreamWaitEvent(sm, e->ev_inv[par], 0));   // inv(k-2) has read Yb[par]
     }
-    void *Y = e->Yb[e->pipe3 ? par : 0];
     {
         ProfScope ps(e, BFIR_K_MAC, sm);
-        MacArgs a;
-        a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
-        a.h = e->H; a.h_ch_stride = (long)e->B * e->N;
-        a.nblk = e->d_nblk;
-        a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
-        a.n_t = tc; a.n_ch = e->GC; a.N = e->N; a.realsize = e->s; a.B = e->B;
-        a.interleaved = e->ilv;
-        launch_mac(a, sm);
+        if (!e->matrix) launch_mac(mac_args(e, c.base_slot, c.Y, tc), sm);
+        else if (launch_mac_matrix(matrix_mac_args(e, c.base_slot, c.Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
     }
     if (!il) {
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
         if (e->pipe3) HIP_TRY(hipStreamWaitEvent(st, e->ev_mac[par], 0));
     }
-    {
-        ProfScope ps(e, BFIR_K_INV, st);
-        InvArgs a;
-        a.src = Y; a.src_ch_stride = (long)e->chunk * e->N;
-        a.dst = e->tout; a.dst_ch_stride = t_stride;
-        a.n_t = tc; a.n_ch = e->GC;
-        a.in_scale = e->out_scale;
-        a.full_output = 0;
-        a.interleaved = e->ilv;
-        launch_inv(e->plan, a, st);
-    }
+    queue_inv(e, p, c, st);
     if (e->pipe3 && !il) HIP_TRY(hipEventRecord(e->ev_inv[par], st));
-    {
-        ProfScope ps(e, BFIR_K_STAGE_OUT, st);
-        StageOutArgs a;
-        a.raw = d_out; a.eng_stride_bytes = out_stride; a.frame_off = frame_off;
-        a.n_eng = e->n_eng; a.C = e->C; a.raw_bytes = e->out_bytes; a.spacing = e->C; a.fmt = e->out_fmt;
-        a.n_frames = (long)tc * e->L;
-        a.src = e->tout; a.src_ch_stride = t_stride;
-        a.realsize = e->s; a.L = e->L; a.max = e->of_max;
-        a.overflow = e->d_of; a.of_shard_stride = e->GC; a.bad_block = e->d_bad; a.block_base = block_base; a.bad_host = e->bad_host_cur;
-        a.dither_tab = e->d_dither_tab; a.dither_size = e->dither_size; a.dither_state = e->d_dither_state;
-        launch_stage_out(a, st);
-    }
-    // input_timecbuf bookkeeping: block j of the chunk lands in buffer
-    // !(curbuf ^ (j & 1)).  Only the references move; the samples stay where
-    // stage_in put them (this time buffer is not rewritten before chunk k+2,
-    // by which time both references have moved on).
-    const size_t Ls = (size_t)e->L * e->s;
-    const int idx_last = 1 ^ e->curbuf ^ ((tc - 1) & 1);
-    if (tc >= 2) { e->hist[1 ^ idx_last].ptr = (char *)tin + (size_t)(tc - 2) * Ls; e->hist[1 ^ idx_last].ch_stride = t_stride; }
-    e->hist[idx_last].ptr = (char *)tin + (size_t)(tc - 1) * Ls; e->hist[idx_last].ch_stride = t_stride;
+    if (p == Path::Staging) queue_stage_out(e, c, st);
     e->curbuf ^= (tc & 1);
     e->blockcounter += (unsigned long long)tc;
     e->chunk_seq += 1;
@@ -1134,12 +1071,8 @@ static int ensure_staging(bfir_engine *e, int min_blocks = 0)
     const size_t bin = (size_t)e->n_eng * hc * e->L * e->C * e->in_bytes;
     const size_t bout = (size_t)e->n_eng * hc * e->L * e->Co * e->out_bytes;
     if (e->stage_bytes_in >= bin && e->stage_bytes_out >= bout) return BFIR_OK;
+    free_staging(e);
     for (int i = 0; i < 2; i++) {
-        if (e->pin_in[i]) (void)hipHostFree(e->pin_in[i]);
-        if (e->pin_out[i]) (void)hipHostFree(e->pin_out[i]);
-        if (e->dev_in[i]) (void)hipFree(e->dev_in[i]);
-        if (e->dev_out[i]) (void)hipFree(e->dev_out[i]);
-        e->pin_in[i] = e->pin_out[i] = e->dev_in[i] = e->dev_out[i] = nullptr;
         HIP_TRY(hipHostMalloc(&e->pin_in[i], bin, hipHostMallocDefault));
         HIP_TRY(hipHostMalloc(&e->pin_out[i], bout, hipHostMallocDefault));
         HIP_TRY(hipMalloc(&e->dev_in[i], bin));
@@ -1163,6 +1096,12 @@ __global__ __launch_bounds__(256) void k_copy16(uint4 *__restrict__ dst, const u
     if (i < n16) dst[i] = src[i];
 }
 
+static void copy16(void *dst, const void *src, size_t bytes, hipStream_t st)
+{
+    const long n16 = (long)(bytes / 16);
+    hipLaunchKernelGGL(k_copy16, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, st, (uint4 *)dst, (const uint4 *)src, n16);
+}
+
 static int run_small(bfir_engine *e, const void *inbuf, void *outbuf, int n_blocks)
 {
     int rc = ensure_chunk(e, n_blocks);
@@ -1184,9 +1123,7 @@ static int run_small(bfir_engine *e, const void *inbuf, void *outbuf, int n_bloc
     const void *src = e->pin_in[0];
     void *dst = e->pin_out[0];
     if (bounce) {
-        const long n16 = (long)(per_in * e->n_eng / 16);
-        hipLaunchKernelGGL(k_copy16, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, e->stream, (uint4 *)e->dev_in[0],
-                           (const uint4 *)e->pin_in[0], n16);
+        copy16(e->dev_in[0], e->pin_in[0], per_in * e->n_eng, e->stream);
         src = e->dev_in[0]; dst = e->dev_out[0];
     }
     e->inline_launch = true;
@@ -1198,11 +1135,7 @@ static int run_small(bfir_engine *e, const void *inbuf, void *outbuf, int n_bloc
     e->bad_host_cur = nullptr;
     e->inline_launch = false;
     if (rc != BFIR_OK) return rc;
-    if (bounce) {
-        const long n16 = (long)(per_out * e->n_eng / 16);
-        hipLaunchKernelGGL(k_copy16, dim3((unsigned)((n16 + 255) / 256)), dim3(256), 0, e->stream, (uint4 *)e->pin_out[0],
-                           (const uint4 *)e->dev_out[0], n16);
-    }
+    if (bounce) copy16(e->pin_out[0], e->dev_out[0], per_out * e->n_eng, e->stream);
     // no copy of the verdict: the kernels flagged bad blocks in pinned host memory themselves (one 4-byte copy was a blit
     // kernel of 3.5 us plus its launch, a tenth of the call)
     HIP_TRY(hipStreamSynchronize(e->stream));

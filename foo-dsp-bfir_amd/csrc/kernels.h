@@ -26,6 +26,16 @@ __device__ __forceinline__ DevOverflow *of_shard(DevOverflow *base, long shard_s
     return base + (long)(blockIdx.x & (BFIR_OF_SHARDS - 1)) * shard_stride;
 }
 
+// XCD-aware, bijective block -> work item remap of a launch of W workgroups: each XCD (blocks b, b+8, ...) gets
+// one contiguous range of work items, so neighbouring items -- k_mac: ordered (channel, bin tile) major / time tile
+// minor -- meet in one L2: it holds a slice of H for the whole launch while consecutive time tiles re-use each
+// other's spectra; in the FFT kernels the channels of a block share the cache lines of their frames.
+__device__ __forceinline__ int xcd_work_item(int b, int W)
+{
+    const int xcd = b & 7, qn = W >> 3, rn = W & 7;
+    return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+}
+
 // brutefir.cpp:316-321's verdict: block t of this launch has a non-finite sample 0.  The first such block of a run is kept
 // by atomicMin in HBM; the latency path (a handful of blocks per call, run_small) also gets one flag per block in pinned
 // host memory -- plain, idempotent stores, visible with the stream's end -- so that no copy has to follow the kernels.

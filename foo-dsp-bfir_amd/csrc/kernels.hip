@@ -191,8 +191,7 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_fwd(FwdArgs a,
     // direct mode: the channels of a block share input cache lines -> give every XCD a contiguous range
     int wi = blockIdx.x;
     if constexpr (DIRECT) {
-        const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-        wi = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+        wi = xcd_work_item(blockIdx.x, gridDim.x);
     }
     const int ncw = a.n_ch / CPW;
     const int t = wi / ncw, gc = (wi - t * ncw) * CPW + half;
@@ -440,8 +439,7 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT, 2) void k_fwd_run(FwdArgs a, con
     __shared__ __attribute__((aligned(16))) V2 ldsb[F::LDSB_ELEMS];
     const int tid = threadIdx.x;
     // (run, channel): the channels of a run share input cache lines -> neighbours on one XCD
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int wi = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    const int wi = xcd_work_item(blockIdx.x, gridDim.x);
     const int r = wi / a.n_ch, gc = wi - r * a.n_ch;
     const int t0 = r * run_len, t1 = min(a.n_t, t0 + run_len);
     if (t0 >= t1) return;
@@ -691,8 +689,7 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT * CPW) void k_inv(InvArgs a,
     V2 *lds = lds_all[half];
     int wi = blockIdx.x;
     if constexpr (DIRECT) {       // the channels of a block write the same cache lines: one XCD
-        const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-        wi = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+        wi = xcd_work_item(blockIdx.x, gridDim.x);
     }
     const int ncw = a.n_ch / CPW;
     const int t = wi / ncw, gc = (wi - t * ncw) * CPW + half;
@@ -844,8 +841,7 @@ __global__ __launch_bounds__(FftCfg<LOG2M>::NT, 2) void k_inv_run(InvArgs a, con
     __shared__ Bits red_max[NT / 64 > 0 ? NT / 64 : 1];
     __shared__ unsigned int red_cnt[NT / 64 > 0 ? NT / 64 : 1];
     const int tid = threadIdx.x;
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int wi = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    const int wi = xcd_work_item(blockIdx.x, gridDim.x);
     const int r = wi / a.n_ch, gc = wi - r * a.n_ch;
     const int t0 = r * run_len, t1 = min(a.n_t, t0 + run_len);
     if (t0 >= t1) return;
@@ -1124,12 +1120,8 @@ __global__ __launch_bounds__(256, WPE) void k_mac(MacArgs a, int nbt, int nTT, i
 {
     static_assert(D >= 1 && TT % D == 0, "prefetch depth must divide the time tile");
     using V4 = typename Vec4<T>::type;
-    // XCD-aware, bijective block -> work remap: each XCD (blocks b, b+8, ...)
-    // gets one contiguous range of work items, ordered (channel, bin tile)
-    // major / time tile minor, so its L2 holds a slice of H for the whole
-    // launch while consecutive time tiles re-use each other's spectra.
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    // work items (kernels.h, xcd_work_item): (channel, bin tile) major, time tile minor
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int s = w / nTT, tt = w - s * nTT;
     const int gc = s / nbt, bt = s - gc * nbt;
     const int g = bt * blockDim.x + threadIdx.x;
@@ -1264,8 +1256,7 @@ __global__ __launch_bounds__(256, 2) void k_mac_lds(MacArgs a, int nbt, int nTQ)
     __shared__ __attribute__((aligned(16))) v4f s_ring[32][2][64];
     __shared__ __attribute__((aligned(16))) v4f s_h[2][2][64];
     static_assert(8 % D == 0, "prefetch depth must divide the unroll");
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int s = w / nTQ, tq = w - s * nTQ;
     const int gc = s / nbt, bt = s - gc * nbt;
     const int lane = threadIdx.x & 63;
@@ -1383,8 +1374,7 @@ __global__ __launch_bounds__(256, 2) void k_mac_lds_d(MacArgs a, int nbt, int nT
     __shared__ __attribute__((aligned(32))) v4d s_ring[16][2][64];
     __shared__ __attribute__((aligned(32))) v4d s_h[2][2][64];
     static_assert(4 % D == 0, "prefetch depth must divide the unroll");
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int s = w / nTQ, tq = w - s * nTQ;
     const int gc = s / nbt, bt = s - gc * nbt;
     const int lane = threadIdx.x & 63;
@@ -1527,8 +1517,7 @@ __global__ __launch_bounds__(256, 2) void k_mac_lds_d2g(MacArgs a, int nbt, int 
 {
     __shared__ __attribute__((aligned(16))) v2d s_ring[32][2][64];
     __shared__ __attribute__((aligned(16))) v2d s_h[2 * G][2][64];
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int s = w / nTQ, tq = w - s * nTQ;
     const int gc = s / nbt, bt = s - gc * nbt;
     const int lane = threadIdx.x & 63;
@@ -1714,9 +1703,8 @@ __global__ __launch_bounds__(256, ACC ? 2 : 3) void k_mac_stream(MacArgs a, int 
         }
         return;
     }
-    // XCD-aware bijective remap (see k_mac): (channel, bin column) major, time range minor
-    const int W = gridDim.x - n_dc, b = blockIdx.x - n_dc, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    // XCD-aware bijective remap (kernels.h): (channel, bin column) major, time range minor
+    const int w = xcd_work_item(blockIdx.x - n_dc, gridDim.x - n_dc);
     const int s = w / nR, r = w - s * nR;
     const int gc = s / ncol, col = s - gc * ncol;
     const unsigned k = col * 256 + threadIdx.x;          // bin: (re, im) pair k of every spectrum

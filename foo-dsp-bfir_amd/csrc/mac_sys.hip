@@ -237,8 +237,7 @@ __global__ __launch_bounds__(256, (sys_min_waves<T, PL, D>())) void k_mac_sys(Ma
         return;
     }
     // XCD-aware bijective remap: (channel, bin column) major, run minor -- the runs of one column meet in one L2
-    const int Wg = gridDim.x - n_dc, b = blockIdx.x - n_dc, xcd = b & 7, qn = Wg >> 3, rn = Wg & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    const int w = xcd_work_item(blockIdx.x - n_dc, gridDim.x - n_dc);
     const int s = w / nR, r = w - s * nR;
     const int gc = s / ncol, col = s - gc * ncol;
     const int stage = SysLanes<S>::stage(threadIdx.x);

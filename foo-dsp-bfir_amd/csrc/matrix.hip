@@ -121,8 +121,7 @@ __device__ __forceinline__ void mat_tile(const MatArgs &a, int o0, int t0, int o
 template <typename T, bool ILV, int NO, int TT>
 __global__ __launch_bounds__(256, 4) void k_mac_matrix(MatArgs a, int nbt, int nTT)
 {
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    const int w = (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int bt = w / nTT, tt = w - bt * nTT;
     const int k = bt * blockDim.x + threadIdx.x;                 // bin
     const int N2 = a.N / 2;

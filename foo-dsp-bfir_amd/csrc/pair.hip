@@ -30,14 +30,6 @@ namespace bfir {
 
 namespace {
 
-// XCD-aware bijective remap: blocks b, b+8, ... run on one XCD; give every XCD one contiguous
-// range of work items so the channel pairs of a block (which share input cache lines) meet in one L2.
-__device__ __forceinline__ int xcd_remap()
-{
-    const int W = gridDim.x, b = blockIdx.x, xcd = b & 7, qn = W >> 3, rn = W & 7;
-    return (xcd < rn ? xcd * (qn + 1) : rn * (qn + 1) + (xcd - rn) * qn) + (b >> 3);
-}
-
 // ---- persistent forward kernel -------------------------------------------------------------------
 // A forward kernel that transforms one block per workgroup waits for memory, not arithmetic
 // (profiles/r02_alias_and_bottleneck_experiments.txt: 0.235 ms of VALU + LDS under 0.33 ms of exposed
@@ -195,7 +187,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, 4) void k_fwd_pair_ps(FwdPairArg
     __shared__ __attribute__((aligned(16))) float2 ldsb[F::LDSB_ELEMS];
 
     const int tid = threadIdx.x;
-    const int w = xcd_remap();
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int half_c = a.C / 2, pairs = a.n_eng * half_c;
     const int rr = w / pairs, pp = w - rr * pairs;                       // run, pair: the pairs of a run share an XCD
     // The two-for-one split halves every sum (Xa = (Z[k] + conj Z[N-k]) / 2 ...): the half goes into the input
@@ -355,7 +347,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, 4) void k_fwd_tp_ps(FwdPairArgs 
     __shared__ __attribute__((aligned(16))) float2 ldsb[F::LDSB_ELEMS];
 
     const int tid = threadIdx.x;
-    const int w = xcd_remap();
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int C = a.C, units = a.n_eng * C;
     const int rr = w / units, pp = w - rr * units;                       // run, channel: the channels of a run share an XCD
     const int g = pp / C, c = pp - g * C;
@@ -512,7 +504,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
     __shared__ unsigned int red_max[NT / 64 > 0 ? NT / 64 : 1][2], red_cnt[NT / 64 > 0 ? NT / 64 : 1][2];
 
     const int tid = threadIdx.x;
-    const int w = xcd_remap();
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int half_c = a.C / 2, pairs = a.n_eng * half_c;
     const int rr = w / pairs, pp = w - rr * pairs;
     const int g = pp / half_c, cp = pp - g * half_c;
@@ -664,7 +656,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
     __shared__ unsigned int red_max[NT / 64 > 0 ? NT / 64 : 1][2], red_cnt[NT / 64 > 0 ? NT / 64 : 1][2];
 
     const int tid = threadIdx.x;
-    const int w = xcd_remap();
+    const int w = xcd_work_item(blockIdx.x, gridDim.x);
     const int C = a.C, units = a.n_eng * C;
     const int rr = w / units, pp = w - rr * units;
     const int g = pp / C, c = pp - g * C;
