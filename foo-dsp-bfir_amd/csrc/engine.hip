@@ -149,6 +149,22 @@ struct bfir_engine {
     // tests) keep the staging kernels.
     bool direct = false;
     FftPlan plan2;                         // transform of 2L complex points
+    // Crossfaded coefficient change (bfir_engine_set_coeff_fade; fftw_convolver.cpp:275-321 over fade_len blocks): the
+    // second filter set H2 (as H) with its partition counts, loaded by the call; the fade is blocks fade_pos .. fade_len-1
+    // of the next fade_len blocks the engine processes (fade_len = 0: none).  run_blocks cuts the chunks at its end, so a
+    // chunk is all fade or all plain; a fade chunk runs the MAC twice -- (H, counts) into Y, (H2, counts2) into Yf -- and
+    // the fade back end (queue_inv_fade) instead of queue_inv.  With the last fade block queued the sets swap.
+    void *H2 = nullptr;
+    int *d_nblk2 = nullptr;
+    std::vector<int> nblk2;
+    int fade_len = 0, fade_pos = 0;
+    float fade_f = 0.f; double fade_d = 0.0;   // 1 / (real)(fade_len L - 1) as the reference computes it (:298, :308)
+    bool fade_fused = false;               // k_inv_fade serves this engine (fp32 pairs, FLOAT_LE out, a plan of 2L points)
+    bool pair_new = false;                 // matrix engines: the path the NEW set alone asks for (after the fade)
+    void *Yf[2] = {nullptr, nullptr};      // products with H2: [GCo][yf_blocks][N], one per chunk parity like Yb
+    int yf_blocks = 0;
+    void *ft[2] = {nullptr, nullptr};      // general back end: planar y_old / y_new, [GCo][ft_blocks][L] each
+    int ft_blocks = 0;
     float *tails[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     const float *hist_raw[2] = {nullptr, nullptr};
     // HP-TPDF dither (integer output + apply_dither; dither.hip): the reference instance's random table
@@ -466,7 +482,8 @@ extern "C" void bfir_engine_destroy(bfir_engine *e)
     fft_plan_destroy(&e->plan);
     fft_plan_destroy(&e->plan2);
     for (int st = 0; st < 2; st++) for (int i = 0; i < 2; i++) if (e->tails[st][i]) (void)hipFree(e->tails[st][i]);
-    void *bufs[] = {e->H, e->saved[0], e->saved[1], e->d_nblk, e->d_of, e->d_bad, e->d_dither_tab, e->d_dither_state};
+    void *bufs[] = {e->H, e->saved[0], e->saved[1], e->d_nblk, e->d_of, e->d_bad, e->d_dither_tab, e->d_dither_state,
+                    e->H2, e->d_nblk2, e->Yf[0], e->Yf[1], e->ft[0], e->ft[1]};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (auto &sp : e->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -494,8 +511,9 @@ extern "C" int bfir_engine_set_chunk(bfir_engine *e, int blocks_per_launch)
 
 // coeff::preprocess_coeff + convolver_coeffs2cbuf for n_rows filters, rows row0 .. of H: coeffs[n] (n < n_coeffs <= n_rows)
 // goes to row row0 + n, nb partitions each.  A NULL entry is an error (null_ok = false) or an all-zero filter, as are the
-// rows past n_coeffs.  Nothing is uploaded before every filter has passed the finite check.
-static int load_filters(bfir_engine *e, int row0, int n_rows, const void *const *coeffs, int n_coeffs, int length, int nb,
+// rows past n_coeffs.  Nothing is uploaded before every filter has passed the finite check.  Hdst: the filter buffer that
+// takes them, H or (a fade's second set) H2.
+static int load_filters(bfir_engine *e, void *Hdst, int row0, int n_rows, const void *const *coeffs, int n_coeffs, int length, int nb,
                         double scale, bool null_ok)
 {
     const size_t taps_pad = (size_t)nb * e->L;
@@ -524,7 +542,7 @@ static int load_filters(bfir_engine *e, int row0, int n_rows, const void *const 
         memcpy(host.data() + (size_t)n * taps_pad * e->s, coeffs[n], cnt * e->s);
     }
     void *d_taps = nullptr;
-    void *rows = (char *)e->H + (size_t)row0 * e->B * cb;
+    void *rows = (char *)Hdst + (size_t)row0 * e->B * cb;
     HIP_TRY(hipMalloc(&d_taps, host.size()));
     HIP_TRY(hipMemcpyAsync(d_taps, host.data(), host.size(), hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipMemsetAsync(rows, 0, (size_t)n_rows * e->B * cb, e->stream));
@@ -555,11 +573,12 @@ extern "C" int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const 
     if (e->matrix) return BFIR_ERR_UNSUPPORTED;                 // bfir_engine_set_coeff_matrix
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
+    e->fade_len = e->fade_pos = 0;                              // a plain change during a fade cancels it: a hard cut, as ever
     e->eng_init[engine_index] = 0;                              // free_coeff(), brutefir.cpp:188
     if (n_coeffs > e->C) n_coeffs = e->C;                       // brutefir.cpp:190-193
     const int nb = std::min(coeff_blocks, e->B);                // run() never looks past B blocks
     const int gc0 = engine_index * e->C;
-    const int rc = load_filters(e, gc0, e->C, coeffs, n_coeffs, length, nb, scale, false);
+    const int rc = load_filters(e, e->H, gc0, e->C, coeffs, n_coeffs, length, nb, scale, false);
     if (rc != BFIR_OK) return rc;
     for (int n = 0; n < e->C; n++) e->nblk[gc0 + n] = nb;
     HIP_TRY(hipMemcpy(e->d_nblk + gc0, e->nblk.data() + gc0, sizeof(int) * e->C, hipMemcpyHostToDevice));
@@ -573,6 +592,27 @@ extern "C" int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, 
     return bfir_engine_set_coeff_at(e, 0, coeffs, n_coeffs, length, coeff_blocks, scale);
 }
 
+// does every input of a matrix engine feed some output under these partition counts ([o C + i])?
+static bool every_input_read(const bfir_engine *e, const std::vector<int> &nblk)
+{
+    for (int i = 0; i < e->C; i++) {
+        bool read = false;
+        for (int o = 0; o < e->Co; o++) read = read || nblk[o * e->C + i] > 0;
+        if (!read) return false;
+    }
+    return true;
+}
+
+// a pair-capable matrix engine between its two paths: same delay-line layout and history bookkeeping on both, the next
+// chunk just takes the other
+static void matrix_take_path(bfir_engine *e, bool pair)
+{
+    if (e->pair != pair)
+        bfir_logf("bfir matrix engine: %s: path=%s from the next block on.",
+                  pair ? "every input feeds an output" : "an input feeds no output", pair ? "pair" : "direct");
+    e->pair = pair; e->direct = !pair;
+}
+
 // the n_out x n_in filters of a matrix engine: coeffs[o n_in + i], NULL = no path from input i to output o
 extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *coeffs, int length, int coeff_blocks,
                                             double scale)
@@ -582,26 +622,93 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
     if (!coeffs || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
+    e->fade_len = e->fade_pos = 0;                              // a plain change during a fade cancels it
     e->eng_init[0] = 0;
     const int P = e->Co * e->C;                                 // filters, [o][i]
     const int nb = std::min(coeff_blocks, e->B);
-    const int rc = load_filters(e, 0, P, coeffs, P, length, nb, scale, true);
+    const int rc = load_filters(e, e->H, 0, P, coeffs, P, length, nb, scale, true);
     if (rc != BFIR_OK) return rc;
     for (int n = 0; n < P; n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
-    if (e->pair_cap) {   // same delay-line layout and history bookkeeping on both paths: the next chunk just takes the other
-        bool every_input_read = true;
-        for (int i = 0; i < e->C; i++) {
-            bool read = false;
-            for (int o = 0; o < e->Co; o++) read = read || e->nblk[o * e->C + i] > 0;
-            every_input_read = every_input_read && read;
-        }
-        if (e->pair != every_input_read)
-            bfir_logf("bfir matrix engine: %s: path=%s from the next block on.",
-                      every_input_read ? "every input feeds an output" : "an input feeds no output", every_input_read ? "pair" : "direct");
-        e->pair = every_input_read; e->direct = !e->pair;
-    }
+    if (e->pair_cap) matrix_take_path(e, every_input_read(e, e->nblk));
     e->eng_init[0] = 1;
     return BFIR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// crossfaded coefficient change: the engine-level form of fftw_convolver::convolver_crossfade_inplace
+// (brutefir/fftw_convolver.cpp:275-321), stretched over fade_blocks blocks
+// ---------------------------------------------------------------------------
+// the old set gives way to the new one: H2 becomes H (the buffer that was H is the next fade's H2)
+static void fade_swap_sets(bfir_engine *e)
+{
+    std::swap(e->H, e->H2);
+    std::swap(e->d_nblk, e->d_nblk2);
+    std::swap(e->nblk, e->nblk2);
+    e->fade_len = e->fade_pos = 0;
+    if (e->matrix && e->pair_cap) matrix_take_path(e, e->pair_new);
+}
+
+// rows: the filters of the call (C of a diagonal engine, Co x C of a matrix engine)
+static int set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, int coeff_blocks, double scale,
+                          int fade_blocks)
+{
+    if (e->n_eng > 1 || e->d_dither_tab) return BFIR_ERR_UNSUPPORTED;   // batches; HP-TPDF dither (a recursion over the output samples)
+    if (!coeffs || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
+    // m = 0 .. K L - 1 must be exact as a float (:302 multiplies by (float)n)
+    if (fade_blocks < 1 || (long long)fade_blocks * e->L > (1ll << 24)) return BFIR_ERR_ARG;
+    if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
+    HIP_TRY(hipSetDevice(e->device));
+    // queued work may still read what was H before the last fade's swap: H2 is written only when the device is idle
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t cb = cbuf_bytes(e);
+    const int n_rows = e->matrix ? e->Co * e->C : e->C;
+    if (!e->H2) {
+        HIP_TRY(hipMalloc(&e->H2, (size_t)n_rows * e->B * cb));
+        HIP_TRY(hipMalloc((void **)&e->d_nblk2, sizeof(int) * e->GC));
+    }
+    e->fade_fused = e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L);
+    if (e->fade_fused && !e->plan2.tw && fft_plan_create(&e->plan2, 2 * e->L, 4) != 0) return BFIR_ERR_HIP;   // direct / staging engines have none yet
+    const int nb = std::min(coeff_blocks, e->B);
+    if (!e->matrix && n_coeffs > e->C) n_coeffs = e->C;
+    // a NaN / Inf tap is refused before anything is uploaded: the engine keeps running the old set
+    const int rc = load_filters(e, e->H2, 0, n_rows, coeffs, e->matrix ? n_rows : n_coeffs, length, nb, scale, e->matrix);
+    if (rc != BFIR_OK) return rc;
+    e->nblk2.assign(e->nblk.size(), 0);
+    for (int n = 0; n < n_rows; n++) e->nblk2[n] = (e->matrix && !coeffs[n]) ? 0 : nb;
+    if (!e->matrix) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
+    if (e->matrix && e->pair_cap) {
+        // no channel pairs around an unread input, per set: the fade's forward transforms take the pair path only if every
+        // input is read under BOTH sets; after the fade the new set decides
+        e->pair_new = every_input_read(e, e->nblk2);
+        matrix_take_path(e, e->pair_new && every_input_read(e, e->nblk));
+    }
+    e->fade_f = (float)(1.0 / (double)(float)(fade_blocks * e->L - 1));
+    e->fade_d = 1.0 / (double)(fade_blocks * e->L - 1);
+    e->fade_len = fade_blocks; e->fade_pos = 0;
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length,
+                                          int coeff_blocks, double scale, int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (e->matrix) return BFIR_ERR_UNSUPPORTED;                 // bfir_engine_set_coeff_matrix_fade
+    if (n_coeffs < 0) return BFIR_ERR_ARG;
+    return set_coeff_fade(e, coeffs, n_coeffs, length, coeff_blocks, scale, fade_blocks);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_fade(bfir_engine *e, const void *const *coeffs, int length, int coeff_blocks,
+                                                 double scale, int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->matrix) return BFIR_ERR_UNSUPPORTED;
+    return set_coeff_fade(e, coeffs, 0, length, coeff_blocks, scale, fade_blocks);
+}
+
+extern "C" int bfir_engine_fade_remaining(const bfir_engine *e)
+{
+    if (!e) return BFIR_ERR_ARG;
+    return e->fade_len > 0 ? e->fade_len - e->fade_pos : 0;
 }
 
 // partition spectrum `block` of filter `f` (H row) to host, in the reference's grouped layout
@@ -734,15 +841,17 @@ struct Chunk {
     // input_timecbuf bookkeeping: block j of the chunk lands in buffer !(curbuf ^ (j & 1)); this is the last block's
     int idx_last;
     void *Y;         // product spectra
+    // a fade chunk (all of its blocks fade): the products with the new set, Yf's own channel stride, m of its first sample
+    bool fade = false; void *Y2 = nullptr; long y2_ch_stride = 0; int m0 = 0;
 };
 
-// The MAC of a diagonal engine's chunk ...
-static MacArgs mac_args(const bfir_engine *e, int base_slot, void *Y, int tc)
+// The MAC of a diagonal engine's chunk (second = the fade's new set: H2 and its counts) ...
+static MacArgs mac_args(const bfir_engine *e, int base_slot, void *Y, int tc, bool second = false)
 {
     MacArgs a;
     a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
-    a.h = e->H; a.h_ch_stride = (long)e->B * e->N;
-    a.nblk = e->d_nblk;
+    a.h = second ? e->H2 : e->H; a.h_ch_stride = (long)e->B * e->N;
+    a.nblk = second ? e->d_nblk2 : e->d_nblk;
     a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
     a.n_t = tc; a.n_ch = e->GC; a.N = e->N; a.realsize = e->s; a.B = e->B;
     a.interleaved = e->ilv;   // the pair path implies it
@@ -750,12 +859,13 @@ static MacArgs mac_args(const bfir_engine *e, int base_slot, void *Y, int tc)
 }
 
 // ... and of a matrix engine's: k_mac_matrix over the engine's delay line and filters.
-static MatArgs matrix_mac_args(const bfir_engine *e, int base_slot, void *Y, int tc)
+static MatArgs matrix_mac_args(const bfir_engine *e, int base_slot, void *Y, int tc, bool second = false)
 {
+    const std::vector<int> &nblk = second ? e->nblk2 : e->nblk;
     MatArgs a;
     a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
-    a.h = e->H; a.h_pair_stride = (long)e->B * e->N;
-    for (int j = 0; j < BFIR_MAT_MAX * BFIR_MAT_MAX; j++) a.nblk[j] = j < (int)e->nblk.size() ? e->nblk[j] : 0;
+    a.h = second ? e->H2 : e->H; a.h_pair_stride = (long)e->B * e->N;
+    for (int j = 0; j < BFIR_MAT_MAX * BFIR_MAT_MAX; j++) a.nblk[j] = j < (int)nblk.size() ? nblk[j] : 0;
     a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
     a.n_t = tc; a.n_in = e->C; a.n_out = e->Co; a.N = e->N; a.realsize = e->s;
     a.interleaved = e->ilv;
@@ -872,24 +982,64 @@ static void queue_inv(bfir_engine *e, Path p, const Chunk &c, hipStream_t st)
 }
 
 // staging path, after the inverse transform: planar tout -> raw frames + overflow statistics (+ dither)
-static void queue_stage_out(bfir_engine *e, const Chunk &c, hipStream_t st)
+// `src`: planar [GCo][..] with src_ch_stride reals per channel -- tout, or a fade's blended scratch (any path: Co channels)
+static void queue_stage_out(bfir_engine *e, const Chunk &c, const void *src, long src_ch_stride, hipStream_t st)
+{
+    ProfScope ps(e, BFIR_K_STAGE_OUT, st);
+    StageOutArgs a;
+    a.raw = c.d_out; a.eng_stride_bytes = c.out_stride; a.frame_off = c.frame_off;
+    a.n_eng = e->n_eng; a.C = e->Co; a.raw_bytes = e->out_bytes; a.spacing = e->Co; a.fmt = e->out_fmt;
+    a.n_frames = (long)c.tc * e->L;
+    a.src = src; a.src_ch_stride = src_ch_stride;
+    a.realsize = e->s; a.L = e->L; a.max = e->of_max;
+    a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+    a.dither_tab = e->d_dither_tab; a.dither_size = e->dither_size; a.dither_state = e->d_dither_state;
+    launch_stage_out(a, st);
+}
+
+// The fade back end of a chunk whose blocks all fade: Y (old set) and Y2 (new set) -> blended output frames.
+static void queue_inv_fade(bfir_engine *e, const Chunk &c, hipStream_t st)
+{
+    if (e->fade_fused) {   // one inverse per output channel and block, blend, statistics and frame store in one kernel
+        ProfScope ps(e, BFIR_K_INV, st);
+        FadeInvArgs a;
+        a.y_old = (const float *)c.Y; a.y_old_ch_stride = (long)e->chunk * e->N;
+        a.y_new = (const float *)c.Y2; a.y_new_ch_stride = c.y2_ch_stride;
+        a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
+        a.n_ch = e->Co; a.n_t = c.tc;
+        a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+        a.f = e->fade_f; a.m0 = c.m0;
+        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+        launch_inv_fade(e->plan2, a, st);
+        return;
+    }
+    // the general form: two planar inverses into the fade's own scratch, the blend, then the staging path's output kernel
+    const long t_stride = (long)e->ft_blocks * e->L;
+    {
+        ProfScope ps(e, BFIR_K_INV, st);
+        InvArgs a;
+        a.n_t = c.tc; a.n_ch = e->GCo;
+        a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
+        a.dst_ch_stride = t_stride;
+        a.src = c.Y; a.src_ch_stride = (long)e->chunk * e->N; a.dst = e->ft[0];
+        launch_inv(e->plan, a, st);
+        a.src = c.Y2; a.src_ch_stride = c.y2_ch_stride; a.dst = e->ft[1];
+        launch_inv(e->plan, a, st);
+        FadeBlendArgs b;
+        b.y_old = e->ft[0]; b.y_new = e->ft[1]; b.ch_stride = t_stride;
+        b.n_ch = e->GCo; b.n = (long)c.tc * e->L;
+        b.f = e->s == 4 ? (double)e->fade_f : e->fade_d; b.m0 = c.m0; b.realsize = e->s;
+        launch_fade_blend(b, st);
+    }
+    queue_stage_out(e, c, e->ft[0], t_stride, st);
+}
+
+// The staging path's time history, once the chunk is queued (plain or fading: its front is the same): only the
+// references move; the samples stay where stage_in put them (this time buffer is not rewritten before chunk k+2, by
+// which time both references have moved on).
+static void move_staging_history(bfir_engine *e, const Chunk &c)
 {
     const long t_stride = (long)e->chunk * e->L;
-    {
-        ProfScope ps(e, BFIR_K_STAGE_OUT, st);
-        StageOutArgs a;
-        a.raw = c.d_out; a.eng_stride_bytes = c.out_stride; a.frame_off = c.frame_off;
-        a.n_eng = e->n_eng; a.C = e->C; a.raw_bytes = e->out_bytes; a.spacing = e->C; a.fmt = e->out_fmt;
-        a.n_frames = (long)c.tc * e->L;
-        a.src = e->tout; a.src_ch_stride = t_stride;
-        a.realsize = e->s; a.L = e->L; a.max = e->of_max;
-        a.overflow = e->d_of; a.of_shard_stride = e->GC; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
-        a.dither_tab = e->d_dither_tab; a.dither_size = e->dither_size; a.dither_state = e->d_dither_state;
-        launch_stage_out(a, st);
-    }
-    // The staging path's time history, once the chunk is queued: only the references move; the samples stay where
-    // stage_in put them (this time buffer is not rewritten before chunk k+2, by which time both references
-    // have moved on).
     const size_t Ls = (size_t)e->L * e->s;
     char *tin = (char *)e->tin[c.par];
     if (c.tc >= 2) { e->hist[1 ^ c.idx_last].ptr = tin + (size_t)(c.tc - 2) * Ls; e->hist[1 ^ c.idx_last].ch_stride = t_stride; }
@@ -912,8 +1062,15 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     c.base_slot = (int)(e->blockcounter % (unsigned long long)e->ring);
     c.idx_last = 1 ^ e->curbuf ^ ((tc - 1) & 1);
     c.Y = e->Yb[e->pipe3 ? par : 0];
+    // run_blocks cut the chunk so that it is all fade or all plain
+    c.fade = e->fade_len > 0;
+    if (c.fade) { c.Y2 = e->Yf[e->pipe3 ? par : 0]; c.y2_ch_stride = (long)e->yf_blocks * e->N; c.m0 = e->fade_pos * e->L; }
     rc = chunk_aligned(e, p, c);
     if (rc != BFIR_OK) return rc;
+    if (c.fade && e->fade_fused && (((uintptr_t)d_out | (uintptr_t)out_stride) & 3)) {
+        bfir_logf("bfir engine: frame buffers must be aligned to their sample size.");
+        return BFIR_ERR_ARG;
+    }
     const bool il = e->inline_launch;
     hipStream_t sf = (e->serial || il) ? st : e->s_front;
     hipStream_t sm = (e->pipe3 && !il) ? e->s_mac : st;
@@ -932,17 +1089,74 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
         ProfScope ps(e, BFIR_K_MAC, sm);
         if (!e->matrix) launch_mac(mac_args(e, c.base_slot, c.Y, tc), sm);
         else if (launch_mac_matrix(matrix_mac_args(e, c.base_slot, c.Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
+        if (c.fade) {   // the same delay line through the same kernels with the new set, behind the first
+            if (!e->matrix) { MacArgs a = mac_args(e, c.base_slot, c.Y2, tc, true); a.y_ch_stride = c.y2_ch_stride; launch_mac(a, sm); }
+            else {
+                MatArgs a = matrix_mac_args(e, c.base_slot, c.Y2, tc, true); a.y_ch_stride = c.y2_ch_stride;
+                if (launch_mac_matrix(a, sm) != 0) return BFIR_ERR_UNSUPPORTED;
+            }
+        }
     }
     if (!il) {
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
         if (e->pipe3) HIP_TRY(hipStreamWaitEvent(st, e->ev_mac[par], 0));
     }
-    queue_inv(e, p, c, st);
+    if (c.fade) queue_inv_fade(e, c, st); else queue_inv(e, p, c, st);
     if (e->pipe3 && !il) HIP_TRY(hipEventRecord(e->ev_inv[par], st));
-    if (p == Path::Staging) queue_stage_out(e, c, st);
+    if (p == Path::Staging) {
+        if (!c.fade) queue_stage_out(e, c, e->tout, (long)e->chunk * e->L, st);
+        move_staging_history(e, c);
+    }
     e->curbuf ^= (tc & 1);
     e->blockcounter += (unsigned long long)tc;
     e->chunk_seq += 1;
+    if (c.fade) {
+        e->fade_pos += tc;
+        if (e->fade_pos >= e->fade_len) fade_swap_sets(e);   // the last fade block is queued: launches take H by value
+    }
+    return BFIR_OK;
+}
+
+// The fade's work buffers, sized for the chunks it can be cut into: min(chunk, fade_len) blocks.
+static int ensure_fade_buffers(bfir_engine *e)
+{
+    const int want = std::min(e->chunk, e->fade_len);
+    const bool need_ft = !e->fade_fused;
+    if (e->yf_blocks >= want && (!need_ft || e->ft_blocks >= want)) return BFIR_OK;
+    HIP_TRY(hipDeviceSynchronize());   // queued fade chunks may still use the old ones
+    for (int i = 0; i < 2; i++) {
+        if (e->Yf[i]) (void)hipFree(e->Yf[i]);
+        if (e->ft[i]) (void)hipFree(e->ft[i]);
+        e->Yf[i] = e->ft[i] = nullptr;
+    }
+    e->yf_blocks = e->ft_blocks = 0;
+    for (int i = 0; i < (e->pipe3 ? 2 : 1); i++) HIP_TRY(hipMalloc(&e->Yf[i], (size_t)e->GCo * want * cbuf_bytes(e)));
+    e->yf_blocks = want;
+    if (need_ft) {
+        for (int i = 0; i < 2; i++) HIP_TRY(hipMalloc(&e->ft[i], (size_t)e->GCo * want * e->L * e->s));
+        e->ft_blocks = want;
+    }
+    return BFIR_OK;
+}
+
+// n blocks of the caller's buffers (from frame frame_off, block block_base of the call), cut into chunks of at most
+// e->chunk blocks and at the end of a fade, so that a chunk is all fade or all plain.
+static int run_blocks(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride, long frame_off, int n,
+                      int block_base, hipStream_t st, hipEvent_t input_ready)
+{
+    for (int c0 = 0; c0 < n;) {
+        int tc = std::min(e->chunk, n - c0);
+        if (e->fade_len > 0) {
+            const int rc = ensure_fade_buffers(e);
+            if (rc != BFIR_OK) return rc;
+            tc = std::min(tc, std::min(e->fade_len - e->fade_pos, e->yf_blocks));
+        }
+        if (e->inline_launch) e->bad_host_cur = e->h_bad + block_base + c0;   // the NaN verdict of block t lands in h_bad[t]
+        const int rc = run_chunk(e, d_in, in_stride, d_out, out_stride, frame_off + (long)c0 * e->L, tc, block_base + c0, st,
+                                 c0 == 0 ? input_ready : nullptr);
+        if (rc != BFIR_OK) return rc;
+        c0 += tc;
+    }
     return BFIR_OK;
 }
 
@@ -989,12 +1203,8 @@ extern "C" int bfir_engine_run_device(bfir_engine *e, const void *d_in, int64_t 
     if (rc != BFIR_OK) return rc;
     // whatever produced d_in on the caller's stream must be done before the front reads it
     HIP_TRY(hipEventRecord(e->ev_entry, st));
-    for (int c0 = 0; c0 < n_blocks; c0 += e->chunk) {
-        const int tc = std::min(e->chunk, n_blocks - c0);
-        rc = run_chunk(e, d_in, in_stride_bytes, d_out, out_stride_bytes, (long)c0 * e->L, tc, c0, st,
-                       c0 == 0 ? e->ev_entry : nullptr);
-        if (rc != BFIR_OK) return rc;
-    }
+    rc = run_blocks(e, d_in, in_stride_bytes, d_out, out_stride_bytes, 0, n_blocks, 0, st, e->ev_entry);
+    if (rc != BFIR_OK) return rc;
     HIP_TRY(hipGetLastError());
     e->async_pending = true;
     return BFIR_OK;
@@ -1127,11 +1337,7 @@ static int run_small(bfir_engine *e, const void *inbuf, void *outbuf, int n_bloc
         src = e->dev_in[0]; dst = e->dev_out[0];
     }
     e->inline_launch = true;
-    for (int c0 = 0; c0 < n_blocks && rc == BFIR_OK; c0 += e->chunk) {     // the work buffers hold e->chunk blocks
-        e->bad_host_cur = e->h_bad + c0;                                   // the NaN verdict of block c0 + t lands in h_bad[c0 + t]
-        rc = run_chunk(e, src, (long)per_in, dst, (long)per_out, (long)c0 * e->L,
-                       std::min(e->chunk, n_blocks - c0), c0, e->stream, nullptr);
-    }
+    rc = run_blocks(e, src, (long)per_in, dst, (long)per_out, 0, n_blocks, 0, e->stream, nullptr);   // the work buffers hold e->chunk blocks
     e->bad_host_cur = nullptr;
     e->inline_launch = false;
     if (rc != BFIR_OK) return rc;
@@ -1197,8 +1403,7 @@ extern "C" int bfir_engine_run(bfir_engine *e, const void *inbuf, void *outbuf, 
             HIP_TRY(hipMemcpyAsync(e->dev_in[b], e->pin_in[b], per_in * e->n_eng, hipMemcpyHostToDevice, e->s_in));
         }
         HIP_TRY(hipEventRecord(e->ev_h2d[b], e->s_in));
-        rc = run_chunk(e, e->dev_in[b], (long)per_in, e->dev_out[b], (long)per_out, 0, tc, c0, e->stream,
-                       e->ev_h2d[b]);
+        rc = run_blocks(e, e->dev_in[b], (long)per_in, e->dev_out[b], (long)per_out, 0, tc, c0, e->stream, e->ev_h2d[b]);
         if (rc != BFIR_OK) return rc;
         HIP_TRY(hipEventRecord(e->ev_comp[b], e->stream));
         HIP_TRY(hipStreamWaitEvent(e->s_out, e->ev_comp[b], 0));
@@ -1225,6 +1430,7 @@ extern "C" void bfir_engine_reset(bfir_engine *e)
     // zeroed ring reproduces; the time-domain history is NOT cleared, so both
     // input_timecbuf halves are kept (copied out of the work buffers).
     (void)materialise_history(e);
+    if (e->fade_len > 0) fade_swap_sets(e);   // a fade ends at once, with the new set active (the device is idle here)
     (void)hipMemset(e->d_of, 0, sizeof(DevOverflow) * e->GCo * BFIR_OF_SHARDS);
     // block t < B-1 of the new run still reads slots (t - i) mod ring, i > t: the B-1 slots at the top of
     // every channel's ring.  Only those need to read as zero; the rest is rewritten before it is read.

@@ -233,6 +233,35 @@ struct InvPairArgs {
 };
 void launch_inv_pair(const FftPlan &plan, const InvPairArgs &a, hipStream_t s);
 
+// fade.hip: the back end of a crossfaded coefficient change (bfir_engine_set_coeff_fade; the reference's blend is
+// fftw_convolver::convolver_crossfade_inplace, brutefir/fftw_convolver.cpp:275-321).  The MAC has run twice over the same
+// delay line: y_old holds the products with the old filters, y_new those with the new ones.  Sample n of block t blends as
+//   out = y_old * (1.0 - f * (real)m) + y_new * f * (real)m,   m = m0 + t L + n,   f = 1 / (real)(K L - 1)
+// with C's promotions (fp32: the first product and the sum are double, :301-303).
+// k_inv_fade, the fused form: fp32, (re, im) pairs, FLOAT_LE frames, 512 <= L <= 8192 (pair_supported).  One workgroup per
+// (output channel, block): Z = Y_old + i Y_new, ONE inverse of 2L points (`plan` is the plan of 2L points), blend, overflow
+// statistics, NaN guard, frame store.
+struct FadeInvArgs {
+    const float *y_old; long y_old_ch_stride;            // [n_ch][..][N] product spectra, (re, im) pairs
+    const float *y_new; long y_new_ch_stride;
+    float *raw; long frame_off;                          // output frames of ONE engine, n_ch channels wide
+    int n_ch, n_t;
+    float scale, max;
+    float f; int m0;                                     // the ramp: 1 / (K L - 1), and m of sample 0 of block 0
+    DevOverflow *overflow; long of_shard_stride;
+    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+};
+void launch_inv_fade(const FftPlan &plan, const FadeInvArgs &a, hipStream_t s);
+// k_fade_blend, the general form's middle step: y_old[c][i] <- blend(y_old[c][i], y_new[c][i]) on planar time buffers
+// [n_ch][..] (i < n: the chunk's n_t L samples of a channel), m = m0 + i; launch_inv fills them, launch_stage_out follows.
+struct FadeBlendArgs {
+    void *y_old; const void *y_new; long ch_stride;      // in reals
+    int n_ch; long n;
+    double f; int m0;                                    // fp32: f is the float the reference computes (:298), widened
+    int realsize;
+};
+void launch_fade_blend(const FadeBlendArgs &a, hipStream_t s);
+
 // mixnscale with one buffer (a7 / a11) on half-complex data, for the stage API.
 void launch_reorder(const void *in, void *out, int n_fft, double scale, int to_grouped, int realsize,
                     hipStream_t s);

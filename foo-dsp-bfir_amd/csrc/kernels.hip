@@ -1008,6 +1008,14 @@ template <typename T, int LOG2M> static void launch_inv_t(const FftPlan &plan, c
                 return;
             }
         }
+        // fp64 engines that keep (re, im) pairs (the run kernels' sizes): a planar destination is the fade's general back end
+        if constexpr (sizeof(T) == 8 && LOG2M >= BFIR_RUN64_MIN_LOG2M && LOG2M <= BFIR_PAIRS64_MAX_LOG2M) {
+            if (a.interleaved) {
+                hipLaunchKernelGGL((k_inv<T, LOG2M, true>), dim3(items), dim3(FftCfg<LOG2M>::NT), 0, s, a,
+                                   (const V2 *)plan.tw, (const V2 *)plan.ws);
+                return;
+            }
+        }
         hipLaunchKernelGGL((k_inv<T, LOG2M, false>), dim3(items), dim3(FftCfg<LOG2M>::NT), 0, s, a,
                            (const V2 *)plan.tw, (const V2 *)plan.ws);
     }

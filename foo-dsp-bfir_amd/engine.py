@@ -104,6 +104,23 @@ class Brutefir:
         return self._lib.bfir_engine_set_coeff_at(self._h, engine_index, ptrs, n_coeffs, length,
                                                   coeff_blocks, float(scale))
 
+    def set_coeff_fade(self, coeffs, fade_blocks, n_coeffs=None, length=None, coeff_blocks=None, scale=1.0):
+        """bfir_engine_set_coeff_fade: load a second filter set and fade to it over the next `fade_blocks` blocks
+        (the linear ramp of fftw_convolver::convolver_crossfade_inplace, brutefir/fftw_convolver.cpp:275-321).
+        Returns 0 or an ERR_* code; on ERR_COEFF the engine keeps running the old filters."""
+        rd = _real_dtype(self.s)
+        arrs = [np.ascontiguousarray(c, dtype=rd) for c in coeffs]
+        n_coeffs = len(arrs) if n_coeffs is None else n_coeffs
+        length = arrs[0].size if length is None else length
+        coeff_blocks = self.B if coeff_blocks is None else coeff_blocks
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return self._lib.bfir_engine_set_coeff_fade(self._h, ptrs, n_coeffs, length, coeff_blocks, float(scale),
+                                                    int(fade_blocks))
+
+    def fade_remaining(self):
+        """Blocks of a pending or running fade still to be processed; 0 = none."""
+        return self._lib.bfir_engine_fade_remaining(self._h)
+
     def run(self, inbuf, outbuf=None):
         """run(void *inbuf, void *outbuf) for every L-frame block in `inbuf`
         (host arrays).  inbuf: [n_blocks*L, C] (one engine) or
@@ -212,6 +229,19 @@ class BrutefirMatrix(Brutefir):
         coeff_blocks = self.B if coeff_blocks is None else coeff_blocks
         ptrs = (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
         return self._lib.bfir_engine_set_coeff_matrix(self._h, ptrs, length, coeff_blocks, float(scale))
+
+    def set_coeff_fade(self, rows, fade_blocks, length=None, coeff_blocks=None, scale=1.0):
+        """bfir_engine_set_coeff_matrix_fade: rows as set_coeff; a filter that is None in one set and present in the
+        other fades in or out over the next `fade_blocks` blocks."""
+        assert len(rows) == self.n_out and all(len(r) == self.n_in for r in rows)
+        rd = _real_dtype(self.s)
+        arrs = [None if h is None else np.ascontiguousarray(h, dtype=rd) for r in rows for h in r]
+        given = [a for a in arrs if a is not None]
+        length = (given[0].size if given else 0) if length is None else length
+        coeff_blocks = self.B if coeff_blocks is None else coeff_blocks
+        ptrs = (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
+        return self._lib.bfir_engine_set_coeff_matrix_fade(self._h, ptrs, length, coeff_blocks, float(scale),
+                                                           int(fade_blocks))
 
     def run(self, inbuf, outbuf=None):
         """inbuf: [n_blocks*L, n_in] frames in the input format.  Returns (rc, outbuf [n_blocks*L, n_out])."""

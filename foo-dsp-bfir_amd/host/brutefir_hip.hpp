@@ -40,6 +40,17 @@ public:
         return bfir_engine_set_coeff(m_e, (const void *const *)coeffs, n_coeffs, length, coeff_blocks, scale);
     }
 
+    // The same with a crossfade over the next fade_blocks blocks instead of a hard cut: the blend of
+    // fftw_convolver::convolver_crossfade_inplace (fftw_convolver.cpp:275-321) at the engine level.  0, -2 (a NaN/Inf tap:
+    // the old filters stay), or a BFIR_ERR_* code (bfir_engine_set_coeff_fade).
+    int set_coeff_fade(void **coeffs, int n_coeffs, int length, int coeff_blocks, double scale, int fade_blocks)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_fade(m_e, (const void *const *)coeffs, n_coeffs, length, coeff_blocks, scale, fade_blocks);
+    }
+    // blocks of a pending or running fade still to be processed; 0 = none
+    int fade_remaining() { return m_e ? bfir_engine_fade_remaining(m_e) : -1; }
+
     // brutefir.cpp:244-343: one block of filter_length interleaved frames; 0 or -1.
     int run(void *inbuf, void *outbuf) { return run_blocks(inbuf, outbuf, 1); }
 

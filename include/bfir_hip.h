@@ -146,9 +146,39 @@ int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, int n_coeff
  * new filters. */
 int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *coeffs, int length, int coeff_blocks,
                                  double scale);
-/* the same for engine `engine_index` of a batch */
+/* bfir_engine_set_coeff for engine `engine_index` of a batch */
 int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const void *const *coeffs,
                              int n_coeffs, int length, int coeff_blocks, double scale);
+
+/* Crossfaded coefficient change: the engine-level form of fftw_convolver::convolver_crossfade_inplace
+ * (brutefir/fftw_convolver.cpp:275-321), which convolves one block with both filter sets and blends the two time signals
+ * with a linear ramp.  Load a second filter set and fade to it over the next fade_blocks blocks the engine processes;
+ * arguments as bfir_engine_set_coeff, fade_blocks >= 1.  With K = fade_blocks, L = filter_length, t0 the first block
+ * processed after the call and y_old / y_new the blocks the old and the new filters give on the same delay line (working
+ * precision, after the output scale), sample n of block t0 <= t < t0 + K is, with m = (t - t0) L + n,
+ *     y_old[n] * (1.0 - f * (real)m) + y_new[n] * f * (real)m,    f = 1 / (real)(K L - 1)
+ * -- with K = 1 the reference's loop (:298-304), C's promotions included (fp32: the first product and the sum are double);
+ * before t0 the output is y_old, from t0 + K on y_new.  fp64 uses the same roles, old faded out and new faded in: the
+ * reference's fp64 branch (:308-314) reads its operands from the wrong halves of buffer_cbuf, which
+ * bfir_convolver_crossfade_inplace reproduces on purpose and the engine does not.  Overflow statistics, the NaN guard and
+ * the format conversion act on the blended sample.  The fade does not depend on how the blocks arrive (one call or many,
+ * host or device pointers, any bfir_engine_set_chunk).
+ * Returns BFIR_ERR_STATE on an engine without coefficients and while another fade is pending or running (poll
+ * bfir_engine_fade_remaining); BFIR_ERR_ARG for fade_blocks < 1 or K L > 2^24 (m must be exact as a float);
+ * BFIR_ERR_UNSUPPORTED on a batch, on an engine that dithers its output (apply_dither with an integer format), and for
+ * the call that does not match the engine's kind (matrix / diagonal); BFIR_ERR_COEFF on a NaN/Inf tap -- unlike
+ * bfir_engine_set_coeff the engine then stays initialised and keeps running the old filters.
+ * A plain bfir_engine_set_coeff* during a fade cancels it and cuts hard; bfir_engine_reset ends it at once with the new
+ * set active; bfir_engine_read_coeff* reads the active set: the old one until the fade's last block has been queued. */
+int bfir_engine_set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length,
+                               int coeff_blocks, double scale, int fade_blocks);
+/* The same for a matrix engine; coeffs[o * n_inputs + i] or NULL as bfir_engine_set_coeff_matrix.  A filter that is NULL
+ * in one set and present in the other fades in or out.  The fade's blocks take the channel-pair path only if every input
+ * feeds an output under BOTH sets; after the fade the new set decides. */
+int bfir_engine_set_coeff_matrix_fade(bfir_engine *e, const void *const *coeffs, int length,
+                                      int coeff_blocks, double scale, int fade_blocks);
+/* Blocks of a pending or running fade still to be processed; 0 = none.  < 0: error. */
+int bfir_engine_fade_remaining(const bfir_engine *e);
 
 /* brutefir::run (brutefir.cpp:244-343) for n_blocks consecutive blocks.
  * inbuf/outbuf: HOST memory, n_blocks * filter_length interleaved frames in
