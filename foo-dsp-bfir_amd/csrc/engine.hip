@@ -183,6 +183,24 @@ struct bfir_engine {
     void *dev_in[2] = {nullptr, nullptr}, *dev_out[2] = {nullptr, nullptr};
     hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr};
     size_t stage_bytes_in = 0, stage_bytes_out = 0;
+    // Two-level ("nup") engine (bfir_engine_create_nup): THIS engine is the head level -- partitions of L over taps
+    // [0, D), D = B L -- and owns the tail level, a diagonal engine of partitions Lt = r L over the taps from D on, whose
+    // back end is a planar inverse into a time ring (nup_tail; queue_inv_tail).  Output = y_head + z[n - D], z the tail's
+    // overlap-save output in blocks of Lt from sample 0.  Tail block j covers head blocks [j r, (j + 1) r); it is run as
+    // soon as its last head block has arrived and first read by head block j r + B (causal: B >= r).  Neither level pairs
+    // blocks in time and neither takes the staging path, so the bits do not depend on how the blocks arrive.
+    bool nup = false, nup_tail = false;
+    bfir_engine *tail = nullptr;
+    int r = 0;
+    bool tail_active = false;              // the filters reach past D: without, the tail does no work at all
+    bool nup_add = false;                  // the chunk being queued has a tail contribution (run_blocks cuts chunks so: all or none)
+    void *pbuf = nullptr;                  // raw input frames [Lt][C] of the tail block that is still arriving (kept across calls)
+    hipEvent_t ev_nup = nullptr;           // pbuf is filled on the caller's stream; the tail's front waits for this
+    // on the tail: its output, planar [GC][zblocks Lt] reals, tail block j in slot j % zblocks; blocks [z_from, z_next) are
+    // (or will, in stream order, be) there.  zblocks >= ceil((chunk + B) / r) + 2: what one head chunk can still need
+    // plus what is written ahead of it.
+    void *zring = nullptr; int zblocks = 0;
+    long long z_from = 0, z_next = 0;
     // profiling
     bool profiling = false;
     struct Span { int k; hipEvent_t a, b; };
@@ -247,6 +265,7 @@ static int alloc_work(bfir_engine *e, int chunk)
     HIP_TRY(hipMalloc(&X, (size_t)e->GC * ring * cb));
     HIP_TRY(hipMalloc(&Y0, (size_t)e->GCo * chunk * cb));
     HIP_TRY(hipMalloc(&Y1, (size_t)e->GCo * chunk * cb));
+    if (e->nup && !e->pair) HIP_TRY(hipMalloc(&tout, (size_t)e->GCo * chunk * e->L * e->s));   // the general nup back end's planar sum
     if (!e->pair && !e->direct) {   // the pair and direct paths have no planar time buffers
         HIP_TRY(hipMalloc(&tin0, (size_t)e->GC * chunk * e->L * e->s));
         HIP_TRY(hipMalloc(&tin1, (size_t)e->GC * chunk * e->L * e->s));
@@ -307,6 +326,11 @@ static void choose_path(bfir_engine *e)
     e->direct = !e->pair && fmt_is_native(e->in_fmt) && fmt_is_native(e->out_fmt) && !(pv && atoi(pv) == 0) &&
                 (dv ? atoi(dv) != 0 : wide);
     if (e->matrix) e->direct = !e->pair;   // a matrix engine has no staging path: float frames only, direct where not paired
+    if (e->nup || e->nup_tail) {           // both levels of a two-level engine likewise, and no pairs in time: an odd count is direct
+        e->pair = e->pair && !e->pair_tp;
+        e->pair_tp = false;
+        e->direct = !e->pair;
+    }
     // fp64 engines whose transforms the run kernels take keep their spectra -- delay line, filter partitions, products --
     // as (re, im) PAIRS like the fp32 engines, not in the reference's groups of four: one 16-byte access per bin in the
     // MAC instead of two of 8, the forward kernel's spectrum straight from registers (no LDS staging), conflict-free reads
@@ -341,9 +365,10 @@ static void log_creation(const bfir_engine *e)
 }
 
 // matrix: `channels` inputs, `channels_out` outputs, one engine (bfir_engine_create_matrix); else channels_out == channels
+// nup_level: 0, or 1 / 2 for the head / tail level of a two-level engine (bfir_engine_create_nup)
 static bfir_engine *engine_create(int n_engines, int filter_length, int filter_blocks, int realsize, int channels,
                                   int channels_out, bool matrix, int in_format, int out_format, int sampling_rate,
-                                  int apply_dither, int device, int *err)
+                                  int apply_dither, int device, int *err, int nup_level = 0)
 {
     int dummy;
     if (!err) err = &dummy;
@@ -376,6 +401,7 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
     e->in_scale = fmt_info(in_format).isfloat ? 1.0 : 1.0 / fmt_full_scale(in_format);
     e->out_scale = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format);
     e->of_max = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format) - 1.0;
+    e->nup = nup_level == 1; e->nup_tail = nup_level == 2;
     choose_path(e);
     e->nblk.assign(matrix ? (size_t)e->Co * e->C : (size_t)e->GC, 0);   // matrix: [o C + i]
     e->eng_init.assign(n_engines, 0);
@@ -473,11 +499,81 @@ extern "C" bfir_engine *bfir_engine_create(int filter_length, int filter_blocks,
                                     out_format, sampling_rate, apply_dither, device, err);
 }
 
+// the partition lengths bfir_engine_create takes (fft_plan_create: 2^4 .. 2^14, one transform's LDS buffer within 160 KB)
+static bool length_supported(int filter_length, int realsize)
+{
+    return filter_length >= 16 && filter_length <= 16384 &&
+           ((size_t)filter_length + (size_t)filter_length / 32) * 2 * (size_t)realsize <= 160 * 1024;
+}
+
+// The tail's time ring for head chunks of up to `chunk` blocks; the blocks still to be read are carried over.
+static int alloc_zring(bfir_engine *e, int chunk)
+{
+    bfir_engine *t = e->tail;
+    const int zb = (chunk + e->B + e->r - 1) / e->r + 2;
+    if (zb <= t->zblocks) return BFIR_OK;
+    const size_t blk = (size_t)t->L * t->s;
+    void *z = nullptr;
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMalloc(&z, (size_t)t->GC * zb * blk));
+    HIP_TRY(hipMemset(z, 0, (size_t)t->GC * zb * blk));
+    if (t->zring) {
+        const long long lo = std::max(t->z_from, t->z_next - t->zblocks);
+        for (long long j = lo; j < t->z_next; j++)
+            HIP_TRY(hipMemcpy2D((char *)z + (size_t)(j % zb) * blk, (size_t)zb * blk, (char *)t->zring + (size_t)(j % t->zblocks) * blk,
+                                (size_t)t->zblocks * blk, blk, t->GC, hipMemcpyDeviceToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(t->zring);
+    }
+    t->zring = z; t->zblocks = zb;
+    return BFIR_OK;
+}
+
+extern "C" bfir_engine *bfir_engine_create_nup(int filter_length, int head_blocks, int tail_ratio, int tail_blocks, int realsize,
+                                               int channels, int in_format, int out_format, int device, int *err)
+{
+    int dummy;
+    if (!err) err = &dummy;
+    *err = BFIR_ERR_ARG;
+    if (channels < 1 || channels > BFIR_MAXCHANNELS) {
+        bfir_logf("Number of channels (%d) exceeds limit (%d).", channels, BFIR_MAXCHANNELS);
+        return nullptr;
+    }
+    if (realsize != 4 && realsize != 8) { bfir_logf("Invalid real size %d.", realsize); return nullptr; }
+    if (filter_length < 1 || (filter_length & (filter_length - 1))) { bfir_logf("Invalid length %d.", filter_length); return nullptr; }
+    // the tail block a head block reads must be complete: head_blocks >= tail_ratio
+    if (tail_ratio < 2 || (tail_ratio & (tail_ratio - 1)) || head_blocks < tail_ratio || tail_blocks < 1) return nullptr;
+    *err = BFIR_ERR_UNSUPPORTED;
+    if (!length_supported(filter_length, realsize) || (long long)tail_ratio * filter_length > 16384 ||
+        !length_supported(tail_ratio * filter_length, realsize))
+        return nullptr;
+    // float frames only (no staging kernels, no dither)
+    if (!fmt_is_native(in_format) || !fmt_is_native(out_format)) return nullptr;
+    bfir_engine *e = engine_create(1, filter_length, head_blocks, realsize, channels, channels, false, in_format, out_format, 44100,
+                                   0, device, err, 1);
+    if (!e) return nullptr;
+    e->r = tail_ratio;
+    e->tail = engine_create(1, tail_ratio * filter_length, tail_blocks, realsize, channels, channels, false, in_format, out_format,
+                            44100, 0, device, err, 2);
+    auto fail = [&](int code) { *err = code; bfir_engine_destroy(e); return (bfir_engine *)nullptr; };
+    if (!e->tail) return fail(*err);
+    if (hipMalloc(&e->pbuf, (size_t)e->tail->L * e->C * e->in_bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_nup, hipEventDisableTiming) != hipSuccess || alloc_zring(e, e->chunk) != BFIR_OK)
+        return fail(BFIR_ERR_HIP);
+    bfir_logf("bfir engine: two levels, head %d x %d, tail %d x %d; back end %s.", e->L, e->B, e->tail->L, e->tail->B,
+              e->pair ? "fused" : "general");
+    return e;
+}
+
 extern "C" void bfir_engine_destroy(bfir_engine *e)
 {
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
+    if (e->tail) bfir_engine_destroy(e->tail);
+    if (e->pbuf) (void)hipFree(e->pbuf);
+    if (e->zring) (void)hipFree(e->zring);
+    if (e->ev_nup) (void)hipEventDestroy(e->ev_nup);
     free_work(e);
     fft_plan_destroy(&e->plan);
     fft_plan_destroy(&e->plan2);
@@ -571,6 +667,7 @@ extern "C" int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const 
     if (!e || engine_index < 0 || engine_index >= e->n_eng || !coeffs || length < 0 || coeff_blocks < 1)
         return BFIR_ERR_ARG;
     if (e->matrix) return BFIR_ERR_UNSUPPORTED;                 // bfir_engine_set_coeff_matrix
+    if (e->nup) return BFIR_ERR_UNSUPPORTED;                    // bfir_engine_set_coeff_nup
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     e->fade_len = e->fade_pos = 0;                              // a plain change during a fade cancels it: a hard cut, as ever
@@ -590,6 +687,55 @@ extern "C" int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, 
                                      int length, int coeff_blocks, double scale)
 {
     return bfir_engine_set_coeff_at(e, 0, coeffs, n_coeffs, length, coeff_blocks, scale);
+}
+
+// The filters of a two-level engine, split at D = B L: taps [0, D) to the head, the rest to the tail.  Mid-stream both
+// delay lines are kept: the head takes the new filters from the next block, the tail from the next tail block that
+// completes; what the tail has already put into its time ring still plays.
+extern "C" int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->nup) return BFIR_ERR_UNSUPPORTED;
+    bfir_engine *t = e->tail;
+    const long long D = (long long)e->B * e->L;
+    if (!coeffs || n_coeffs < 0 || length < 0 || (long long)length > D + (long long)t->B * t->L) return BFIR_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    e->eng_init[0] = 0;
+    if (n_coeffs > e->C) n_coeffs = e->C;
+    const int len_h = (int)std::min<long long>(length, D), len_t = length - len_h;
+    const int nb_h = std::min(e->B, std::max(1, (len_h + e->L - 1) / e->L));
+    int rc = load_filters(e, e->H, 0, e->C, coeffs, n_coeffs, len_h, nb_h, scale, false);
+    if (rc != BFIR_OK) return rc;
+    const int nb_t = len_t > 0 ? std::min(t->B, (len_t + t->L - 1) / t->L) : 0;
+    if (len_t > 0) {
+        std::vector<const void *> rest((size_t)n_coeffs);
+        for (int n = 0; n < n_coeffs; n++) rest[n] = (const char *)coeffs[n] + (size_t)D * e->s;
+        rc = load_filters(t, t->H, 0, t->C, rest.data(), n_coeffs, len_t, nb_t, scale, false);
+        if (rc != BFIR_OK) return rc;
+    }
+    for (int n = 0; n < e->C; n++) { e->nblk[n] = nb_h; t->nblk[n] = nb_t; }
+    HIP_TRY(hipMemcpy(e->d_nblk, e->nblk.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(t->d_nblk, t->nblk.data(), sizeof(int) * t->C, hipMemcpyHostToDevice));
+    if (len_t > 0 && !e->tail_active) {
+        // The tail starts (again) with the next tail block that begins: its signal state is cleared, the blocks it did
+        // not compute read as zero, and its first Bt blocks lack the input from before (a transient like the one of a new
+        // engine).  Output queued before it stopped is still in the ring.
+        const size_t blk = (size_t)t->L * t->s;
+        const long long j0 = (long long)((e->blockcounter + e->r - 1) / e->r);
+        HIP_TRY(hipMemset(t->X, 0, (size_t)t->GC * t->ring * cbuf_bytes(t)));
+        for (int st = 0; st < 2; st++) for (int i = 0; i < 2; i++) HIP_TRY(hipMemset(t->tails[st][i], 0, (size_t)t->L * t->C * t->in_bytes));
+        const long long oldest = std::max(0ll, ((long long)e->blockcounter - e->B) / e->r);   // the oldest tail block still to be read
+        if (t->z_next <= oldest || t->z_next == t->z_from) t->z_from = j0;
+        else for (long long j = t->z_next; j < j0; j++)   // fewer than B / r + 2 <= zblocks of them
+            HIP_TRY(hipMemset2D((char *)t->zring + (size_t)(j % t->zblocks) * blk, (size_t)t->zblocks * blk, 0, blk, t->GC));
+        t->z_next = j0;
+        t->blockcounter = 0; t->curbuf = 0;
+    }
+    e->tail_active = len_t > 0;
+    t->eng_init[0] = 1;
+    e->eng_init[0] = 1;
+    return BFIR_OK;
 }
 
 // does every input of a matrix engine feed some output under these partition counts ([o C + i])?
@@ -653,6 +799,7 @@ static int set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_coeff
                           int fade_blocks)
 {
     if (e->n_eng > 1 || e->d_dither_tab) return BFIR_ERR_UNSUPPORTED;   // batches; HP-TPDF dither (a recursion over the output samples)
+    if (e->nup) return BFIR_ERR_UNSUPPORTED;                            // two-level engines do not fade
     if (!coeffs || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
     // m = 0 .. K L - 1 must be exact as a float (:302 multiplies by (float)n)
     if (fade_blocks < 1 || (long long)fade_blocks * e->L > (1ll << 24)) return BFIR_ERR_ARG;
@@ -708,6 +855,7 @@ extern "C" int bfir_engine_set_coeff_matrix_fade(bfir_engine *e, const void *con
 extern "C" int bfir_engine_fade_remaining(const bfir_engine *e)
 {
     if (!e) return BFIR_ERR_ARG;
+    if (e->nup) return BFIR_ERR_UNSUPPORTED;
     return e->fade_len > 0 ? e->fade_len - e->fade_pos : 0;
 }
 
@@ -736,7 +884,18 @@ extern "C" int bfir_engine_read_coeff(bfir_engine *e, int channel, int block, vo
 {
     if (!e || channel < 0 || channel >= e->GC || block < 0 || block >= e->B || !dst) return BFIR_ERR_ARG;
     if (e->matrix) return BFIR_ERR_UNSUPPORTED;                 // bfir_engine_read_coeff_matrix
+    if (e->nup) return BFIR_ERR_UNSUPPORTED;                    // bfir_engine_read_coeff_nup
     return read_spectrum(e, channel, block, dst);
+}
+
+extern "C" int bfir_engine_read_coeff_nup(bfir_engine *e, int level, int channel, int block, void *dst)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->nup) return BFIR_ERR_UNSUPPORTED;
+    if (level < 0 || level > 1 || !dst) return BFIR_ERR_ARG;
+    bfir_engine *lv = level ? e->tail : e;
+    if (channel < 0 || channel >= lv->GC || block < 0 || block >= lv->B) return BFIR_ERR_ARG;
+    return read_spectrum(lv, channel, block, dst);
 }
 
 extern "C" int bfir_engine_read_coeff_matrix(bfir_engine *e, int output, int input, int block, void *dst)
@@ -791,6 +950,7 @@ static void drain_spans(bfir_engine *e)
 extern "C" int bfir_engine_set_profiling(bfir_engine *e, int enable)
 {
     if (!e) return BFIR_ERR_ARG;
+    if (e->tail) (void)bfir_engine_set_profiling(e->tail, enable);   // a two-level engine reports the sum of its levels
     drain_spans(e);
     e->profiling = enable != 0;
     if (e->profiling && e->ev_pool.size() < 4096) {   // keep event creation out of timed regions
@@ -804,8 +964,9 @@ extern "C" int bfir_engine_get_profile(bfir_engine *e, int kernel, double *total
 {
     if (!e || kernel < 0 || kernel >= BFIR_K_COUNT) return BFIR_ERR_ARG;
     drain_spans(e);
-    if (total_ms) *total_ms = e->prof_ms[kernel];
-    if (launches) *launches = e->prof_n[kernel];
+    if (e->tail) drain_spans(e->tail);
+    if (total_ms) *total_ms = e->prof_ms[kernel] + (e->tail ? e->tail->prof_ms[kernel] : 0.0);
+    if (launches) *launches = e->prof_n[kernel] + (e->tail ? e->tail->prof_n[kernel] : 0);
     return BFIR_OK;
 }
 
@@ -1034,6 +1195,63 @@ static void queue_inv_fade(bfir_engine *e, const Chunk &c, hipStream_t st)
     queue_stage_out(e, c, e->ft[0], t_stride, st);
 }
 
+// The back end of a tail level's chunk (tc tail blocks from block z_next on): planar inverses into the time ring, one per
+// stretch between wraps.
+static void queue_inv_tail(bfir_engine *e, const Chunk &c, hipStream_t st)
+{
+    ProfScope ps(e, BFIR_K_INV, st);
+    for (int t0 = 0; t0 < c.tc;) {
+        const int slot = (int)((e->z_next + t0) % e->zblocks), n = std::min(c.tc - t0, e->zblocks - slot);
+        InvArgs a;
+        a.src = (const char *)c.Y + (size_t)t0 * cbuf_bytes(e); a.src_ch_stride = (long)e->chunk * e->N;
+        a.dst = (char *)e->zring + (size_t)slot * e->L * e->s; a.dst_ch_stride = (long)e->zblocks * e->L;
+        a.n_t = n; a.n_ch = e->GC;
+        a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
+        launch_inv(e->plan, a, st);
+        t0 += n;
+    }
+    e->z_next += c.tc;
+}
+
+// The back end of a head chunk whose blocks all have a tail contribution: Y and the tail's time ring -> output frames.
+static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
+{
+    const bfir_engine *t = e->tail;
+    const long zlen = (long)t->zblocks * t->L;
+    const long long m0 = ((long long)e->blockcounter - e->B) * e->L, m_min = t->z_from * (long long)t->L;
+    const long m0r = (long)(((m0 % zlen) + zlen) % zlen);
+    if (e->pair) {   // one inverse per channel pair and block, the sum, statistics and frame store in one kernel
+        ProfScope ps(e, BFIR_K_INV, st);
+        NupInvArgs a;
+        a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
+        a.z = (const float *)t->zring; a.z_ch_stride = zlen; a.zlen = zlen;
+        a.m0 = m0; a.m_min = m_min; a.m0r = m0r;
+        a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
+        a.n_ch = e->C; a.n_t = c.tc;
+        a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+        launch_inv_nup(e->plan2, a, st);
+        return;
+    }
+    // the general form: a planar inverse into tout, the sum, then the staging path's output kernel
+    const long t_stride = (long)e->chunk * e->L;
+    {
+        ProfScope ps(e, BFIR_K_INV, st);
+        InvArgs a;
+        a.src = c.Y; a.src_ch_stride = (long)e->chunk * e->N; a.dst = e->tout; a.dst_ch_stride = t_stride;
+        a.n_t = c.tc; a.n_ch = e->GC;
+        a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
+        launch_inv(e->plan, a, st);
+        NupCombineArgs b;
+        b.y = e->tout; b.y_ch_stride = t_stride;
+        b.z = t->zring; b.z_ch_stride = zlen; b.zlen = zlen;
+        b.m0 = m0; b.m_min = m_min; b.m0r = m0r;
+        b.n_ch = e->GC; b.n = (long)c.tc * e->L; b.realsize = e->s;
+        launch_nup_combine(b, st);
+    }
+    queue_stage_out(e, c, e->tout, t_stride, st);
+}
+
 // The staging path's time history, once the chunk is queued (plain or fading: its front is the same): only the
 // references move; the samples stay where stage_in put them (this time buffer is not rewritten before chunk k+2, by
 // which time both references have moved on).
@@ -1101,7 +1319,10 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
         if (e->pipe3) HIP_TRY(hipStreamWaitEvent(st, e->ev_mac[par], 0));
     }
-    if (c.fade) queue_inv_fade(e, c, st); else queue_inv(e, p, c, st);
+    if (c.fade) queue_inv_fade(e, c, st);
+    else if (e->nup_tail) queue_inv_tail(e, c, st);
+    else if (e->nup_add) queue_inv_nup(e, c, st);
+    else queue_inv(e, p, c, st);
     if (e->pipe3 && !il) HIP_TRY(hipEventRecord(e->ev_inv[par], st));
     if (p == Path::Staging) {
         if (!c.fade) queue_stage_out(e, c, e->tout, (long)e->chunk * e->L, st);
@@ -1139,13 +1360,76 @@ static int ensure_fade_buffers(bfir_engine *e)
     return BFIR_OK;
 }
 
+// Two-level engines, ahead of head chunk [a0, a0 + *tc) (a0 = blockcounter): run every tail block that is complete with
+// head block a0 + *tc - 1 and not yet run, then cut the chunk so that its blocks all have a tail contribution or none
+// (nup_add).  A tail block that lies wholly in this call's buffer is transformed straight from the caller's frames --
+// neighbours in one launch -- and the one that began in an earlier call from pbuf, where nup_keep_partial put its first
+// frames; all of a call's input is there when the call is made, so chunks need not be cut at multiples of r.  The
+// tail's front and MAC run on the tail's own streams, its inverse on st: stream order keeps the ring's writes ahead of
+// this chunk's back end and behind the reads of the chunks before.
+static int nup_tail_ahead(bfir_engine *e, const void *d_in, long frame_off, long long call0, int *tc, hipStream_t st,
+                          hipEvent_t input_ready)
+{
+    bfir_engine *t = e->tail;
+    const int r = e->r;
+    const long long a0 = (long long)e->blockcounter, a1 = a0 + *tc;
+    const size_t fb = (size_t)e->C * e->in_bytes;   // bytes per input frame
+    t->inline_launch = e->inline_launch;
+    if (e->tail_active) {
+        for (const long long j_end = a1 / r; t->z_next < j_end;) {
+            const long long j = t->z_next;
+            if (j * r < call0) {   // began before this call: the rest of its frames join the ones kept in pbuf
+                const long long have = call0 - j * r;
+                if (!e->inline_launch && input_ready) HIP_TRY(hipStreamWaitEvent(st, input_ready, 0));
+                HIP_TRY(hipMemcpyAsync((char *)e->pbuf + (size_t)have * e->L * fb, (const char *)d_in + (size_t)frame_off * fb,
+                                       (size_t)(r - have) * e->L * fb, hipMemcpyDefault, st));
+                if (!e->inline_launch) HIP_TRY(hipEventRecord(e->ev_nup, st));
+                const int rc = run_chunk(t, e->pbuf, 0, nullptr, 0, 0, 1, 0, st, e->inline_launch ? nullptr : e->ev_nup);
+                if (rc != BFIR_OK) return rc;
+            } else {
+                const int nt = (int)std::min<long long>(j_end - j, t->chunk);
+                const int rc = run_chunk(t, d_in, 0, nullptr, 0, frame_off + (long)(j * r - call0) * e->L, nt, 0, st, input_ready);
+                if (rc != BFIR_OK) return rc;
+            }
+        }
+    }
+    // head block a reads tail block (a - B) / r: there from z_from on, and (a stopped tail) up to z_next
+    auto adds = [&](long long a) { return a >= e->B && (a - e->B) / r >= t->z_from && (a - e->B) / r < t->z_next; };
+    e->nup_add = adds(a0);
+    int same = 1;
+    while (same < *tc && adds(a0 + same) == e->nup_add) same++;
+    *tc = same;
+    return BFIR_OK;
+}
+
+// ... and at the end of a call: the frames of the tail block that is still arriving go to pbuf, because the caller's
+// buffer is gone when the rest of it comes.
+static int nup_keep_partial(bfir_engine *e, const void *d_in, long frame_off, long long call0, int n, hipStream_t st,
+                            hipEvent_t input_ready)
+{
+    const bfir_engine *t = e->tail;
+    const long long lo = std::max(t->z_next * e->r, call0), hi = call0 + n;
+    if (lo >= hi) return BFIR_OK;
+    const size_t fb = (size_t)e->C * e->in_bytes;
+    if (!e->inline_launch && input_ready) HIP_TRY(hipStreamWaitEvent(st, input_ready, 0));
+    HIP_TRY(hipMemcpyAsync((char *)e->pbuf + (size_t)(lo - t->z_next * e->r) * e->L * fb,
+                           (const char *)d_in + ((size_t)frame_off + (size_t)(lo - call0) * e->L) * fb, (size_t)(hi - lo) * e->L * fb,
+                           hipMemcpyDefault, st));
+    return BFIR_OK;
+}
+
 // n blocks of the caller's buffers (from frame frame_off, block block_base of the call), cut into chunks of at most
 // e->chunk blocks and at the end of a fade, so that a chunk is all fade or all plain.
 static int run_blocks(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride, long frame_off, int n,
                       int block_base, hipStream_t st, hipEvent_t input_ready)
 {
+    const long long call0 = (long long)e->blockcounter;   // the head block at frame_off (two-level engines)
     for (int c0 = 0; c0 < n;) {
         int tc = std::min(e->chunk, n - c0);
+        if (e->nup) {
+            const int rc = nup_tail_ahead(e, d_in, frame_off, call0, &tc, st, input_ready);
+            if (rc != BFIR_OK) return rc;
+        }
         if (e->fade_len > 0) {
             const int rc = ensure_fade_buffers(e);
             if (rc != BFIR_OK) return rc;
@@ -1157,6 +1441,7 @@ static int run_blocks(bfir_engine *e, const void *d_in, long in_stride, void *d_
         if (rc != BFIR_OK) return rc;
         c0 += tc;
     }
+    if (e->nup && e->tail_active) return nup_keep_partial(e, d_in, frame_off, call0, n, st, input_ready);
     return BFIR_OK;
 }
 
@@ -1187,7 +1472,14 @@ static int ensure_chunk(bfir_engine *e, int n_blocks)
     // other kernels of the pipeline get the GPU in between; integer outputs are off the measured path)
     if (e->d_dither_tab) limit = std::min(limit, 64);
     const int want = std::max(1, std::min(limit, n_blocks));
-    if (want > e->chunk) return alloc_work(e, want);
+    if (want > e->chunk) {
+        const int rc = alloc_work(e, want);
+        if (rc != BFIR_OK || !e->nup) return rc;
+        // the tail's launches take the tail blocks of one head chunk; its ring what that chunk can still need
+        const int tw = (want + e->r - 1) / e->r;
+        if (tw > e->tail->chunk) { const int rc2 = alloc_work(e->tail, tw); if (rc2 != BFIR_OK) return rc2; }
+        return alloc_zring(e, want);
+    }
     return BFIR_OK;
 }
 
@@ -1421,10 +1713,29 @@ extern "C" int bfir_engine_run(bfir_engine *e, const void *inbuf, void *outbuf, 
     return bfir_engine_sync(e);
 }
 
+// A two-level engine forgets all signal state -- both delay lines, both time histories, the tail's partial input block and
+// its queued output -- and zeroes the counters: it then behaves as newly created with the same coefficients.  (The plain
+// engine keeps input_timecbuf, a quirk of the reference that has no two-level meaning.)
+static void nup_reset(bfir_engine *e)
+{
+    (void)hipDeviceSynchronize();
+    bfir_engine *lv[2] = {e, e->tail};
+    for (bfir_engine *l : lv) {
+        (void)hipMemset(l->X, 0, (size_t)l->GC * l->ring * cbuf_bytes(l));
+        for (int st = 0; st < 2; st++)
+            for (int i = 0; i < 2; i++) (void)hipMemset(l->tails[st][i], 0, (size_t)l->L * l->C * l->in_bytes);
+        l->blockcounter = 0; l->curbuf = 0;
+    }
+    e->tail->z_from = e->tail->z_next = 0;
+    (void)hipMemset(e->d_of, 0, sizeof(DevOverflow) * e->GCo * BFIR_OF_SHARDS);
+    (void)hipDeviceSynchronize();
+}
+
 extern "C" void bfir_engine_reset(bfir_engine *e)
 {
     if (!e) return;
     (void)hipSetDevice(e->device);
+    if (e->nup) { nup_reset(e); return; }
     // brutefir.cpp:346-367: counters only.  procblocks = 0 hides every
     // delay-line slot written before the reset (brutefir.cpp:292), which the
     // zeroed ring reproduces; the time-domain history is NOT cleared, so both

@@ -262,6 +262,35 @@ struct FadeBlendArgs {
 };
 void launch_fade_blend(const FadeBlendArgs &a, hipStream_t s);
 
+// nup.hip: the back end of a two-level engine (bfir_engine_create_nup).  The head level's products are in y; the tail level
+// has left its time output z in a planar ring [n_ch][zlen] of working precision, sample m of z at m mod zlen.  Sample n of
+// block t of the chunk is  y_head[n] + z[m],  m = m0 + t L + n  (one addition, head first); nothing is added where
+// m < m_min.  m0, m_min and zlen are multiples of L; m0r = m0 mod zlen.
+// k_inv_nup, the fused form: fp32, (re, im) pairs, FLOAT_LE frames, even n_ch, 512 <= L <= 8192 (pair_supported).  One
+// workgroup per (channel pair, block): Z = Y_a + i Y_b, ONE inverse of 2L points (`plan` is the plan of 2L points), the sum,
+// overflow statistics, NaN guard, frame store.
+struct NupInvArgs {
+    const float *y; long y_ch_stride;                    // [n_ch][..][N] product spectra, (re, im) pairs
+    const float *z; long z_ch_stride; long zlen;         // the tail's time ring
+    long long m0, m_min; long m0r;
+    float *raw; long frame_off;                          // output frames of ONE engine, n_ch channels wide
+    int n_ch, n_t;
+    float scale, max;
+    DevOverflow *overflow; long of_shard_stride;
+    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+};
+void launch_inv_nup(const FftPlan &plan, const NupInvArgs &a, hipStream_t s);
+// k_nup_combine, the general form's middle step: y[c][i] <- y[c][i] + z[c][(m0 + i) mod zlen] on a planar time buffer
+// [n_ch][..] (i < n: the chunk's n_t L samples of a channel); launch_inv fills it, launch_stage_out follows.
+struct NupCombineArgs {
+    void *y; long y_ch_stride;                           // in reals
+    const void *z; long z_ch_stride; long zlen;
+    long long m0, m_min; long m0r;
+    int n_ch; long n;
+    int realsize;
+};
+void launch_nup_combine(const NupCombineArgs &a, hipStream_t s);
+
 // mixnscale with one buffer (a7 / a11) on half-complex data, for the stage API.
 void launch_reorder(const void *in, void *out, int n_fft, double scale, int to_grouped, int realsize,
                     hipStream_t s);

@@ -267,3 +267,51 @@ class BrutefirMatrix(Brutefir):
         if rc != 0:
             raise BfirError(rc, "bfir_engine_read_coeff_matrix")
         return dst
+
+
+class BrutefirNup(Brutefir):
+    """Two partition lengths in one engine (bfir_engine_create_nup): taps [0, D), D = head_blocks * filter_length, run on
+    partitions of filter_length, the rest on tail_blocks partitions of tail_ratio * filter_length.  Same convolution, same
+    zero latency and the same filter_length-frame blocks as Brutefir(filter_length, ceil(taps / filter_length), ...), with
+    head_blocks + tail_blocks partitions of MAC work per sample instead.  head_blocks >= tail_ratio, a power of two >= 2.
+    Frames are FLOAT_LE or FLOAT64_LE; the default is the working precision's.
+
+    run / run_device / sync / reset / overflow / check_overflows / set_chunk / set_profiling / profile / close are
+    Brutefir's; reset() discards all signal state (the engine then behaves as newly created with the same filters)."""
+
+    def __init__(self, filter_length, head_blocks, tail_ratio, tail_blocks, realsize, channels, in_format=None,
+                 out_format=None, device=0):
+        dflt = SAMPLE_FORMAT_FLOAT_LE if realsize == 4 else SAMPLE_FORMAT_FLOAT64_LE
+        self.L, self.B, self.s, self.C = filter_length, head_blocks, realsize, channels
+        self.head_blocks, self.tail_ratio, self.tail_blocks = head_blocks, tail_ratio, tail_blocks
+        self.D = head_blocks * filter_length
+        self.max_taps = self.D + tail_blocks * tail_ratio * filter_length
+        self.in_format = dflt if in_format is None else in_format
+        self.out_format = dflt if out_format is None else out_format
+        self.n_engines, self.device = 1, device
+        self._lib = _lib.load()
+        err = C.c_int(0)
+        self._h = self._lib.bfir_engine_create_nup(filter_length, head_blocks, tail_ratio, tail_blocks, realsize, channels,
+                                                   self.in_format, self.out_format, device, C.byref(err))
+        if not self._h:
+            raise BfirError(err.value, "bfir_engine_create_nup")
+
+    def set_coeff(self, coeffs, scale=1.0):
+        """coeffs[c]: the taps of channel c, at most max_taps of them; split at D between the two levels.
+        Returns 0 or an ERR_* code (ERR_COEFF: a NaN / Inf tap, the engine is uninitialised)."""
+        rd = _real_dtype(self.s)
+        arrs = [np.ascontiguousarray(c, dtype=rd) for c in coeffs]
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return self._lib.bfir_engine_set_coeff_nup(self._h, ptrs, len(arrs), arrs[0].size, float(scale))
+
+    def set_coeff_fade(self, *args, **kwargs):
+        raise BfirError(_lib.ERR_UNSUPPORTED, "bfir_engine_set_coeff_fade")
+
+    def coeff_block(self, level, channel, block):
+        """Partition spectrum `block` of `channel` on level 0 (head, 2 L reals) or 1 (tail, 2 tail_ratio L reals)."""
+        n = 2 * self.L * (self.tail_ratio if level else 1)
+        dst = np.zeros(n, dtype=_real_dtype(self.s))
+        rc = self._lib.bfir_engine_read_coeff_nup(self._h, level, channel, block, dst.ctypes.data)
+        if rc != 0:
+            raise BfirError(rc, "bfir_engine_read_coeff_nup")
+        return dst

@@ -23,6 +23,19 @@ public:
         m_err = err;
         memset(m_last, 0, sizeof(m_last));
     }
+    // Two partition lengths (bfir_engine_create_nup): taps [0, head_blocks * filter_length) on partitions of filter_length,
+    // the rest on tail_blocks partitions of tail_ratio * filter_length; run() keeps its filter_length-frame blocks.
+    // Float frames only, no dither.  Coefficients: the set_coeff(coeffs, n_coeffs, length, scale) overload.
+    struct two_level { int head_blocks, tail_ratio, tail_blocks; };
+    brutefir(int filter_length, two_level levels, int realsize, int channels, int in_format, int out_format, int device = 0)
+        : m_channels(channels)
+    {
+        int err = 0;
+        m_e = bfir_engine_create_nup(filter_length, levels.head_blocks, levels.tail_ratio, levels.tail_blocks, realsize,
+                                     channels, in_format, out_format, device, &err);
+        m_err = err;
+        memset(m_last, 0, sizeof(m_last));
+    }
     ~brutefir() { bfir_engine_destroy(m_e); }
     brutefir(const brutefir &) = delete;
     brutefir &operator=(const brutefir &) = delete;
@@ -50,6 +63,13 @@ public:
     }
     // blocks of a pending or running fade still to be processed; 0 = none
     int fade_remaining() { return m_e ? bfir_engine_fade_remaining(m_e) : -1; }
+
+    // A two-level engine's filters: `length` taps per channel, split between the levels (bfir_engine_set_coeff_nup).
+    int set_coeff(void **coeffs, int n_coeffs, int length, double scale)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_nup(m_e, (const void *const *)coeffs, n_coeffs, length, scale);
+    }
 
     // brutefir.cpp:244-343: one block of filter_length interleaved frames; 0 or -1.
     int run(void *inbuf, void *outbuf) { return run_blocks(inbuf, outbuf, 1); }

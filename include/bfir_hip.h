@@ -127,6 +127,40 @@ bfir_engine *bfir_engine_create_batch(int n_engines, int filter_length, int filt
 bfir_engine *bfir_engine_create_matrix(int filter_length, int filter_blocks, int realsize, int n_inputs,
                                        int n_outputs, int in_format, int out_format, int device, int *err);
 
+/* Two partition lengths in one engine ("nup": non-uniform partitioning): a long impulse response at a small block length
+ * without a partition count that grows with it.  The head level convolves taps [0, D), D = head_blocks * filter_length,
+ * in partitions of filter_length = L; the tail level the taps from D on in tail_blocks partitions of tail_ratio * L.  The
+ * engine computes the linear convolution a uniform engine of partition L computes, with no added latency and L-frame
+ * blocks at its interface:  y[n] = y_head[n] + z[n - D],  z the tail's output in blocks of tail_ratio * L from sample 0
+ * (z[m] = 0 for m < 0).  A tail block is transformed when its last L-block has arrived and first read head_blocks -
+ * tail_ratio + 1 blocks later, hence head_blocks >= tail_ratio.  The output sample is one addition in working precision,
+ * head first, each term after the output scale; format conversion, overflow statistics and the NaN guard (sample 0 of
+ * every L-block) act on the sum.  The output does not depend on how the blocks arrive (one call or many, host or
+ * device pointers, any bfir_engine_set_chunk).  While the filters do not reach past D the tail does no work and the
+ * output is, bit for bit, that of bfir_engine_create(L, head_blocks, ...) run in direct mode or on channel pairs.
+ * A diagonal engine, 1 <= channels <= BFIR_MAXCHANNELS; an odd channel count runs one channel per transform.
+ * BFIR_ERR_ARG: tail_ratio not a power of two or below 2, head_blocks < tail_ratio, tail_blocks < 1.
+ * BFIR_ERR_UNSUPPORTED: filter_length or tail_ratio * filter_length outside what bfir_engine_create takes for realsize; a
+ * frame format other than FLOAT_LE / FLOAT64_LE.  Arguments are checked before the device.
+ * run, run_device, sync, get_overflow, set_chunk, is_initialized, set_profiling, get_profile (the sum of both levels) and
+ * destroy work on it unchanged in meaning, in blocks of L frames.  bfir_engine_reset discards ALL signal state of such an
+ * engine -- both delay lines, both time histories, the tail's partial input block and its queued output -- and zeroes
+ * the counters; the engine then behaves as newly created with the same coefficients.  (The plain engine keeps
+ * input_timecbuf across a reset, a quirk of the reference with no two-level meaning.)
+ * bfir_engine_set_coeff, _set_coeff_at, _read_coeff, the matrix calls and the fade calls return BFIR_ERR_UNSUPPORTED on
+ * it; the three nup calls the same on every other kind of engine. */
+bfir_engine *bfir_engine_create_nup(int filter_length, int head_blocks, int tail_ratio, int tail_blocks, int realsize,
+                                    int channels, int in_format, int out_format, int device, int *err);
+/* coeffs[n]: `length` taps in working precision, length <= D + tail_blocks * tail_ratio * L (more: BFIR_ERR_ARG); split
+ * at D, ragged ends zero-filled as coeff::preprocess_coeff does.  A NaN/Inf tap: BFIR_ERR_COEFF and the engine is
+ * uninitialised.  Mid-stream both delay lines are kept: the head uses the new filters from the next block, the tail from
+ * the next tail block that completes, and tail output already queued still plays -- the change reaches the output tap by
+ * tap within head_blocks + tail_ratio blocks.  A tail that had no taps starts with the next tail block that begins, on an
+ * empty delay line. */
+int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale);
+/* partition spectrum `block` of `channel`: level 0 = head (2 L reals), 1 = tail (2 tail_ratio L reals); grouped layout */
+int bfir_engine_read_coeff_nup(bfir_engine *e, int level, int channel, int block, void *dst);
+
 void bfir_engine_destroy(bfir_engine *e);
 
 /* brutefir::is_initialized */
