@@ -1,10 +1,16 @@
 """The transform-size matrix: one row per (kernel family, realsize, L) the engine supports, the channel count, frame
 formats and switches that make the engine take that family, and what its creation log line must then report.
 
-Plain data, importable without a GPU: tests/test_size_matrix.py checks on the CPU that CELLS covers exactly the set
-the sources in csrc/ support; tests/test_size_matrix_gpu.py runs every row on the device."""
+NUP_CELLS, FADE_CELLS and MATRIX_CELLS are the same for the engine kinds built on top of the plain diagonal engine:
+two-level engines (csrc/nup.hip and the tail level in engine.hip), crossfaded coefficient changes (csrc/fade.hip) and
+matrix engines (csrc/matrix.hip).
+
+Plain data, importable without a GPU: tests/test_size_matrix.py checks on the CPU that the lists cover exactly the set
+the sources in csrc/ support; tests/test_size_matrix_gpu.py and tests/test_size_matrix_kinds_gpu.py run every row on
+the device."""
 import os
 import re
+import zlib
 
 import numpy as np
 
@@ -40,7 +46,7 @@ def _const(src, name):
 
 def source_limits():
     """The size lists and limits in csrc/ that decide which kernels an engine of size L can run."""
-    k, p = _read("kernels.hip"), _read("pair.hip")
+    k, p, kh = _read("kernels.hip"), _read("pair.hip"), _read("kernels.h")
     lds = re.search(r"filter_length\s*/\s*32\)\s*\*\s*2\s*\*\s*\(size_t\)realsize\s*>\s*(\d+)\s*\*\s*1024", k)
     run_max = re.search(r"bool run64_supported\(.*?filter_length <= (\d+);", k, re.S)
     assert lds and run_max
@@ -51,7 +57,23 @@ def source_limits():
         "run64_max_len": int(run_max.group(1)),
         "pairs64_max_log2m": _const(k, "BFIR_PAIRS64_MAX_LOG2M"),
         "lds_bytes": int(lds.group(1)) * 1024,
+        "nup_log2n": _macro_list(_read("nup.hip"), "BFIR_FOR_NUP_LOG2N"),
+        "fade_log2n": _macro_list(_read("fade.hip"), "BFIR_FOR_FADE_LOG2N"),
+        "mat_small_max": _const(kh, "BFIR_MAT_SMALL_MAX"),
     }
+
+
+def fade_fused_rule():
+    """The right-hand side of `e->fade_fused = ...;` in engine.hip: which engines k_inv_fade serves."""
+    m = re.search(r"e->fade_fused\s*=\s*([^;]+);", _read("engine.hip"))
+    assert m
+    return " ".join(m.group(1).split())
+
+
+def fade_is_fused(lim, s, L, out_fmt):
+    """fade_fused_rule() restated: fp32 spectra kept as (re, im) pairs (2L >= 512: choose_path), FLOAT_LE output frames
+    and a pair plan of 2L points (pair_supported)."""
+    return s == 4 and 2 * L >= 512 and out_fmt == FLOAT_LE and L in [1 << (n - 1) for n in lim["pair_log2n"]]
 
 
 def supported_lengths(lim, s):
@@ -84,6 +106,16 @@ def supported_set(lim):
         "run64_pairs": (8, run_pairs),
         "run64_grouped": (8, run),
         "plugin": (8, f64),
+        # two-level engines: the head's L with a tail of 2L (the smallest ratio) that the level below takes as well; the
+        # fused back end where k_inv_nup has an instance of 2L points
+        "nup_fused": (4, [1 << (n - 1) for n in lim["nup_log2n"]]),
+        "nup_general32": (4, [L for L in f32 if 2 * L in f32]),
+        "nup_general64": (8, [L for L in f64 if 2 * L in f64]),
+        "fade_fused": (4, [1 << (n - 1) for n in lim["fade_log2n"]]),
+        "fade_general32": (4, f32),
+        "fade_general64": (8, f64),
+        "matrix32": (4, f32),
+        "matrix64": (8, f64),
     }
     return {(f, s, L) for f, (s, Ls) in fams.items() for L in Ls}
 
@@ -154,6 +186,107 @@ REFUSALS = [(8, 16384, "ERR_UNSUPPORTED"), (4, 8, "ERR_UNSUPPORTED"), (8, 8, "ER
             (4, 32768, "ERR_UNSUPPORTED"), (8, 32768, "ERR_UNSUPPORTED")]
 
 
+# ---- the engine kinds on top of the plain diagonal engine ---------------------------------------------------------------
+# Same recipe as above for all three: flat_ir filters (a distinct one per channel or per (output, input) pair) cast to the
+# working precision, uniform noise with the odd channels (inputs) at 1/8, the float64 / long-double reference, the
+# per-block, per-channel norm of block_errors and the tolerance of tolerance() -- the project's own, nothing new.
+def _kind_cell(family, s, L, C, fin, fout, tag, **more):
+    cell = {"id": "%s-s%d-L%d-C%d-%d.%d%s" % (family, s, L, C, fin, fout, tag), "family": family, "s": s, "L": L, "C": C,
+            "in_fmt": fin, "out_fmt": fout, "env": {k: None for k in PATH_SWITCHES}}
+    cell.update(more)
+    return cell
+
+
+def _nup_cell(family, s, L, C, fin, fout, back, r=2, Bt=2):
+    """Bh = r; taps end RAGGED short of the last tail partition; nb blocks make the tail's delay line and its time ring
+    wrap (tests/test_nup_gpu.py: nb >= Bh + r (Bt + 2) + 3)."""
+    Bh = r
+    return _kind_cell(family, s, L, C, fin, fout, "-r%dx%d" % (r, Bt), Bh=Bh, r=r, Bt=Bt, back=back,
+                      taps=Bh * L + (Bt - 1) * r * L + r * L - RAGGED, nb=Bh + r * (Bt + 2) + 3)
+
+
+def _build_nup_cells():
+    cells = []
+    add = lambda *a, **k: cells.append(_nup_cell(*a, **k))
+    for L in (512, 1024, 2048, 4096, 8192):       # k_inv_nup: fp32, float frames, an even channel count
+        for C in (2, 8):
+            add("nup_fused", 4, L, C, FLOAT_LE, FLOAT_LE, "fused")
+    add("nup_fused", 4, 512, 2, FLOAT_LE, FLOAT_LE, "fused", r=32, Bt=1)      # a large ratio: tail partitions of 16384
+    for L in [1 << lg for lg in range(4, 14)]:    # k_nup_combine<float>: an odd count anywhere, any count below the pair plans
+        add("nup_general32", 4, L, 3, FLOAT_LE, FLOAT_LE, "general")
+        if L < 512:
+            add("nup_general32", 4, L, 2, FLOAT_LE, FLOAT_LE, "general")
+    for L in [1 << lg for lg in range(4, 13)]:    # k_nup_combine<double>
+        for C in (2, 3):
+            add("nup_general64", 8, L, C, FLOAT64_LE, FLOAT64_LE, "general")
+        if L in (64, 1024, 4096):                 # the plug-in's shape: fp64 arithmetic, float32 stereo frames
+            add("nup_general64", 8, L, 2, FLOAT_LE, FLOAT_LE, "general")
+    return cells
+
+
+FADE_K = 3                # blocks of the fade; with chunks of 2 it is cut into 2 + 1, so the second part starts at m0 = 2L
+
+
+def _build_fade_cells():
+    """B partitions, ragged taps; t0 = B + 1 blocks, the fade, K + B + 2 more.  The new set has 1/8 of the old set's gain
+    in half of the cells and 8 times in the other half (gains (1, 1/8) and (1/8, 1): the loud set is the same size in
+    both), so a leak between the halves of Z = Y_old + i Y_new shows at either end of the ramp."""
+    cells = []
+
+    def add(family, s, L, C, fin, fout):
+        lg = L.bit_length() - 1
+        new_gain = 0.125 if (lg + C) % 2 == 0 else 8.0
+        cells.append(_kind_cell(family, s, L, C, fin, fout, "-g%g" % new_gain, new_gain=new_gain, t0=B + 1,
+                                nb=B + 1 + FADE_K + B + 2, taps=B * L - RAGGED))
+    for L in (512, 1024, 2048, 4096, 8192):       # k_inv_fade: channel pairs and pairs in time
+        for C in (2, 3):
+            add("fade_fused", 4, L, C, FLOAT_LE, FLOAT_LE)
+    for L in (16, 32, 64, 128, 256, 16384):       # k_fade_blend<float>: outside the pair plans
+        for C in (2, 3):
+            add("fade_general32", 4, L, C, FLOAT_LE, FLOAT_LE)
+    for L in (512, 1024, 2048, 4096, 8192):       # ... and inside them where the output frames are not FLOAT_LE
+        add("fade_general32", 4, L, 2, FLOAT_LE, FLOAT64_LE)
+    for L in [1 << lg for lg in range(4, 14)]:    # k_fade_blend<double>
+        add("fade_general64", 8, L, 2, FLOAT64_LE, FLOAT64_LE)
+        if L in (64, 1024, 4096):
+            add("fade_general64", 8, L, 3, FLOAT_LE, FLOAT_LE)
+    return cells
+
+
+MATRIX_CALLS = (3, 11)    # blocks per call: the one-block-per-lane MAC (<= BFIR_MAT_SMALL_MAX), then time tiles 8 + 3 / 4 + 4 + 3
+
+
+def _build_matrix_cells():
+    """B partitions, ragged taps, one NULL filter; every matrix engine here is in direct mode (an odd count on one side, or
+    fp64)."""
+    cells = []
+
+    def add(family, s, L, n_in, n_out, fmt):
+        lg = L.bit_length() - 1
+        layout = "pairs" if (L >= 256 if s == 4 else 1024 <= L <= 4096) else "grouped"
+        cells.append(_kind_cell(family, s, L, n_in, fmt, fmt, "-to%d" % n_out, n_in=n_in, n_out=n_out,
+                                null=(lg % n_out, lg % n_in), path="direct", layout=layout, nb=sum(MATRIX_CALLS),
+                                taps=B * L - RAGGED))
+    for L in [1 << lg for lg in range(4, 15)]:
+        add("matrix32", 4, L, 2, 3, FLOAT_LE)     # an output tile of 4 with one row unused
+        if L in (16, 256, 4096):
+            add("matrix32", 4, L, 3, 5, FLOAT_LE)  # two output tiles, the second ragged
+    for L in [1 << lg for lg in range(4, 14)]:
+        add("matrix64", 8, L, 2, 3, FLOAT64_LE)   # output tiles of 2, the second ragged
+        if L == 1024:
+            add("matrix64", 8, L, 2, 2, FLOAT_LE)
+    return cells
+
+
+NUP_CELLS = _build_nup_cells()
+FADE_CELLS = _build_fade_cells()
+MATRIX_CELLS = _build_matrix_cells()
+KIND_CELLS = NUP_CELLS + FADE_CELLS + MATRIX_CELLS
+
+# bfir_engine_create_nup must fail: (realsize, L, tail_ratio, error name) -- the tail's partition is past the range
+NUP_REFUSALS = [(4, 16384, 2, "ERR_UNSUPPORTED"), (8, 8192, 2, "ERR_UNSUPPORTED")]
+
+
 # ---- test data and the float64 reference ------------------------------------------------------------------------
 def flat_ir(rng, channels, taps):
     """Distinct float64 impulse responses with a flat envelope (every partition, the ragged tail included, carries
@@ -222,3 +355,84 @@ def hc2r(hc):
     X.real = hc[:n // 2 + 1]
     X.imag[1:n // 2] = hc[n // 2 + 1:][::-1]
     return np.fft.irfft(X, n) * n
+
+
+# ---- data, references and the norm of the engine-kind cells ---------------------------------------------------------
+def tolerance(cell, TOL):
+    """The project's own (conftest.TOL): 1e-5 for fp32 arithmetic or float32 output frames, TOL[8] otherwise."""
+    return 1e-5 if (cell["s"] == 4 or cell["out_fmt"] == FLOAT_LE) else TOL[cell["s"]]
+
+
+def block_errors(y, ref, L):
+    """[C, n_blocks] max |y - ref| of each output block of each channel over that channel's own max |ref|."""
+    y, ref = np.asarray(y, np.float64), np.asarray(ref, np.float64)
+    nb, Cn = ref.shape[0] // L, ref.shape[1]
+    d = np.abs(y - ref).reshape(nb, L, Cn).max(axis=1).T
+    return d / np.maximum(np.abs(ref).max(axis=0), 1e-300)[:, None]
+
+
+def _rng(cell):
+    return np.random.default_rng(zlib.crc32(cell["id"].encode()))
+
+
+def _noise(orc, rng, cell):
+    """The frames sent: uniform noise, odd channels at 1/8, in the input format."""
+    nb, L, Cn = cell["nb"], cell["L"], cell["C"]
+    return (rng.uniform(-1.0, 1.0, (nb * L, Cn)) * amplitudes(nb, L, Cn, False)).astype(orc.fmt_dtype(cell["in_fmt"]))
+
+
+def reference(orc, x, h):
+    """[frames, C] float64: reference_conv per channel, from the float64 value of the frames and taps actually sent."""
+    x64 = np.asarray(x, np.float64)
+    return np.stack([reference_conv(orc, x64[:, c], np.asarray(h[c], np.float64)) for c in range(len(h))], axis=1)
+
+
+def nup_data(orc, cell):
+    """(h, x) of a two-level cell: taps in the working precision, frames in the input format."""
+    rng = _rng(cell)
+    h = [v.astype(orc.real_dtype(cell["s"])) for v in flat_ir(rng, cell["C"], cell["taps"])]
+    return h, _noise(orc, rng, cell)
+
+
+def fade_data(orc, cell):
+    """(h_old, h_new, x) of a fade cell."""
+    rng = _rng(cell)
+    dt = orc.real_dtype(cell["s"])
+    g_old, g_new = (1.0, 0.125) if cell["new_gain"] < 1.0 else (0.125, 1.0)
+    h_old = [(v * g_old).astype(dt) for v in flat_ir(rng, cell["C"], cell["taps"])]
+    h_new = [(v * g_new).astype(dt) for v in flat_ir(rng, cell["C"], cell["taps"])]
+    return h_old, h_new, _noise(orc, rng, cell)
+
+
+def fade_reference(orc, cell, h_old, h_new, x):
+    """float64: y_old before block t0, y_old (1 - f m) + y_new f m with f = 1 / (K L - 1), m = (t - t0) L + n over the K
+    blocks of the fade, y_new after it; y_old / y_new the reference convolutions of the whole stream."""
+    L, t0, K = cell["L"], cell["t0"], FADE_K
+    y_old, y_new = reference(orc, x, h_old), reference(orc, x, h_new)
+    y = y_old.copy()
+    y[(t0 + K) * L:] = y_new[(t0 + K) * L:]
+    fm = (np.arange(K * L) / (K * L - 1.0))[:, None]
+    a, b = t0 * L, (t0 + K) * L
+    y[a:b] = y_old[a:b] * (1.0 - fm) + y_new[a:b] * fm
+    return y
+
+
+def matrix_data(orc, cell):
+    """(rows, x) of a matrix cell: rows[o][i] the taps of h_{o,i}, None at cell["null"]."""
+    rng = _rng(cell)
+    dt = orc.real_dtype(cell["s"])
+    rows = [[v.astype(dt) for v in flat_ir(rng, cell["n_in"], cell["taps"])] for _ in range(cell["n_out"])]
+    o, i = cell["null"]
+    rows[o][i] = None
+    return rows, _noise(orc, rng, cell)
+
+
+def matrix_reference_conv(orc, rows, x):
+    """[frames, n_out] float64: output o is the sum over the inputs of reference_conv(x_i, h_{o,i})."""
+    x64 = np.asarray(x, np.float64)
+    out = np.zeros((x64.shape[0], len(rows)))
+    for o, row in enumerate(rows):
+        for i, h in enumerate(row):
+            if h is not None:
+                out[:, o] += reference_conv(orc, x64[:, i], np.asarray(h, np.float64))
+    return out

@@ -1,17 +1,28 @@
 """The size matrix of tests/test_size_matrix_gpu.py against the sources, on the CPU: adding a transform size to the
 kernels or moving a size limit fails here until the matrix follows."""
+import collections
+
 import numpy as np
 import pytest
 
 import size_matrix as SM
+from conftest import TOL, rel_err
+from test_fade import fade_expected
+from test_matrix import matrix_reference
+
+ALL_CELLS = SM.CELLS + SM.KIND_CELLS
 
 
 def test_matrix_covers_exactly_what_the_sources_support():
     lim = SM.source_limits()
     want = SM.supported_set(lim)
-    have = {(c["family"], c["s"], c["L"]) for c in SM.CELLS}
+    have = {(c["family"], c["s"], c["L"]) for c in ALL_CELLS}
     assert sorted(want - have) == [], "sizes the build supports that no cell runs"
     assert sorted(have - want) == [], "cells at sizes the build does not support"
+    # ... list by list: a family's cells are in the list of its kind and nowhere else
+    for prefix, cells in (("nup_", SM.NUP_CELLS), ("fade_", SM.FADE_CELLS), ("matrix", SM.MATRIX_CELLS)):
+        assert {k for k in want if k[0].startswith(prefix)} == {(c["family"], c["s"], c["L"]) for c in cells}
+    assert not [c["id"] for c in SM.CELLS if c["family"].startswith(("nup_", "fade_", "matrix"))]
 
 
 def test_matrix_refusals_are_the_unsupported_neighbours():
@@ -27,11 +38,17 @@ def test_source_limits_parse():
     assert lim["pair_log2n"] and set(lim["pair_log2n"]) <= {lg + 1 for lg in lim["log2m"]}
     assert lim["run64_min_log2m"] <= lim["pairs64_max_log2m"] and (1 << lim["pairs64_max_log2m"]) <= lim["run64_max_len"]
     assert lim["lds_bytes"] > 0
+    # the fused back ends of the two-level engines and of the fade run where the pair plans do (engine.hip asks
+    # pair_supported for both), one instance per plan
+    assert lim["nup_log2n"] == lim["pair_log2n"] and lim["fade_log2n"] == lim["pair_log2n"]
+    assert max(SM.MATRIX_CALLS[0], 1) <= lim["mat_small_max"] < SM.MATRIX_CALLS[1]
 
 
 def test_cells_set_every_path_switch_and_are_unique():
-    ids = [c["id"] for c in SM.CELLS]
+    ids = [c["id"] for c in ALL_CELLS]
     assert len(ids) == len(set(ids))
+    for c in SM.KIND_CELLS:
+        assert set(c["env"]) == set(SM.PATH_SWITCHES), c["id"]
     for c in SM.CELLS:
         assert set(c["env"]) == set(SM.PATH_SWITCHES), c["id"]
         assert c["path"] in ("pair", "time-pair", "direct", "staging") and c["layout"] in ("pairs", "grouped")
@@ -67,3 +84,109 @@ def test_flat_ir_keeps_the_tail_loud():
         assert abs(np.abs(h).sum() - 1.0) < 1e-12
         first, tail = np.abs(h[:L]).mean(), np.abs(h[(SM.B - 1) * L:]).mean()
         assert 0.5 < tail / first < 2.0
+
+
+# ---- the engine kinds: two-level engines, fades, matrix engines ------------------------------------------------------
+def test_kind_cells_are_the_ones_the_sweep_is_made_of():
+    """Per family, the number of cells the sizes in the sources ask for: taking an entry out of a list fails here (or in
+    the coverage test above, where it was the only one of its size)."""
+    lim = SM.source_limits()
+    f32, f64 = SM.supported_lengths(lim, 4), SM.supported_lengths(lim, 8)
+    fused = [1 << (n - 1) for n in lim["pair_log2n"]]
+    t32, t64 = [L for L in f32 if 2 * L in f32], [L for L in f64 if 2 * L in f64]
+    want = {
+        "nup_fused": 2 * len(fused) + 1,                                    # C = 2, 8; the large ratio
+        "nup_general32": len(t32) + len([L for L in t32 if L < min(fused)]),       # C = 3; C = 2 below the pair plans
+        "nup_general64": 2 * len(t64) + 3,                                  # C = 2, 3; the plug-in's frames at three sizes
+        "fade_fused": 2 * len(fused),                                       # channel pairs, pairs in time
+        "fade_general32": 2 * (len(f32) - len(fused)) + len(fused),         # C = 2, 3 outside the plans; double frames inside
+        "fade_general64": len(f64) + 3,
+        "matrix32": len(f32) + 3,
+        "matrix64": len(f64) + 1,
+    }
+    assert dict(collections.Counter(c["family"] for c in SM.KIND_CELLS)) == want
+
+
+def test_two_level_cells_reach_every_tail_length():
+    lim = SM.source_limits()
+    for s in (4, 8):
+        tails = {c["r"] * c["L"] for c in SM.NUP_CELLS if c["s"] == s}
+        assert tails == {Lt for Lt in SM.supported_lengths(lim, s) if Lt >= 32}, s
+    for c in SM.NUP_CELLS:
+        assert c["Bh"] == c["r"] and c["back"] == ("fused" if c["family"] == "nup_fused" else "general"), c["id"]
+        # ends inside the last tail partition; both the tail's delay line and its time ring wrap
+        assert 0 < c["Bh"] * c["L"] + c["Bt"] * c["r"] * c["L"] - c["taps"] < c["r"] * c["L"]
+        assert c["nb"] >= c["Bh"] + c["r"] * (c["Bt"] + 2) + 3
+        # what engine.hip's choose_path gives the head: channel pairs (no pairs in time on a two-level engine)
+        pair = c["s"] == 4 and c["in_fmt"] == c["out_fmt"] == SM.FLOAT_LE and c["C"] % 2 == 0 and \
+            c["L"] in [1 << (n - 1) for n in lim["nup_log2n"]]
+        assert pair == (c["back"] == "fused"), c["id"]
+    # the refusals: one step past the largest tail of each precision
+    assert {(s, L) for s, L, r, _ in SM.NUP_REFUSALS if r == 2} == {(s, max(SM.supported_lengths(lim, s))) for s in (4, 8)}
+
+
+def test_fade_cells_follow_the_engines_rule():
+    """engine.hip `e->fade_fused = ...`: the rule as SM.fade_is_fused restates it, and every cell on its side of it."""
+    lim = SM.source_limits()
+    rule = SM.fade_fused_rule()
+    assert rule == "e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L)", rule
+    for c in SM.FADE_CELLS:
+        assert SM.fade_is_fused(lim, c["s"], c["L"], c["out_fmt"]) == (c["family"] == "fade_fused"), c["id"]
+    # both gain directions in every family, and on both fused paths (channel pairs: C = 2, pairs in time: C = 3)
+    for fam in ("fade_fused", "fade_general32", "fade_general64"):
+        assert {c["new_gain"] for c in SM.FADE_CELLS if c["family"] == fam} == {0.125, 8.0}
+    for Cn in (2, 3):
+        assert {c["new_gain"] for c in SM.FADE_CELLS if c["family"] == "fade_fused" and c["C"] == Cn} == {0.125, 8.0}
+
+
+def _oracle_uniform(orc, cell, h, x):
+    L = cell["L"]
+    o = orc.Engine(L, -(-cell["taps"] // L), cell["s"], cell["C"], cell["in_fmt"], cell["out_fmt"])
+    assert o.set_coeff(h) == 0
+    rc, y = o.run(x)
+    assert rc == 0
+    o.close()
+    return y
+
+
+@pytest.mark.parametrize("cell", SM.KIND_CELLS, ids=[c["id"] for c in SM.KIND_CELLS])
+def test_kind_cell_leaves_a_margin(orc, cell):
+    """No cell sits at the edge of its tolerance because of its own data: the oracle's uniform engine on the cell's data
+    is within half the tolerance of the float64 reference, in the norm the GPU test uses."""
+    L, s = cell["L"], cell["s"]
+    if cell in SM.NUP_CELLS:
+        h, x = SM.nup_data(orc, cell)
+        y, ref = _oracle_uniform(orc, cell, h, x), SM.reference(orc, x, h)
+    elif cell in SM.FADE_CELLS:
+        h_old, h_new, x = SM.fade_data(orc, cell)
+        y, _, _ = fade_expected(orc, L, SM.B, s, cell["C"], h_old, h_new, x, cell["t0"], SM.FADE_K, cell["in_fmt"],
+                                cell["out_fmt"])
+        ref = SM.fade_reference(orc, cell, h_old, h_new, x)
+    else:
+        rows, x = SM.matrix_data(orc, cell)
+        y, ref = matrix_reference(orc, L, SM.B, s, rows, x), SM.matrix_reference_conv(orc, rows, x)
+    err = SM.block_errors(y, ref, L)
+    assert err.max() <= 0.5 * SM.tolerance(cell, TOL), (err.max(), np.unravel_index(np.argmax(err), err.shape))
+
+
+def test_a_quiet_tail_hides_what_the_per_block_norm_shows(orc):
+    """Why the cells use flat_ir and block_errors: a last tail partition that is 0.1 % too loud moves the per-block,
+    per-channel norm with flat filters by far more than the fp32 tolerance, and conftest.rel_err with oracle.synth_ir
+    (e^-6 over the taps) on the same shape by less than it."""
+    s, L, Bh, r, Bt, Cn = 8, 64, 4, 2, 5, 3
+    taps, nb = Bh * L + Bt * r * L - SM.RAGGED, Bh + r * (Bt + 2) + 3
+    last = Bh * L + (Bt - 1) * r * L
+    rng = np.random.default_rng(11)
+
+    def moved(h, x, norm):
+        y = np.stack([SM.fft_conv(x[:, c], h[c]) for c in range(Cn)], axis=1)
+        h2 = [v.copy() for v in h]
+        for v in h2:
+            v[last:] *= 1.0 + 1e-3
+        return norm(np.stack([SM.fft_conv(x[:, c], h2[c]) for c in range(Cn)], axis=1), y)
+
+    x_flat = rng.uniform(-1.0, 1.0, (nb * L, Cn)) * SM.amplitudes(nb, L, Cn, False)
+    flat = moved(SM.flat_ir(rng, Cn, taps), x_flat, lambda y, ref: SM.block_errors(y, ref, L).max())
+    quiet = moved(orc.synth_ir(rng, Cn, taps, np.float64), orc.synth_audio(rng, nb * L, Cn, np.float64), rel_err)
+    print("last tail partition x (1 + 1e-3): flat_ir / block_errors %.3g, synth_ir / rel_err %.3g" % (flat, quiet))
+    assert flat > 1e-5 and quiet < 1e-5

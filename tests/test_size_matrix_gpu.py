@@ -30,14 +30,6 @@ def creation_log(bfir):
         print("size matrix: worst per-block error %-16s realsize %d: %.3g" % (k[0], k[1], WORST[k]))
 
 
-def _block_errors(y, ref, L):
-    """[C, n_blocks] max |y - ref| of each output block of each channel over that channel's own max |ref|."""
-    y, ref = np.asarray(y, np.float64), np.asarray(ref, np.float64)
-    nb, Cn = ref.shape[0] // L, ref.shape[1]
-    d = np.abs(y - ref).reshape(nb, L, Cn).max(axis=1).T
-    return d / np.maximum(np.abs(ref).max(axis=0), 1e-300)[:, None]
-
-
 def _frames(orc, fmt, x):
     return x.astype(orc.fmt_dtype(fmt))
 
@@ -80,7 +72,7 @@ def test_engine_size_matrix(orc, bfir, creation_log, cell):
 
     x64 = x.astype(np.float64)
     ref = np.stack([SM.reference_conv(orc, x64[:, c], h[c].astype(np.float64)) for c in range(Cn)], axis=1)
-    err = _block_errors(y, ref, L)
+    err = SM.block_errors(y, ref, L)
     key = (cell["family"], s)
     WORST[key] = max(WORST.get(key, 0.0), float(err.max()))
     assert err.max() <= tol, np.unravel_index(np.argmax(err), err.shape)
@@ -89,7 +81,7 @@ def test_engine_size_matrix(orc, bfir, creation_log, cell):
     assert o.set_coeff(h) == 0
     rc, y_orc = o.run(x)
     assert rc == 0
-    assert _block_errors(y, y_orc, L).max() <= tol
+    assert SM.block_errors(y, y_orc, L).max() <= tol
 
 
 @pytest.mark.parametrize("s,L,err", SM.REFUSALS)

@@ -1,0 +1,167 @@
+"""The size matrix for the engine kinds on top of the plain diagonal engine (tests/size_matrix.py: NUP_CELLS, FADE_CELLS,
+MATRIX_CELLS): two-level engines, crossfaded coefficient changes and matrix engines at every transform size their kernels
+have, with flat-envelope filters, odd channels at 1/8 and the per-block, per-channel norm, each against a float64 /
+long-double reference computed here from the frames and taps actually sent -- and against the oracle, as the plain sweep
+does (tests/test_size_matrix_gpu.py)."""
+import numpy as np
+import pytest
+
+import size_matrix as SM
+from conftest import TOL, env_override
+from test_fade import fade_expected
+from test_matrix import matrix_reference
+
+pytestmark = pytest.mark.gpu
+
+WORST = {}          # (family, realsize) -> worst per-block error seen against the float64 reference
+
+
+@pytest.fixture(scope="module")
+def creation_log(bfir):
+    """Lines the library logs, captured through bfir_set_log_callback (the callback object is kept alive here)."""
+    from foo_dsp_bfir_amd import _lib
+    lines = []
+    cb = _lib.LOG_FN(lambda msg: lines.append(msg.decode(errors="replace")))
+    lib = bfir.load()
+    lib.bfir_set_log_callback(cb)
+    yield lines
+    lib.bfir_set_log_callback(_lib.LOG_FN())
+    for k in sorted(WORST):
+        print("size matrix: worst per-block error %-16s realsize %d: %.3g" % (k[0], k[1], WORST[k]))
+
+
+def _check(cell, y, ref, y_orc):
+    """The per-block norm against the float64 reference (recorded in WORST), then against the oracle."""
+    L, tol = cell["L"], SM.tolerance(cell, TOL)
+    err = SM.block_errors(y, ref, L)
+    key = (cell["family"], cell["s"])
+    WORST[key] = max(WORST.get(key, 0.0), float(err.max()))
+    print("%s: worst per-block error %.3g (tol %.3g)" % (cell["id"], err.max(), tol))
+    assert err.max() <= tol, np.unravel_index(np.argmax(err), err.shape)         # (channel, block)
+    err = SM.block_errors(y, y_orc, L)
+    assert err.max() <= tol, np.unravel_index(np.argmax(err), err.shape)
+
+
+def _run_calls(eng, x, L, cuts):
+    """One run() per stretch of blocks [cuts[k], cuts[k + 1])."""
+    ys = []
+    for a, e in zip(cuts[:-1], cuts[1:]):
+        rc, y = eng.run(x[a * L:e * L])
+        assert rc == 0
+        ys.append(y)
+    return np.concatenate(ys)
+
+
+def _engine_lines(creation_log):
+    made = [ln for ln in creation_log if ln.startswith("bfir engine: ") and "two levels" not in ln]
+    return [dict(kv.split("=") for kv in ln.split(". ")[-1].split()) for ln in made]
+
+
+# ---- two-level engines -----------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cell", SM.NUP_CELLS, ids=[c["id"] for c in SM.NUP_CELLS])
+def test_nup_size_matrix(orc, bfir, creation_log, cell):
+    s, L, Cn, Bh, r, Bt = cell["s"], cell["L"], cell["C"], cell["Bh"], cell["r"], cell["Bt"]
+    D, Lt, nb = Bh * L, r * L, cell["nb"]
+    h, x = SM.nup_data(orc, cell)
+
+    with env_override(**cell["env"]):
+        del creation_log[:]
+        eng = bfir.BrutefirNup(L, Bh, r, Bt, s, Cn, cell["in_fmt"], cell["out_fmt"])
+        made = [ln for ln in creation_log if "two levels" in ln]
+        assert made == ["bfir engine: two levels, head %d x %d, tail %d x %d; back end %s." % (L, Bh, Lt, Bt, cell["back"])], \
+            creation_log
+        eng.set_chunk(3)
+        assert eng.set_coeff(h) == 0
+        # partition spectra of both levels, the ragged last tail partition included, in the grouped layout
+        for level, (Lp, Bp, lo) in enumerate(((L, Bh, 0), (Lt, Bt, D))):
+            for c in range(Cn):
+                for b in range(Bp):
+                    want = SM.grouped_spectrum(h[c][lo + b * Lp:lo + (b + 1) * Lp], Lp, 1.0)
+                    got = eng.coeff_block(level, c, b).astype(np.float64)
+                    assert np.abs(got - want).max() <= TOL[s] * np.abs(want).max(), (level, c, b)
+        # r + 1 blocks (the call ends inside a tail block), one block alone (the latency path), then the rest
+        y = _run_calls(eng, x, L, (0, r + 1, r + 2, nb))
+        eng.close()
+
+    o = orc.Engine(L, -(-cell["taps"] // L), s, Cn, cell["in_fmt"], cell["out_fmt"])
+    assert o.set_coeff(h) == 0
+    rc, y_orc = o.run(x)
+    assert rc == 0
+    o.close()
+    _check(cell, y, SM.reference(orc, x, h), y_orc)
+
+
+@pytest.mark.parametrize("s,L,r,err", SM.NUP_REFUSALS)
+def test_nup_refuses_size(bfir, s, L, r, err):
+    with pytest.raises(bfir.BfirError) as ei:
+        bfir.BrutefirNup(L, r, r, 2, s, 2)
+    assert ei.value.code == getattr(bfir, err)
+    # nothing left behind: the device still makes and runs a two-level engine of a supported size
+    dt = np.float32 if s == 4 else np.float64
+    eng = bfir.BrutefirNup(1024, 2, 2, 2, s, 2)
+    assert eng.set_coeff([np.ones(2 * 1024 + 10, dt) / 4096] * 2) == 0
+    rc, y = eng.run(np.ones((8 * 1024, 2), dt))
+    assert rc == 0 and np.all(np.isfinite(y))
+    assert abs(float(y[-1, 0]) - (2 * 1024 + 10) / 4096) <= 1e-5          # all taps under a constant input: their sum
+    eng.close()
+
+
+# ---- crossfaded coefficient changes ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("cell", SM.FADE_CELLS, ids=[c["id"] for c in SM.FADE_CELLS])
+def test_fade_size_matrix(orc, bfir, creation_log, cell):
+    s, L, Cn, t0, nb, K = cell["s"], cell["L"], cell["C"], cell["t0"], cell["nb"], SM.FADE_K
+    fused = cell["family"] == "fade_fused"
+    h_old, h_new, x = SM.fade_data(orc, cell)
+
+    with env_override(**cell["env"]):
+        del creation_log[:]
+        eng = bfir.Brutefir(L, SM.B, s, Cn, cell["in_fmt"], cell["out_fmt"])
+        made = _engine_lines(creation_log)
+        assert len(made) == 1, creation_log
+        path = made[0]["path"]
+        assert not fused or path == ("pair" if Cn % 2 == 0 else "time-pair"), made
+        eng.set_chunk(2)                     # the fade's K = 3 blocks are cut into 2 + 1: the second part starts at m0 = 2 L
+        eng.set_profiling(True)
+        assert eng.set_coeff(h_old) == 0
+        rc, y0 = eng.run(x[:t0 * L])
+        assert rc == 0
+        assert eng.set_coeff_fade(h_new, K) == 0
+        rc, y1 = eng.run(x[t0 * L:])
+        assert rc == 0 and eng.fade_remaining() == 0
+        # which back end ran: the plain chunks of these paths stage no output, the general fade does (queue_stage_out)
+        if path != "staging":
+            staged = eng.profile()["k_stage_out"][1]
+            assert (staged == 0) if fused else (staged > 0), (path, staged)
+        eng.close()
+    y = np.concatenate([y0, y1])
+
+    want, _, _ = fade_expected(orc, L, SM.B, s, Cn, h_old, h_new, x, t0, K, cell["in_fmt"], cell["out_fmt"])
+    _check(cell, y, SM.fade_reference(orc, cell, h_old, h_new, x), want)
+
+
+# ---- matrix engines --------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cell", SM.MATRIX_CELLS, ids=[c["id"] for c in SM.MATRIX_CELLS])
+def test_matrix_size_matrix(orc, bfir, creation_log, cell):
+    s, L, n_in, n_out = cell["s"], cell["L"], cell["n_in"], cell["n_out"]
+    rows, x = SM.matrix_data(orc, cell)
+    first, second = SM.MATRIX_CALLS
+
+    with env_override(**cell["env"]):
+        del creation_log[:]
+        eng = bfir.BrutefirMatrix(L, SM.B, s, n_in, n_out, cell["in_fmt"], cell["out_fmt"])
+        made = _engine_lines(creation_log)
+        assert len(made) == 1 and (made[0]["path"], made[0]["layout"]) == (cell["path"], cell["layout"]), creation_log
+        eng.set_chunk(second)
+        assert eng.set_coeff(rows) == 0
+        # every present filter's partition spectra, the ragged one included; the NULL filter's stay out of the sums
+        for o, row in enumerate(rows):
+            for i, h in enumerate(row):
+                for b in range(SM.B if h is not None else 0):
+                    want = SM.grouped_spectrum(h[b * L:(b + 1) * L], L, 1.0)
+                    got = eng.coeff_block(o, i, b).astype(np.float64)
+                    assert np.abs(got - want).max() <= TOL[s] * np.abs(want).max(), (o, i, b)
+        y = _run_calls(eng, x, L, (0, first, first + second))
+        eng.close()
+    assert y.shape == (cell["nb"] * L, n_out)
+
+    _check(cell, y, SM.matrix_reference_conv(orc, rows, x), matrix_reference(orc, L, SM.B, s, rows, x))
