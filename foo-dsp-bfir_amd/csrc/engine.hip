@@ -189,13 +189,22 @@ struct bfir_engine {
     // overlap-save output in blocks of Lt from sample 0.  Tail block j covers head blocks [j r, (j + 1) r); it is run as
     // soon as its last head block has arrived and first read by head block j r + B (causal: B >= r).  Neither level pairs
     // blocks in time and neither takes the staging path, so the bits do not depend on how the blocks arrive.
+    // A multi-level engine (bfir_engine_create_levels) is the same with up to BFIR_MAX_LEVELS - 1 tails, every one a
+    // diagonal engine with a ring of its own: tail[i] is level k = i + 1, partitions of L_k = lv_r[i] L over the taps from
+    // D_k = lv_D[i] L on; output = ((y_head + z_1[n - D_1]) + z_2[n - D_2]) + z_3[n - D_3].  Two levels are n_tail = 1.
     bool nup = false, nup_tail = false;
-    bfir_engine *tail = nullptr;
-    int r = 0;
-    bool tail_active = false;              // the filters reach past D: without, the tail does no work at all
-    bool nup_add = false;                  // the chunk being queued has a tail contribution (run_blocks cuts chunks so: all or none)
-    void *pbuf = nullptr;                  // raw input frames [Lt][C] of the tail block that is still arriving (kept across calls)
-    hipEvent_t ev_nup = nullptr;           // pbuf is filled on the caller's stream; the tail's front waits for this
+    bool levels = false;                   // created by bfir_engine_create_levels: a kind of its own at the C ABI
+    int n_tail = 0;
+    bfir_engine *tail[BFIR_MAX_LEVELS - 1] = {nullptr, nullptr, nullptr};
+    int lv_r[BFIR_MAX_LEVELS - 1] = {0, 0, 0}, lv_D[BFIR_MAX_LEVELS - 1] = {0, 0, 0};   // L_k / L and D_k / L (head blocks)
+    bool lv_active[BFIR_MAX_LEVELS - 1] = {false, false, false};   // the filters reach past D_k: without, level k does no work at all
+    int nup_mask = 0;                      // bit i: tail[i] contributes to the chunk being queued (run_blocks cuts chunks so: every block the same set)
+    // raw input frames [L_last][C] from the start of the largest level's block that is still arriving (kept across calls):
+    // head block a at (a mod lv_r[n_tail - 1]) L.  The blocks of all levels start at sample 0 and their lengths are nested
+    // powers of two, so the one buffer holds every level's partial block; frames of head blocks below pbuf_upto are there.
+    void *pbuf = nullptr;
+    long long pbuf_upto = 0;
+    hipEvent_t ev_nup = nullptr;           // pbuf is filled on the caller's stream; a tail's front waits for this
     // on the tail: its output, planar [GC][zblocks Lt] reals, tail block j in slot j % zblocks; blocks [z_from, z_next) are
     // (or will, in stream order, be) there.  zblocks >= ceil((chunk + B) / r) + 2: what one head chunk can still need
     // plus what is written ahead of it.
@@ -506,11 +515,11 @@ static bool length_supported(int filter_length, int realsize)
            ((size_t)filter_length + (size_t)filter_length / 32) * 2 * (size_t)realsize <= 160 * 1024;
 }
 
-// The tail's time ring for head chunks of up to `chunk` blocks; the blocks still to be read are carried over.
-static int alloc_zring(bfir_engine *e, int chunk)
+// The time ring of tail[i] for head chunks of up to `chunk` blocks; the blocks still to be read are carried over.
+static int alloc_zring(bfir_engine *e, int i, int chunk)
 {
-    bfir_engine *t = e->tail;
-    const int zb = (chunk + e->B + e->r - 1) / e->r + 2;
+    bfir_engine *t = e->tail[i];
+    const int zb = (chunk + e->lv_D[i] + e->lv_r[i] - 1) / e->lv_r[i] + 2;
     if (zb <= t->zblocks) return BFIR_OK;
     const size_t blk = (size_t)t->L * t->s;
     void *z = nullptr;
@@ -527,6 +536,30 @@ static int alloc_zring(bfir_engine *e, int chunk)
     }
     t->zring = z; t->zblocks = zb;
     return BFIR_OK;
+}
+
+// The head (level 0) and its tails, for arguments that have passed the checks of the two entry points below.
+static bfir_engine *create_split(int filter_length, int n_levels, const int *blocks, const int *ratios, int realsize, int channels,
+                                 int in_format, int out_format, int device, int *err)
+{
+    bfir_engine *e = engine_create(1, filter_length, blocks[0], realsize, channels, channels, false, in_format, out_format, 44100,
+                                   0, device, err, 1);
+    if (!e) return nullptr;
+    auto fail = [&](int code) { *err = code; bfir_engine_destroy(e); return (bfir_engine *)nullptr; };
+    int r = 1, D = blocks[0];
+    for (int k = 1; k < n_levels; k++) {
+        r *= ratios[k];
+        bfir_engine *t = engine_create(1, r * filter_length, blocks[k], realsize, channels, channels, false, in_format, out_format,
+                                       44100, 0, device, err, 2);
+        if (!t) return fail(*err);
+        e->tail[k - 1] = t; e->lv_r[k - 1] = r; e->lv_D[k - 1] = D; e->n_tail = k;
+        D += blocks[k] * r;
+    }
+    if (hipMalloc(&e->pbuf, (size_t)e->tail[e->n_tail - 1]->L * e->C * e->in_bytes) != hipSuccess ||
+        hipEventCreateWithFlags(&e->ev_nup, hipEventDisableTiming) != hipSuccess)
+        return fail(BFIR_ERR_HIP);
+    for (int i = 0; i < e->n_tail; i++) if (alloc_zring(e, i, e->chunk) != BFIR_OK) return fail(BFIR_ERR_HIP);
+    return e;
 }
 
 extern "C" bfir_engine *bfir_engine_create_nup(int filter_length, int head_blocks, int tail_ratio, int tail_blocks, int realsize,
@@ -549,19 +582,49 @@ extern "C" bfir_engine *bfir_engine_create_nup(int filter_length, int head_block
         return nullptr;
     // float frames only (no staging kernels, no dither)
     if (!fmt_is_native(in_format) || !fmt_is_native(out_format)) return nullptr;
-    bfir_engine *e = engine_create(1, filter_length, head_blocks, realsize, channels, channels, false, in_format, out_format, 44100,
-                                   0, device, err, 1);
+    const int blocks[2] = {head_blocks, tail_blocks}, ratios[2] = {1, tail_ratio};
+    bfir_engine *e = create_split(filter_length, 2, blocks, ratios, realsize, channels, in_format, out_format, device, err);
     if (!e) return nullptr;
-    e->r = tail_ratio;
-    e->tail = engine_create(1, tail_ratio * filter_length, tail_blocks, realsize, channels, channels, false, in_format, out_format,
-                            44100, 0, device, err, 2);
-    auto fail = [&](int code) { *err = code; bfir_engine_destroy(e); return (bfir_engine *)nullptr; };
-    if (!e->tail) return fail(*err);
-    if (hipMalloc(&e->pbuf, (size_t)e->tail->L * e->C * e->in_bytes) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_nup, hipEventDisableTiming) != hipSuccess || alloc_zring(e, e->chunk) != BFIR_OK)
-        return fail(BFIR_ERR_HIP);
-    bfir_logf("bfir engine: two levels, head %d x %d, tail %d x %d; back end %s.", e->L, e->B, e->tail->L, e->tail->B,
+    bfir_logf("bfir engine: two levels, head %d x %d, tail %d x %d; back end %s.", e->L, e->B, e->tail[0]->L, e->tail[0]->B,
               e->pair ? "fused" : "general");
+    return e;
+}
+
+extern "C" bfir_engine *bfir_engine_create_levels(int filter_length, int n_levels, const int *blocks, const int *ratios,
+                                                  int realsize, int channels, int in_format, int out_format, int device, int *err)
+{
+    int dummy;
+    if (!err) err = &dummy;
+    *err = BFIR_ERR_ARG;
+    if (channels < 1 || channels > BFIR_MAXCHANNELS) {
+        bfir_logf("Number of channels (%d) exceeds limit (%d).", channels, BFIR_MAXCHANNELS);
+        return nullptr;
+    }
+    if (realsize != 4 && realsize != 8) { bfir_logf("Invalid real size %d.", realsize); return nullptr; }
+    if (filter_length < 1 || (filter_length & (filter_length - 1))) { bfir_logf("Invalid length %d.", filter_length); return nullptr; }
+    if (n_levels < 2 || n_levels > BFIR_MAX_LEVELS || !blocks || !ratios || ratios[0] != 1) return nullptr;
+    // L_k and D_k in samples, as doubles: exact at every size a transform could have, and no overflow at any other
+    double Lk[BFIR_MAX_LEVELS], Dk = 0.0;
+    for (int k = 0; k < n_levels; k++) {
+        if (blocks[k] < 1) return nullptr;
+        if (k > 0 && (ratios[k] < 2 || (ratios[k] & (ratios[k] - 1)))) return nullptr;
+        Lk[k] = k == 0 ? (double)filter_length : Lk[k - 1] * ratios[k];
+        // a block of level k is first read D_k samples after it began: it must be complete by then
+        if (k > 0 && Dk < Lk[k]) return nullptr;
+        Dk += blocks[k] * Lk[k];
+    }
+    *err = BFIR_ERR_UNSUPPORTED;
+    for (int k = 0; k < n_levels; k++)
+        if (Lk[k] > 16384.0 || !length_supported((int)Lk[k], realsize)) return nullptr;
+    // float frames only (no staging kernels, no dither)
+    if (!fmt_is_native(in_format) || !fmt_is_native(out_format)) return nullptr;
+    bfir_engine *e = create_split(filter_length, n_levels, blocks, ratios, realsize, channels, in_format, out_format, device, err);
+    if (!e) return nullptr;
+    e->levels = true;
+    char desc[160];
+    int n = snprintf(desc, sizeof(desc), "%d x %d", e->L, e->B);
+    for (int i = 0; i < e->n_tail; i++) n += snprintf(desc + n, sizeof(desc) - n, ", %d x %d", e->tail[i]->L, e->tail[i]->B);
+    bfir_logf("bfir engine: %d levels, %s; back end %s.", n_levels, desc, e->pair ? "fused" : "general");
     return e;
 }
 
@@ -570,7 +633,7 @@ extern "C" void bfir_engine_destroy(bfir_engine *e)
     if (!e) return;
     (void)hipSetDevice(e->device);
     (void)hipDeviceSynchronize();
-    if (e->tail) bfir_engine_destroy(e->tail);
+    for (bfir_engine *t : e->tail) if (t) bfir_engine_destroy(t);
     if (e->pbuf) (void)hipFree(e->pbuf);
     if (e->zring) (void)hipFree(e->zring);
     if (e->ev_nup) (void)hipEventDestroy(e->ev_nup);
@@ -689,53 +752,76 @@ extern "C" int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, 
     return bfir_engine_set_coeff_at(e, 0, coeffs, n_coeffs, length, coeff_blocks, scale);
 }
 
-// The filters of a two-level engine, split at D = B L: taps [0, D) to the head, the rest to the tail.  Mid-stream both
-// delay lines are kept: the head takes the new filters from the next block, the tail from the next tail block that
-// completes; what the tail has already put into its time ring still plays.
-extern "C" int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
+// The filters of a two-level or multi-level engine, split at every D_k: taps [0, D_1) to the head, [D_k, D_(k+1)) to level
+// k.  Mid-stream every delay line is kept: the head takes the new filters from the next block, level k from its next
+// block that completes; what a level has already put into its time ring still plays.
+static int set_coeff_split(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
 {
-    if (!e) return BFIR_ERR_ARG;
-    if (!e->nup) return BFIR_ERR_UNSUPPORTED;
-    bfir_engine *t = e->tail;
-    const long long D = (long long)e->B * e->L;
-    if (!coeffs || n_coeffs < 0 || length < 0 || (long long)length > D + (long long)t->B * t->L) return BFIR_ERR_ARG;
+    long long cap = (long long)e->B * e->L;
+    for (int i = 0; i < e->n_tail; i++) cap += (long long)e->tail[i]->B * e->tail[i]->L;
+    if (!coeffs || n_coeffs < 0 || length < 0 || (long long)length > cap) return BFIR_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     e->eng_init[0] = 0;
     if (n_coeffs > e->C) n_coeffs = e->C;
-    const int len_h = (int)std::min<long long>(length, D), len_t = length - len_h;
+    const int len_h = (int)std::min<long long>(length, (long long)e->B * e->L);
     const int nb_h = std::min(e->B, std::max(1, (len_h + e->L - 1) / e->L));
     int rc = load_filters(e, e->H, 0, e->C, coeffs, n_coeffs, len_h, nb_h, scale, false);
     if (rc != BFIR_OK) return rc;
-    const int nb_t = len_t > 0 ? std::min(t->B, (len_t + t->L - 1) / t->L) : 0;
-    if (len_t > 0) {
-        std::vector<const void *> rest((size_t)n_coeffs);
-        for (int n = 0; n < n_coeffs; n++) rest[n] = (const char *)coeffs[n] + (size_t)D * e->s;
-        rc = load_filters(t, t->H, 0, t->C, rest.data(), n_coeffs, len_t, nb_t, scale, false);
-        if (rc != BFIR_OK) return rc;
+    int len_lv[BFIR_MAX_LEVELS - 1], nb_lv[BFIR_MAX_LEVELS - 1];
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        const long long D = (long long)e->lv_D[i] * e->L;
+        const int len_t = len_lv[i] = (int)std::max(0ll, std::min((long long)length - D, (long long)t->B * t->L));
+        nb_lv[i] = len_t > 0 ? std::min(t->B, (len_t + t->L - 1) / t->L) : 0;
+        if (len_t > 0) {
+            std::vector<const void *> rest((size_t)n_coeffs);
+            for (int n = 0; n < n_coeffs; n++) rest[n] = (const char *)coeffs[n] + (size_t)D * e->s;
+            rc = load_filters(t, t->H, 0, t->C, rest.data(), n_coeffs, len_t, nb_lv[i], scale, false);
+            if (rc != BFIR_OK) return rc;
+        }
     }
-    for (int n = 0; n < e->C; n++) { e->nblk[n] = nb_h; t->nblk[n] = nb_t; }
+    for (int n = 0; n < e->C; n++) e->nblk[n] = nb_h;
     HIP_TRY(hipMemcpy(e->d_nblk, e->nblk.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(t->d_nblk, t->nblk.data(), sizeof(int) * t->C, hipMemcpyHostToDevice));
-    if (len_t > 0 && !e->tail_active) {
-        // The tail starts (again) with the next tail block that begins: its signal state is cleared, the blocks it did
-        // not compute read as zero, and its first Bt blocks lack the input from before (a transient like the one of a new
-        // engine).  Output queued before it stopped is still in the ring.
-        const size_t blk = (size_t)t->L * t->s;
-        const long long j0 = (long long)((e->blockcounter + e->r - 1) / e->r);
-        HIP_TRY(hipMemset(t->X, 0, (size_t)t->GC * t->ring * cbuf_bytes(t)));
-        for (int st = 0; st < 2; st++) for (int i = 0; i < 2; i++) HIP_TRY(hipMemset(t->tails[st][i], 0, (size_t)t->L * t->C * t->in_bytes));
-        const long long oldest = std::max(0ll, ((long long)e->blockcounter - e->B) / e->r);   // the oldest tail block still to be read
-        if (t->z_next <= oldest || t->z_next == t->z_from) t->z_from = j0;
-        else for (long long j = t->z_next; j < j0; j++)   // fewer than B / r + 2 <= zblocks of them
-            HIP_TRY(hipMemset2D((char *)t->zring + (size_t)(j % t->zblocks) * blk, (size_t)t->zblocks * blk, 0, blk, t->GC));
-        t->z_next = j0;
-        t->blockcounter = 0; t->curbuf = 0;
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        const int r = e->lv_r[i];
+        for (int n = 0; n < e->C; n++) t->nblk[n] = nb_lv[i];
+        HIP_TRY(hipMemcpy(t->d_nblk, t->nblk.data(), sizeof(int) * t->C, hipMemcpyHostToDevice));
+        if (len_lv[i] > 0 && !e->lv_active[i]) {
+            // The level starts (again) with its next block that begins: its signal state is cleared, the blocks it did
+            // not compute read as zero, and its first blocks lack the input from before (a transient like the one of a new
+            // engine).  Output queued before it stopped is still in the ring.
+            const size_t blk = (size_t)t->L * t->s;
+            const long long j0 = (long long)((e->blockcounter + r - 1) / r);
+            HIP_TRY(hipMemset(t->X, 0, (size_t)t->GC * t->ring * cbuf_bytes(t)));
+            for (int st = 0; st < 2; st++) for (int h = 0; h < 2; h++) HIP_TRY(hipMemset(t->tails[st][h], 0, (size_t)t->L * t->C * t->in_bytes));
+            const long long oldest = std::max(0ll, ((long long)e->blockcounter - e->lv_D[i]) / r);   // the oldest block of the level still to be read
+            if (t->z_next <= oldest || t->z_next == t->z_from) t->z_from = j0;
+            else for (long long j = t->z_next; j < j0; j++)   // fewer than D_k / L_k + 2 <= zblocks of them
+                HIP_TRY(hipMemset2D((char *)t->zring + (size_t)(j % t->zblocks) * blk, (size_t)t->zblocks * blk, 0, blk, t->GC));
+            t->z_next = j0;
+            t->blockcounter = 0; t->curbuf = 0;
+        }
+        e->lv_active[i] = len_lv[i] > 0;
+        t->eng_init[0] = 1;
     }
-    e->tail_active = len_t > 0;
-    t->eng_init[0] = 1;
     e->eng_init[0] = 1;
     return BFIR_OK;
+}
+
+extern "C" int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->nup || e->levels) return BFIR_ERR_UNSUPPORTED;
+    return set_coeff_split(e, coeffs, n_coeffs, length, scale);
+}
+
+extern "C" int bfir_engine_set_coeff_levels(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->levels) return BFIR_ERR_UNSUPPORTED;
+    return set_coeff_split(e, coeffs, n_coeffs, length, scale);
 }
 
 // does every input of a matrix engine feed some output under these partition counts ([o C + i])?
@@ -891,9 +977,19 @@ extern "C" int bfir_engine_read_coeff(bfir_engine *e, int channel, int block, vo
 extern "C" int bfir_engine_read_coeff_nup(bfir_engine *e, int level, int channel, int block, void *dst)
 {
     if (!e) return BFIR_ERR_ARG;
-    if (!e->nup) return BFIR_ERR_UNSUPPORTED;
+    if (!e->nup || e->levels) return BFIR_ERR_UNSUPPORTED;
     if (level < 0 || level > 1 || !dst) return BFIR_ERR_ARG;
-    bfir_engine *lv = level ? e->tail : e;
+    bfir_engine *lv = level ? e->tail[0] : e;
+    if (channel < 0 || channel >= lv->GC || block < 0 || block >= lv->B) return BFIR_ERR_ARG;
+    return read_spectrum(lv, channel, block, dst);
+}
+
+extern "C" int bfir_engine_read_coeff_levels(bfir_engine *e, int level, int channel, int block, void *dst)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->levels) return BFIR_ERR_UNSUPPORTED;
+    if (level < 0 || level > e->n_tail || !dst) return BFIR_ERR_ARG;
+    bfir_engine *lv = level ? e->tail[level - 1] : e;
     if (channel < 0 || channel >= lv->GC || block < 0 || block >= lv->B) return BFIR_ERR_ARG;
     return read_spectrum(lv, channel, block, dst);
 }
@@ -950,7 +1046,7 @@ static void drain_spans(bfir_engine *e)
 extern "C" int bfir_engine_set_profiling(bfir_engine *e, int enable)
 {
     if (!e) return BFIR_ERR_ARG;
-    if (e->tail) (void)bfir_engine_set_profiling(e->tail, enable);   // a two-level engine reports the sum of its levels
+    for (bfir_engine *t : e->tail) if (t) (void)bfir_engine_set_profiling(t, enable);   // a two- or multi-level engine reports the sum of its levels
     drain_spans(e);
     e->profiling = enable != 0;
     if (e->profiling && e->ev_pool.size() < 4096) {   // keep event creation out of timed regions
@@ -964,9 +1060,12 @@ extern "C" int bfir_engine_get_profile(bfir_engine *e, int kernel, double *total
 {
     if (!e || kernel < 0 || kernel >= BFIR_K_COUNT) return BFIR_ERR_ARG;
     drain_spans(e);
-    if (e->tail) drain_spans(e->tail);
-    if (total_ms) *total_ms = e->prof_ms[kernel] + (e->tail ? e->tail->prof_ms[kernel] : 0.0);
-    if (launches) *launches = e->prof_n[kernel] + (e->tail ? e->tail->prof_n[kernel] : 0);
+    double ms = e->prof_ms[kernel];
+    int64_t n = e->prof_n[kernel];
+    for (bfir_engine *t : e->tail)
+        if (t) { drain_spans(t); ms += t->prof_ms[kernel]; n += t->prof_n[kernel]; }
+    if (total_ms) *total_ms = ms;
+    if (launches) *launches = n;
     return BFIR_OK;
 }
 
@@ -1213,24 +1312,43 @@ static void queue_inv_tail(bfir_engine *e, const Chunk &c, hipStream_t st)
     e->z_next += c.tc;
 }
 
-// The back end of a head chunk whose blocks all have a tail contribution: Y and the tail's time ring -> output frames.
+// The back end of a head chunk whose blocks all have the contributions of the tails in nup_mask: Y and their time rings
+// -> output frames.  One ring takes the two-level kernels (nup.hip), two or three take those of levels.hip.
 static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
 {
-    const bfir_engine *t = e->tail;
-    const long zlen = (long)t->zblocks * t->L;
-    const long long m0 = ((long long)e->blockcounter - e->B) * e->L, m_min = t->z_from * (long long)t->L;
-    const long m0r = (long)(((m0 % zlen) + zlen) % zlen);
+    LevelRing ring[BFIR_LEVEL_RINGS];
+    int nr = 0;
+    for (int i = 0; i < e->n_tail; i++) {
+        if (!(e->nup_mask >> i & 1)) continue;
+        const bfir_engine *t = e->tail[i];
+        LevelRing &g = ring[nr++];
+        g.z = t->zring; g.zlen = g.z_ch_stride = (long)t->zblocks * t->L;
+        g.m0 = ((long long)e->blockcounter - e->lv_D[i]) * e->L; g.m_min = t->z_from * (long long)t->L;
+        g.m0r = (long)(((g.m0 % g.zlen) + g.zlen) % g.zlen);
+    }
     if (e->pair) {   // one inverse per channel pair and block, the sum, statistics and frame store in one kernel
         ProfScope ps(e, BFIR_K_INV, st);
-        NupInvArgs a;
-        a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
-        a.z = (const float *)t->zring; a.z_ch_stride = zlen; a.zlen = zlen;
-        a.m0 = m0; a.m_min = m_min; a.m0r = m0r;
-        a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
-        a.n_ch = e->C; a.n_t = c.tc;
-        a.scale = (float)e->out_scale; a.max = (float)e->of_max;
-        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
-        launch_inv_nup(e->plan2, a, st);
+        if (nr == 1) {
+            NupInvArgs a;
+            a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
+            a.z = (const float *)ring[0].z; a.z_ch_stride = ring[0].z_ch_stride; a.zlen = ring[0].zlen;
+            a.m0 = ring[0].m0; a.m_min = ring[0].m_min; a.m0r = ring[0].m0r;
+            a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
+            a.n_ch = e->C; a.n_t = c.tc;
+            a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+            a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+            launch_inv_nup(e->plan2, a, st);
+        } else {
+            LevelsInvArgs a;
+            a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
+            for (int k = 0; k < BFIR_LEVEL_RINGS; k++) a.ring[k] = ring[k < nr ? k : 0];
+            a.n_rings = nr;
+            a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
+            a.n_ch = e->C; a.n_t = c.tc;
+            a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+            a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+            launch_inv_levels(e->plan2, a, st);
+        }
         return;
     }
     // the general form: a planar inverse into tout, the sum, then the staging path's output kernel
@@ -1242,12 +1360,21 @@ static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
         a.n_t = c.tc; a.n_ch = e->GC;
         a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
         launch_inv(e->plan, a, st);
-        NupCombineArgs b;
-        b.y = e->tout; b.y_ch_stride = t_stride;
-        b.z = t->zring; b.z_ch_stride = zlen; b.zlen = zlen;
-        b.m0 = m0; b.m_min = m_min; b.m0r = m0r;
-        b.n_ch = e->GC; b.n = (long)c.tc * e->L; b.realsize = e->s;
-        launch_nup_combine(b, st);
+        if (nr == 1) {
+            NupCombineArgs b;
+            b.y = e->tout; b.y_ch_stride = t_stride;
+            b.z = ring[0].z; b.z_ch_stride = ring[0].z_ch_stride; b.zlen = ring[0].zlen;
+            b.m0 = ring[0].m0; b.m_min = ring[0].m_min; b.m0r = ring[0].m0r;
+            b.n_ch = e->GC; b.n = (long)c.tc * e->L; b.realsize = e->s;
+            launch_nup_combine(b, st);
+        } else {
+            LevelsCombineArgs b;
+            b.y = e->tout; b.y_ch_stride = t_stride;
+            for (int k = 0; k < BFIR_LEVEL_RINGS; k++) b.ring[k] = ring[k < nr ? k : 0];
+            b.n_rings = nr;
+            b.n_ch = e->GC; b.n = (long)c.tc * e->L; b.realsize = e->s;
+            launch_levels_combine(b, st);
+        }
     }
     queue_stage_out(e, c, e->tout, t_stride, st);
 }
@@ -1321,7 +1448,7 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     }
     if (c.fade) queue_inv_fade(e, c, st);
     else if (e->nup_tail) queue_inv_tail(e, c, st);
-    else if (e->nup_add) queue_inv_nup(e, c, st);
+    else if (e->nup_mask) queue_inv_nup(e, c, st);
     else queue_inv(e, p, c, st);
     if (e->pipe3 && !il) HIP_TRY(hipEventRecord(e->ev_inv[par], st));
     if (p == Path::Staging) {
@@ -1360,31 +1487,48 @@ static int ensure_fade_buffers(bfir_engine *e)
     return BFIR_OK;
 }
 
-// Two-level engines, ahead of head chunk [a0, a0 + *tc) (a0 = blockcounter): run every tail block that is complete with
-// head block a0 + *tc - 1 and not yet run, then cut the chunk so that its blocks all have a tail contribution or none
-// (nup_add).  A tail block that lies wholly in this call's buffer is transformed straight from the caller's frames --
-// neighbours in one launch -- and the one that began in an earlier call from pbuf, where nup_keep_partial put its first
-// frames; all of a call's input is there when the call is made, so chunks need not be cut at multiples of r.  The
-// tail's front and MAC run on the tail's own streams, its inverse on st: stream order keeps the ring's writes ahead of
-// this chunk's back end and behind the reads of the chunks before.
+// The frames of head blocks [lo, hi) of this call (the head block at frame_off is call0) -> pbuf, but for those that
+// this call has put there already.  [lo, hi) lies in one block of the largest level.
+static int nup_keep(bfir_engine *e, const void *d_in, long frame_off, long long call0, long long lo, long long hi, hipStream_t st,
+                    hipEvent_t input_ready)
+{
+    lo = std::max(lo, std::max(call0, e->pbuf_upto));
+    if (lo >= hi) return BFIR_OK;
+    const size_t fb = (size_t)e->C * e->in_bytes;   // bytes per input frame
+    if (!e->inline_launch && input_ready) HIP_TRY(hipStreamWaitEvent(st, input_ready, 0));
+    HIP_TRY(hipMemcpyAsync((char *)e->pbuf + (size_t)(lo % e->lv_r[e->n_tail - 1]) * e->L * fb,
+                           (const char *)d_in + ((size_t)frame_off + (size_t)(lo - call0) * e->L) * fb, (size_t)(hi - lo) * e->L * fb,
+                           hipMemcpyDefault, st));
+    e->pbuf_upto = hi;
+    return BFIR_OK;
+}
+
+// Two- and multi-level engines, ahead of head chunk [a0, a0 + *tc) (a0 = blockcounter): run, level after level, every
+// block of the level that is complete with head block a0 + *tc - 1 and not yet run, then cut the chunk so that its blocks
+// all have the same set of contributing levels (nup_mask).  A block that lies wholly in this call's buffer is transformed
+// straight from the caller's frames -- neighbours in one launch -- and the one that began in an earlier call from pbuf,
+// where nup_keep_partial put its first frames; all of a call's input is there when the call is made, so chunks need not
+// be cut at multiples of any r.  A tail's front and MAC run on the tail's own streams, its inverse on st: stream order keeps
+// every ring's writes ahead of this chunk's back end and behind the reads of the chunks before.
 static int nup_tail_ahead(bfir_engine *e, const void *d_in, long frame_off, long long call0, int *tc, hipStream_t st,
                           hipEvent_t input_ready)
 {
-    bfir_engine *t = e->tail;
-    const int r = e->r;
     const long long a0 = (long long)e->blockcounter, a1 = a0 + *tc;
     const size_t fb = (size_t)e->C * e->in_bytes;   // bytes per input frame
-    t->inline_launch = e->inline_launch;
-    if (e->tail_active) {
+    const int r_last = e->lv_r[e->n_tail - 1];
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        const int r = e->lv_r[i];
+        t->inline_launch = e->inline_launch;
+        if (!e->lv_active[i]) continue;
         for (const long long j_end = a1 / r; t->z_next < j_end;) {
             const long long j = t->z_next;
             if (j * r < call0) {   // began before this call: the rest of its frames join the ones kept in pbuf
-                const long long have = call0 - j * r;
-                if (!e->inline_launch && input_ready) HIP_TRY(hipStreamWaitEvent(st, input_ready, 0));
-                HIP_TRY(hipMemcpyAsync((char *)e->pbuf + (size_t)have * e->L * fb, (const char *)d_in + (size_t)frame_off * fb,
-                                       (size_t)(r - have) * e->L * fb, hipMemcpyDefault, st));
+                int rc = nup_keep(e, d_in, frame_off, call0, j * r, (j + 1) * r, st, input_ready);
+                if (rc != BFIR_OK) return rc;
                 if (!e->inline_launch) HIP_TRY(hipEventRecord(e->ev_nup, st));
-                const int rc = run_chunk(t, e->pbuf, 0, nullptr, 0, 0, 1, 0, st, e->inline_launch ? nullptr : e->ev_nup);
+                rc = run_chunk(t, (const char *)e->pbuf + (size_t)((j * r) % r_last) * e->L * fb, 0, nullptr, 0, 0, 1, 0, st,
+                               e->inline_launch ? nullptr : e->ev_nup);
                 if (rc != BFIR_OK) return rc;
             } else {
                 const int nt = (int)std::min<long long>(j_end - j, t->chunk);
@@ -1393,29 +1537,33 @@ static int nup_tail_ahead(bfir_engine *e, const void *d_in, long frame_off, long
             }
         }
     }
-    // head block a reads tail block (a - B) / r: there from z_from on, and (a stopped tail) up to z_next
-    auto adds = [&](long long a) { return a >= e->B && (a - e->B) / r >= t->z_from && (a - e->B) / r < t->z_next; };
-    e->nup_add = adds(a0);
+    // head block a reads block (a - D_k / L) / r of level k: there from z_from on, and (a stopped level) up to z_next
+    auto mask = [&](long long a) {
+        int m = 0;
+        for (int i = 0; i < e->n_tail; i++) {
+            const bfir_engine *t = e->tail[i];
+            const long long d = a - e->lv_D[i];
+            if (d >= 0 && d / e->lv_r[i] >= t->z_from && d / e->lv_r[i] < t->z_next) m |= 1 << i;
+        }
+        return m;
+    };
+    e->nup_mask = mask(a0);
     int same = 1;
-    while (same < *tc && adds(a0 + same) == e->nup_add) same++;
+    while (same < *tc && mask(a0 + same) == e->nup_mask) same++;
     *tc = same;
     return BFIR_OK;
 }
 
-// ... and at the end of a call: the frames of the tail block that is still arriving go to pbuf, because the caller's
-// buffer is gone when the rest of it comes.
+// ... and at the end of a call: the frames of the blocks that are still arriving go to pbuf, because the caller's
+// buffer is gone when the rest of them comes.
 static int nup_keep_partial(bfir_engine *e, const void *d_in, long frame_off, long long call0, int n, hipStream_t st,
                             hipEvent_t input_ready)
 {
-    const bfir_engine *t = e->tail;
-    const long long lo = std::max(t->z_next * e->r, call0), hi = call0 + n;
-    if (lo >= hi) return BFIR_OK;
-    const size_t fb = (size_t)e->C * e->in_bytes;
-    if (!e->inline_launch && input_ready) HIP_TRY(hipStreamWaitEvent(st, input_ready, 0));
-    HIP_TRY(hipMemcpyAsync((char *)e->pbuf + (size_t)(lo - t->z_next * e->r) * e->L * fb,
-                           (const char *)d_in + ((size_t)frame_off + (size_t)(lo - call0) * e->L) * fb, (size_t)(hi - lo) * e->L * fb,
-                           hipMemcpyDefault, st));
-    return BFIR_OK;
+    const long long hi = call0 + n;
+    long long lo = hi;
+    for (int i = 0; i < e->n_tail; i++)
+        if (e->lv_active[i]) lo = std::min(lo, e->tail[i]->z_next * e->lv_r[i]);
+    return nup_keep(e, d_in, frame_off, call0, lo, hi, st, input_ready);
 }
 
 // n blocks of the caller's buffers (from frame frame_off, block block_base of the call), cut into chunks of at most
@@ -1441,7 +1589,7 @@ static int run_blocks(bfir_engine *e, const void *d_in, long in_stride, void *d_
         if (rc != BFIR_OK) return rc;
         c0 += tc;
     }
-    if (e->nup && e->tail_active) return nup_keep_partial(e, d_in, frame_off, call0, n, st, input_ready);
+    if (e->nup) return nup_keep_partial(e, d_in, frame_off, call0, n, st, input_ready);
     return BFIR_OK;
 }
 
@@ -1475,10 +1623,14 @@ static int ensure_chunk(bfir_engine *e, int n_blocks)
     if (want > e->chunk) {
         const int rc = alloc_work(e, want);
         if (rc != BFIR_OK || !e->nup) return rc;
-        // the tail's launches take the tail blocks of one head chunk; its ring what that chunk can still need
-        const int tw = (want + e->r - 1) / e->r;
-        if (tw > e->tail->chunk) { const int rc2 = alloc_work(e->tail, tw); if (rc2 != BFIR_OK) return rc2; }
-        return alloc_zring(e, want);
+        // a tail's launches take its blocks of one head chunk; its ring what that chunk can still need
+        for (int i = 0; i < e->n_tail; i++) {
+            const int tw = (want + e->lv_r[i] - 1) / e->lv_r[i];
+            if (tw > e->tail[i]->chunk) { const int rc2 = alloc_work(e->tail[i], tw); if (rc2 != BFIR_OK) return rc2; }
+            const int rc3 = alloc_zring(e, i, want);
+            if (rc3 != BFIR_OK) return rc3;
+        }
+        return BFIR_OK;
     }
     return BFIR_OK;
 }
@@ -1713,20 +1865,22 @@ extern "C" int bfir_engine_run(bfir_engine *e, const void *inbuf, void *outbuf, 
     return bfir_engine_sync(e);
 }
 
-// A two-level engine forgets all signal state -- both delay lines, both time histories, the tail's partial input block and
-// its queued output -- and zeroes the counters: it then behaves as newly created with the same coefficients.  (The plain
-// engine keeps input_timecbuf, a quirk of the reference that has no two-level meaning.)
+// A two- or multi-level engine forgets all signal state -- every delay line, every time history, the partial input blocks
+// and every level's queued output -- and zeroes the counters: it then behaves as newly created with the same coefficients.
+// (The plain engine keeps input_timecbuf, a quirk of the reference that has no meaning here.)
 static void nup_reset(bfir_engine *e)
 {
     (void)hipDeviceSynchronize();
-    bfir_engine *lv[2] = {e, e->tail};
+    bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
     for (bfir_engine *l : lv) {
+        if (!l) continue;
         (void)hipMemset(l->X, 0, (size_t)l->GC * l->ring * cbuf_bytes(l));
         for (int st = 0; st < 2; st++)
             for (int i = 0; i < 2; i++) (void)hipMemset(l->tails[st][i], 0, (size_t)l->L * l->C * l->in_bytes);
         l->blockcounter = 0; l->curbuf = 0;
+        l->z_from = l->z_next = 0;
     }
-    e->tail->z_from = e->tail->z_next = 0;
+    e->pbuf_upto = 0;
     (void)hipMemset(e->d_of, 0, sizeof(DevOverflow) * e->GCo * BFIR_OF_SHARDS);
     (void)hipDeviceSynchronize();
 }

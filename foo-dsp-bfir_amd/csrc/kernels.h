@@ -291,6 +291,38 @@ struct NupCombineArgs {
 };
 void launch_nup_combine(const NupCombineArgs &a, hipStream_t s);
 
+// levels.hip: the back end of a multi-level engine (bfir_engine_create_levels) for a chunk to which two or three tail
+// levels contribute (one: the two-level back end above).  Every contributing level has left its time output in a ring of
+// its own, described as in NupInvArgs; sample n of block t is  ((y_head[n] + z_0[m_0]) + z_1[m_1]) + z_2[m_2],
+// m_r = ring[r].m0 + t L + n, the rings in level order, nothing added from a ring where m_r < ring[r].m_min.  Each m0,
+// m_min and zlen is a multiple of L, so a block's L samples of a ring are contiguous: the rings wrap between blocks only.
+constexpr int BFIR_LEVEL_RINGS = 3;
+struct LevelRing {
+    const void *z; long z_ch_stride; long zlen;          // planar [n_ch][zlen] reals of working precision
+    long long m0, m_min; long m0r;                       // m0r = m0 mod zlen
+};
+// k_inv_levels, the fused form: as k_inv_nup (fp32, (re, im) pairs, FLOAT_LE frames, even n_ch, 512 <= L <= 8192; `plan` is
+// the plan of 2L points) with n_rings = 2 or 3 additions per sample.
+struct LevelsInvArgs {
+    const float *y; long y_ch_stride;                    // [n_ch][..][N] product spectra, (re, im) pairs
+    LevelRing ring[BFIR_LEVEL_RINGS]; int n_rings;
+    float *raw; long frame_off;                          // output frames of ONE engine, n_ch channels wide
+    int n_ch, n_t;
+    float scale, max;
+    DevOverflow *overflow; long of_shard_stride;
+    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+};
+void launch_inv_levels(const FftPlan &plan, const LevelsInvArgs &a, hipStream_t s);
+// k_levels_combine, the general form's middle step: y[c][i] <- y[c][i] + z_0 + z_1 (+ z_2) on a planar time buffer
+// [n_ch][..] (i < n: the chunk's n_t L samples of a channel) in one pass; launch_inv fills it, launch_stage_out follows.
+struct LevelsCombineArgs {
+    void *y; long y_ch_stride;                           // in reals
+    LevelRing ring[BFIR_LEVEL_RINGS]; int n_rings;
+    int n_ch; long n;
+    int realsize;
+};
+void launch_levels_combine(const LevelsCombineArgs &a, hipStream_t s);
+
 // mixnscale with one buffer (a7 / a11) on half-complex data, for the stage API.
 void launch_reorder(const void *in, void *out, int n_fft, double scale, int to_grouped, int realsize,
                     hipStream_t s);

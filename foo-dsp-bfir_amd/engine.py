@@ -315,3 +315,57 @@ class BrutefirNup(Brutefir):
         if rc != 0:
             raise BfirError(rc, "bfir_engine_read_coeff_nup")
         return dst
+
+
+class BrutefirLevels(Brutefir):
+    """Three or four partition lengths in one engine (bfir_engine_create_levels): level k has blocks[k] partitions of
+    L_k = ratios[k] * L_(k-1) (L_0 = filter_length, ratios[0] = 1, the others powers of two >= 2) and convolves taps
+    [D[k], D[k + 1]), D[0] = 0 and D[k + 1] = D[k] + blocks[k] * L_k; D[k] >= L_k for k >= 1.  Same convolution, same zero
+    latency and the same filter_length-frame blocks as Brutefir(filter_length, ceil(taps / filter_length), ...), with
+    sum(blocks) partitions of MAC work per sample instead.  Two levels are allowed and give BrutefirNup's bytes.
+    Frames are FLOAT_LE or FLOAT64_LE; the default is the working precision's.
+
+    run / run_device / sync / reset / overflow / check_overflows / set_chunk / set_profiling / profile / close are
+    Brutefir's; reset() discards all signal state of all levels."""
+
+    def __init__(self, filter_length, blocks, ratios, realsize, channels, in_format=None, out_format=None, device=0):
+        dflt = SAMPLE_FORMAT_FLOAT_LE if realsize == 4 else SAMPLE_FORMAT_FLOAT64_LE
+        blocks, ratios = [int(b) for b in blocks], [int(r) for r in ratios]
+        assert len(blocks) == len(ratios)
+        self.L, self.B, self.s, self.C = filter_length, blocks[0] if blocks else 0, realsize, channels
+        self.blocks, self.ratios = tuple(blocks), tuple(ratios)
+        self.lengths, self.D = [], [0]
+        for b, r in zip(blocks, ratios):
+            self.lengths.append(filter_length if not self.lengths else self.lengths[-1] * r)
+            self.D.append(self.D[-1] + b * self.lengths[-1])
+        self.max_taps = self.D.pop()
+        self.in_format = dflt if in_format is None else in_format
+        self.out_format = dflt if out_format is None else out_format
+        self.n_engines, self.device = 1, device
+        self._lib = _lib.load()
+        err = C.c_int(0)
+        n = len(blocks)
+        self._h = self._lib.bfir_engine_create_levels(filter_length, n, (C.c_int * n)(*blocks), (C.c_int * n)(*ratios), realsize,
+                                                      channels, self.in_format, self.out_format, device, C.byref(err))
+        if not self._h:
+            raise BfirError(err.value, "bfir_engine_create_levels")
+
+    def set_coeff(self, coeffs, scale=1.0):
+        """coeffs[c]: the taps of channel c, at most max_taps of them; split at every D[k] between the levels.
+        Returns 0 or an ERR_* code (ERR_COEFF: a NaN / Inf tap, the engine is uninitialised)."""
+        rd = _real_dtype(self.s)
+        arrs = [np.ascontiguousarray(c, dtype=rd) for c in coeffs]
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return self._lib.bfir_engine_set_coeff_levels(self._h, ptrs, len(arrs), arrs[0].size, float(scale))
+
+    def set_coeff_fade(self, *args, **kwargs):
+        raise BfirError(_lib.ERR_UNSUPPORTED, "bfir_engine_set_coeff_fade")
+
+    def coeff_block(self, level, channel, block):
+        """Partition spectrum `block` of `channel` on `level`: 2 L_level reals."""
+        n = 2 * self.lengths[level] if 0 <= level < len(self.lengths) else 2 * self.L
+        dst = np.zeros(n, dtype=_real_dtype(self.s))
+        rc = self._lib.bfir_engine_read_coeff_levels(self._h, level, channel, block, dst.ctypes.data)
+        if rc != 0:
+            raise BfirError(rc, "bfir_engine_read_coeff_levels")
+        return dst

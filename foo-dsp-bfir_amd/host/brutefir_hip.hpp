@@ -36,6 +36,18 @@ public:
         m_err = err;
         memset(m_last, 0, sizeof(m_last));
     }
+    // Three or four partition lengths (bfir_engine_create_levels): level k has blocks[k] partitions of ratios[k] times the
+    // length of level k - 1 (ratios[0] = 1).  Coefficients: set_coeff_levels(coeffs, n_coeffs, length, scale).
+    struct multi_level { int n_levels; int blocks[BFIR_MAX_LEVELS]; int ratios[BFIR_MAX_LEVELS]; };
+    brutefir(int filter_length, const multi_level &levels, int realsize, int channels, int in_format, int out_format, int device = 0)
+        : m_channels(channels)
+    {
+        int err = 0;
+        m_e = bfir_engine_create_levels(filter_length, levels.n_levels, levels.blocks, levels.ratios, realsize, channels, in_format,
+                                        out_format, device, &err);
+        m_err = err;
+        memset(m_last, 0, sizeof(m_last));
+    }
     ~brutefir() { bfir_engine_destroy(m_e); }
     brutefir(const brutefir &) = delete;
     brutefir &operator=(const brutefir &) = delete;
@@ -69,6 +81,13 @@ public:
     {
         if (!m_e) return -1;
         return bfir_engine_set_coeff_nup(m_e, (const void *const *)coeffs, n_coeffs, length, scale);
+    }
+
+    // A multi-level engine's filters: `length` taps per channel, split between the levels (bfir_engine_set_coeff_levels).
+    int set_coeff_levels(void **coeffs, int n_coeffs, int length, double scale)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_levels(m_e, (const void *const *)coeffs, n_coeffs, length, scale);
     }
 
     // brutefir.cpp:244-343: one block of filter_length interleaved frames; 0 or -1.

@@ -161,6 +161,36 @@ int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_c
 /* partition spectrum `block` of `channel`: level 0 = head (2 L reals), 1 = tail (2 tail_ratio L reals); grouped layout */
 int bfir_engine_read_coeff_nup(bfir_engine *e, int level, int channel, int block, void *dst);
 
+/* Three or four partition lengths in one engine: the two-level engine above with more tails.  Level k (0 <= k < n_levels)
+ * has blocks[k] partitions of L_k, L_0 = filter_length and L_k = ratios[k] * L_(k-1) (ratios[0] must be 1), and convolves
+ * taps [D_k, D_(k+1)), D_0 = 0 and D_k = D_(k-1) + blocks[k-1] * L_(k-1).  With z_k level k's overlap-save output in blocks
+ * of L_k from sample 0 (z_k[m] = 0 for m < 0) the engine computes
+ *   y[n] = ((y_0[n] + z_1[n - D_1]) + z_2[n - D_2]) + z_3[n - D_3]
+ * -- the uniform engine's convolution, L_0-frame blocks at the interface, no added latency -- the additions in working
+ * precision and in that order, each term after the output scale; format conversion, overflow statistics and the NaN guard
+ * act on the sum.  A level whose tap range holds no taps does no work and adds nothing: filters that end at or before D_2
+ * give the bytes of bfir_engine_create_nup(L_0, blocks[0], ratios[1], blocks[1], ...), n_levels = 2 the same.
+ * Everything else is as for two levels: 1 <= channels <= BFIR_MAXCHANNELS, an odd count one channel per transform; the
+ * output does not depend on how the blocks arrive; bfir_engine_reset discards all signal state of all levels.
+ * BFIR_ERR_ARG: n_levels outside 2 .. BFIR_MAX_LEVELS; a null array; ratios[0] != 1; a ratios[k], k >= 1, that is not a
+ * power of two >= 2; a blocks[k] < 1; D_k < L_k for some k >= 1 (a block of level k must be complete before it is read:
+ * for two levels, head_blocks >= tail_ratio).  BFIR_ERR_UNSUPPORTED: an L_k outside what bfir_engine_create takes for
+ * realsize; a frame format other than FLOAT_LE / FLOAT64_LE.  Arguments are checked before the device.
+ * Such an engine is a kind of its own: bfir_engine_set_coeff, _set_coeff_at, _read_coeff, the matrix calls, the fade calls
+ * and the three nup calls return BFIR_ERR_UNSUPPORTED on it, the three levels calls the same on every other kind of
+ * engine (one from bfir_engine_create_nup included). */
+#define BFIR_MAX_LEVELS 4
+bfir_engine *bfir_engine_create_levels(int filter_length, int n_levels, const int *blocks, const int *ratios,
+                                       int realsize, int channels, int in_format, int out_format, int device, int *err);
+/* coeffs[n]: `length` taps in working precision, length <= D_(n_levels) (more: BFIR_ERR_ARG); split at every D_k, ragged
+ * ends zero-filled.  A NaN/Inf tap: BFIR_ERR_COEFF and the engine is uninitialised.  Mid-stream every delay line is kept:
+ * the head uses the new filters from the next block, level k from its next block that completes, and ring contents
+ * already written still play.  A level that gains taps starts with its next block that begins, on an empty delay line; a
+ * level that loses its taps stops, and its queued output plays out. */
+int bfir_engine_set_coeff_levels(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale);
+/* partition spectrum `block` of `channel` on level `level`: 2 L_level reals, grouped layout */
+int bfir_engine_read_coeff_levels(bfir_engine *e, int level, int channel, int block, void *dst);
+
 void bfir_engine_destroy(bfir_engine *e);
 
 /* brutefir::is_initialized */
