@@ -210,6 +210,22 @@ struct bfir_engine {
     // plus what is written ahead of it.
     void *zring = nullptr; int zblocks = 0;
     long long z_from = 0, z_next = 0;
+    // Crossfaded coefficient change on a two- or multi-level engine (bfir_engine_set_coeff_nup_fade / _levels_fade).  The
+    // head fades as a uniform engine does (H2, fade_len, fade_pos, Yf above), over head blocks [a_f, a_f + K), a_f its block
+    // counter at the call.  Tail i (r = lv_r[i], Dk = lv_D[i]; head block a reads its block (a - Dk) / r) must have its
+    // output under the new set from block j0 = (a_f - Dk) / r on and under the old set up to block j1 = (a_f + K - 1 - Dk) / r,
+    // so it keeps a second time ring, zring2, with the geometry of the first, for the new set's output:
+    //   at the call   blocks [j0, z_next) have run with the old set: their MAC runs again with H2 on the delay line the tail
+    //                 still holds (its ring is ring_extra = ceil(Dk / r) + 1 slots deeper for this) into zring2;
+    //   lf_mode 1     blocks up to j1: MAC and inverse twice, (H, zring) and (H2, zring2); launches are cut at j1;
+    //   lf_mode 2     blocks past j1: the sets have swapped on the tail, the one inverse goes into zring2;
+    //   fade end      with the head's last fade block queued (block j1 is complete by then, because Dk >= r) zring2
+    //                 becomes zring (lf_mode 0).
+    // The head's fading chunks blend the sums over the old rings and over the new rings (queue_inv_lfade).
+    int ring_extra = 0;                    // on a tail: delay-line slots on top of 2 chunk + B
+    void *zring2 = nullptr;                // on a tail: allocated, like H2 and Yf, at the first fade
+    int lf_mode = 0; long long lf_j1 = -1;
+    bool lf_stop = false;                  // on a tail: the new set does not reach this level, it stops when the fade ends
     // profiling
     bool profiling = false;
     struct Span { int k; hipEvent_t a, b; };
@@ -267,8 +283,9 @@ static void free_work(bfir_engine *e)
 static int alloc_work(bfir_engine *e, int chunk)
 {
     const size_t cb = cbuf_bytes(e);
-    // fwd of chunk k+1 may run while mac of chunk k still reads its B-1 older slots
-    const int ring = 2 * chunk + e->B;
+    // fwd of chunk k+1 may run while mac of chunk k still reads its B-1 older slots; a tail level of a two- or multi-level
+    // engine keeps ring_extra blocks more, whose MAC a fade runs again (bfir_engine_set_coeff_levels_fade)
+    const int ring = 2 * chunk + e->B + e->ring_extra;
     if (e->X) { int rc = materialise_history(e); if (rc != BFIR_OK) return rc; }
     void *X = nullptr, *Y0 = nullptr, *Y1 = nullptr, *tin0 = nullptr, *tin1 = nullptr, *tout = nullptr;
     HIP_TRY(hipMalloc(&X, (size_t)e->GC * ring * cb));
@@ -282,8 +299,8 @@ static int alloc_work(bfir_engine *e, int chunk)
     }
     HIP_TRY(hipMemset(X, 0, (size_t)e->GC * ring * cb));
     if (e->X) {
-        // keep the last B-1 spectra: absolute block j lives in slot j % ring
-        const int keep = (int)std::min<unsigned long long>(e->blockcounter, (unsigned long long)(e->B - 1));
+        // keep the last B-1 spectra (a tail level: ring_extra more): absolute block j lives in slot j % ring
+        const int keep = (int)std::min<unsigned long long>(e->blockcounter, (unsigned long long)(e->B - 1 + e->ring_extra));
         for (int d = 1; d <= keep; d++) {
             const unsigned long long j = e->blockcounter - d;
             const size_t so = (size_t)(j % e->ring) * cb, dn = (size_t)(j % ring) * cb;
@@ -377,7 +394,7 @@ static void log_creation(const bfir_engine *e)
 // nup_level: 0, or 1 / 2 for the head / tail level of a two-level engine (bfir_engine_create_nup)
 static bfir_engine *engine_create(int n_engines, int filter_length, int filter_blocks, int realsize, int channels,
                                   int channels_out, bool matrix, int in_format, int out_format, int sampling_rate,
-                                  int apply_dither, int device, int *err, int nup_level = 0)
+                                  int apply_dither, int device, int *err, int nup_level = 0, int ring_extra = 0)
 {
     int dummy;
     if (!err) err = &dummy;
@@ -411,6 +428,7 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
     e->out_scale = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format);
     e->of_max = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format) - 1.0;
     e->nup = nup_level == 1; e->nup_tail = nup_level == 2;
+    e->ring_extra = ring_extra;
     choose_path(e);
     e->nblk.assign(matrix ? (size_t)e->Co * e->C : (size_t)e->GC, 0);   // matrix: [o C + i]
     e->eng_init.assign(n_engines, 0);
@@ -522,19 +540,24 @@ static int alloc_zring(bfir_engine *e, int i, int chunk)
     const int zb = (chunk + e->lv_D[i] + e->lv_r[i] - 1) / e->lv_r[i] + 2;
     if (zb <= t->zblocks) return BFIR_OK;
     const size_t blk = (size_t)t->L * t->s;
-    void *z = nullptr;
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMalloc(&z, (size_t)t->GC * zb * blk));
-    HIP_TRY(hipMemset(z, 0, (size_t)t->GC * zb * blk));
-    if (t->zring) {
-        const long long lo = std::max(t->z_from, t->z_next - t->zblocks);
-        for (long long j = lo; j < t->z_next; j++)
-            HIP_TRY(hipMemcpy2D((char *)z + (size_t)(j % zb) * blk, (size_t)zb * blk, (char *)t->zring + (size_t)(j % t->zblocks) * blk,
-                                (size_t)t->zblocks * blk, blk, t->GC, hipMemcpyDeviceToDevice));
-        HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(t->zring);
+    void **rings[2] = {&t->zring, &t->zring2};   // the second ring (a fade's new set) exists from the first fade on
+    for (void **zr : rings) {
+        if (zr == &t->zring2 && !t->zring2) continue;
+        void *z = nullptr;
+        HIP_TRY(hipMalloc(&z, (size_t)t->GC * zb * blk));
+        HIP_TRY(hipMemset(z, 0, (size_t)t->GC * zb * blk));
+        if (*zr) {
+            const long long lo = std::max(t->z_from, t->z_next - t->zblocks);
+            for (long long j = lo; j < t->z_next; j++)
+                HIP_TRY(hipMemcpy2D((char *)z + (size_t)(j % zb) * blk, (size_t)zb * blk, (char *)*zr + (size_t)(j % t->zblocks) * blk,
+                                    (size_t)t->zblocks * blk, blk, t->GC, hipMemcpyDeviceToDevice));
+            HIP_TRY(hipDeviceSynchronize());
+            (void)hipFree(*zr);
+        }
+        *zr = z;
     }
-    t->zring = z; t->zblocks = zb;
+    t->zblocks = zb;
     return BFIR_OK;
 }
 
@@ -549,8 +572,9 @@ static bfir_engine *create_split(int filter_length, int n_levels, const int *blo
     int r = 1, D = blocks[0];
     for (int k = 1; k < n_levels; k++) {
         r *= ratios[k];
+        // ceil(D_k / r) + 1 slots on top: the blocks a fade's catch-up runs again (at most that many) and their history
         bfir_engine *t = engine_create(1, r * filter_length, blocks[k], realsize, channels, channels, false, in_format, out_format,
-                                       44100, 0, device, err, 2);
+                                       44100, 0, device, err, 2, (D + r - 1) / r + 1);
         if (!t) return fail(*err);
         e->tail[k - 1] = t; e->lv_r[k - 1] = r; e->lv_D[k - 1] = D; e->n_tail = k;
         D += blocks[k] * r;
@@ -636,6 +660,7 @@ extern "C" void bfir_engine_destroy(bfir_engine *e)
     for (bfir_engine *t : e->tail) if (t) bfir_engine_destroy(t);
     if (e->pbuf) (void)hipFree(e->pbuf);
     if (e->zring) (void)hipFree(e->zring);
+    if (e->zring2) (void)hipFree(e->zring2);
     if (e->ev_nup) (void)hipEventDestroy(e->ev_nup);
     free_work(e);
     fft_plan_destroy(&e->plan);
@@ -752,6 +777,8 @@ extern "C" int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, 
     return bfir_engine_set_coeff_at(e, 0, coeffs, n_coeffs, length, coeff_blocks, scale);
 }
 
+static void lfade_finish(bfir_engine *e, bool take_new);
+
 // The filters of a two-level or multi-level engine, split at every D_k: taps [0, D_1) to the head, [D_k, D_(k+1)) to level
 // k.  Mid-stream every delay line is kept: the head takes the new filters from the next block, level k from its next
 // block that completes; what a level has already put into its time ring still plays.
@@ -762,6 +789,7 @@ static int set_coeff_split(bfir_engine *e, const void *const *coeffs, int n_coef
     if (!coeffs || n_coeffs < 0 || length < 0 || (long long)length > cap) return BFIR_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
+    if (e->fade_len > 0) { e->fade_len = e->fade_pos = 0; lfade_finish(e, false); }   // a plain change during a fade cancels it: a hard cut
     e->eng_init[0] = 0;
     if (n_coeffs > e->C) n_coeffs = e->C;
     const int len_h = (int)std::min<long long>(length, (long long)e->B * e->L);
@@ -870,6 +898,30 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
 // crossfaded coefficient change: the engine-level form of fftw_convolver::convolver_crossfade_inplace
 // (brutefir/fftw_convolver.cpp:275-321), stretched over fade_blocks blocks
 // ---------------------------------------------------------------------------
+// a tail level of a fading two- or multi-level engine takes the new set (its H2 becomes H) ...
+static void tail_swap_sets(bfir_engine *t)
+{
+    std::swap(t->H, t->H2);
+    std::swap(t->d_nblk, t->d_nblk2);
+    std::swap(t->nblk, t->nblk2);
+}
+
+// ... and the fade of such an engine ends, for its tails.  take_new (the head has queued its last fade block, or
+// bfir_engine_reset): every level is on the new set, the second ring of every level becomes its ring, and a level the new
+// set does not reach stops as bfir_engine_set_coeff_levels would stop it.  Without (a plain set_coeff ends the fade, a hard
+// cut): a level keeps the ring that holds its output up to z_next -- the second one if it has passed its last old block.
+static void lfade_finish(bfir_engine *e, bool take_new)
+{
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        if (!t->lf_mode) continue;
+        if (take_new && t->lf_mode == 1) tail_swap_sets(t);
+        if (take_new || t->lf_mode == 2) std::swap(t->zring, t->zring2);
+        if (take_new && t->lf_stop) e->lv_active[i] = false;
+        t->lf_mode = 0; t->lf_stop = false;
+    }
+}
+
 // the old set gives way to the new one: H2 becomes H (the buffer that was H is the next fade's H2)
 static void fade_swap_sets(bfir_engine *e)
 {
@@ -878,6 +930,7 @@ static void fade_swap_sets(bfir_engine *e)
     std::swap(e->nblk, e->nblk2);
     e->fade_len = e->fade_pos = 0;
     if (e->matrix && e->pair_cap) matrix_take_path(e, e->pair_new);
+    if (e->nup) lfade_finish(e, true);
 }
 
 // rows: the filters of the call (C of a diagonal engine, Co x C of a matrix engine)
@@ -1296,20 +1349,30 @@ static void queue_inv_fade(bfir_engine *e, const Chunk &c, hipStream_t st)
 
 // The back end of a tail level's chunk (tc tail blocks from block z_next on): planar inverses into the time ring, one per
 // stretch between wraps.
-static void queue_inv_tail(bfir_engine *e, const Chunk &c, hipStream_t st)
+// n blocks of product spectra (channel stride y_ch_stride reals) -> tail blocks j .. of a time ring of the level
+static void inv_to_ring(bfir_engine *e, const void *Y, long y_ch_stride, void *zring, long long j, int n_blocks, hipStream_t st)
 {
-    ProfScope ps(e, BFIR_K_INV, st);
-    for (int t0 = 0; t0 < c.tc;) {
-        const int slot = (int)((e->z_next + t0) % e->zblocks), n = std::min(c.tc - t0, e->zblocks - slot);
+    for (int t0 = 0; t0 < n_blocks;) {
+        const int slot = (int)((j + t0) % e->zblocks), n = std::min(n_blocks - t0, e->zblocks - slot);
         InvArgs a;
-        a.src = (const char *)c.Y + (size_t)t0 * cbuf_bytes(e); a.src_ch_stride = (long)e->chunk * e->N;
-        a.dst = (char *)e->zring + (size_t)slot * e->L * e->s; a.dst_ch_stride = (long)e->zblocks * e->L;
+        a.src = (const char *)Y + (size_t)t0 * cbuf_bytes(e); a.src_ch_stride = y_ch_stride;
+        a.dst = (char *)zring + (size_t)slot * e->L * e->s; a.dst_ch_stride = (long)e->zblocks * e->L;
         a.n_t = n; a.n_ch = e->GC;
         a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
         launch_inv(e->plan, a, st);
         t0 += n;
     }
+}
+
+// During a fade (lf_mode, above): up to its last old block the level has run its MAC twice and inverts both products, the
+// old set's into its ring and the new set's into the second ring; past it the one product is the new set's.
+static void queue_inv_tail(bfir_engine *e, const Chunk &c, hipStream_t st)
+{
+    ProfScope ps(e, BFIR_K_INV, st);
+    inv_to_ring(e, c.Y, (long)e->chunk * e->N, e->lf_mode == 2 ? e->zring2 : e->zring, e->z_next, c.tc, st);
+    if (e->lf_mode == 1) inv_to_ring(e, c.Y2, c.y2_ch_stride, e->zring2, e->z_next, c.tc, st);
     e->z_next += c.tc;
+    if (e->lf_mode == 1 && e->z_next > e->lf_j1) { tail_swap_sets(e); e->lf_mode = 2; }   // launches take H by value
 }
 
 // The back end of a head chunk whose blocks all have the contributions of the tails in nup_mask: Y and their time rings
@@ -1379,6 +1442,62 @@ static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
     queue_stage_out(e, c, e->tout, t_stride, st);
 }
 
+// The back end of a FADING head chunk of a two- or multi-level engine whose blocks all have the contributions of the tails
+// in nup_mask (not empty): Y, Y2 and the two rings of every contributing level -> blended output frames (lfade.hip).
+static void queue_inv_lfade(bfir_engine *e, const Chunk &c, hipStream_t st)
+{
+    LevelRing ring[BFIR_LEVEL_RINGS];
+    const void *z_new[BFIR_LEVEL_RINGS];
+    int nr = 0;
+    for (int i = 0; i < e->n_tail; i++) {
+        if (!(e->nup_mask >> i & 1)) continue;
+        const bfir_engine *t = e->tail[i];
+        // a level outside the fade (neither set reaches it, but output queued before it stopped still plays) adds the same to both sums
+        z_new[nr] = t->lf_mode ? t->zring2 : t->zring;
+        LevelRing &g = ring[nr++];
+        g.z = t->zring; g.zlen = g.z_ch_stride = (long)t->zblocks * t->L;
+        g.m0 = ((long long)e->blockcounter - e->lv_D[i]) * e->L; g.m_min = t->z_from * (long long)t->L;
+        g.m0r = (long)(((g.m0 % g.zlen) + g.zlen) % g.zlen);
+    }
+    for (int k = nr; k < BFIR_LEVEL_RINGS; k++) { ring[k] = ring[0]; z_new[k] = z_new[0]; }
+    if (e->fade_fused) {   // one inverse per channel and block, both sums, blend, statistics and frame store in one kernel
+        ProfScope ps(e, BFIR_K_INV, st);
+        LfadeInvArgs a;
+        a.y_old = (const float *)c.Y; a.y_old_ch_stride = (long)e->chunk * e->N;
+        a.y_new = (const float *)c.Y2; a.y_new_ch_stride = c.y2_ch_stride;
+        for (int k = 0; k < BFIR_LEVEL_RINGS; k++) { a.ring[k] = ring[k]; a.z_new[k] = z_new[k]; }
+        a.n_rings = nr;
+        a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
+        a.n_ch = e->C; a.n_t = c.tc;
+        a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+        a.f = e->fade_f; a.m0 = c.m0;
+        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+        launch_inv_lfade(e->plan2, a, st);
+        return;
+    }
+    // the general form: two planar inverses into the fade's own scratch, sums and blend, then the staging path's output kernel
+    const long t_stride = (long)e->ft_blocks * e->L;
+    {
+        ProfScope ps(e, BFIR_K_INV, st);
+        InvArgs a;
+        a.n_t = c.tc; a.n_ch = e->GC;
+        a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
+        a.dst_ch_stride = t_stride;
+        a.src = c.Y; a.src_ch_stride = (long)e->chunk * e->N; a.dst = e->ft[0];
+        launch_inv(e->plan, a, st);
+        a.src = c.Y2; a.src_ch_stride = c.y2_ch_stride; a.dst = e->ft[1];
+        launch_inv(e->plan, a, st);
+        LfadeSumArgs b;
+        b.y_old = e->ft[0]; b.y_new = e->ft[1]; b.ch_stride = t_stride;
+        for (int k = 0; k < BFIR_LEVEL_RINGS; k++) { b.ring[k] = ring[k]; b.z_new[k] = z_new[k]; }
+        b.n_rings = nr;
+        b.n_ch = e->GC; b.n = (long)c.tc * e->L;
+        b.f = e->s == 4 ? (double)e->fade_f : e->fade_d; b.m0 = c.m0; b.realsize = e->s;
+        launch_lfade_sum(b, st);
+    }
+    queue_stage_out(e, c, e->ft[0], t_stride, st);
+}
+
 // The staging path's time history, once the chunk is queued (plain or fading: its front is the same): only the
 // references move; the samples stay where stage_in put them (this time buffer is not rewritten before chunk k+2, by
 // which time both references have moved on).
@@ -1409,7 +1528,8 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     c.Y = e->Yb[e->pipe3 ? par : 0];
     // run_blocks cut the chunk so that it is all fade or all plain
     c.fade = e->fade_len > 0;
-    if (c.fade) { c.Y2 = e->Yf[e->pipe3 ? par : 0]; c.y2_ch_stride = (long)e->yf_blocks * e->N; c.m0 = e->fade_pos * e->L; }
+    const bool both = c.fade || e->lf_mode == 1;   // ... or, a tail level of a fading engine, all up to its last old block: both sets
+    if (both) { c.Y2 = e->Yf[e->pipe3 ? par : 0]; c.y2_ch_stride = (long)e->yf_blocks * e->N; c.m0 = e->fade_pos * e->L; }
     rc = chunk_aligned(e, p, c);
     if (rc != BFIR_OK) return rc;
     if (c.fade && e->fade_fused && (((uintptr_t)d_out | (uintptr_t)out_stride) & 3)) {
@@ -1434,7 +1554,7 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
         ProfScope ps(e, BFIR_K_MAC, sm);
         if (!e->matrix) launch_mac(mac_args(e, c.base_slot, c.Y, tc), sm);
         else if (launch_mac_matrix(matrix_mac_args(e, c.base_slot, c.Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
-        if (c.fade) {   // the same delay line through the same kernels with the new set, behind the first
+        if (both) {   // the same delay line through the same kernels with the new set, behind the first
             if (!e->matrix) { MacArgs a = mac_args(e, c.base_slot, c.Y2, tc, true); a.y_ch_stride = c.y2_ch_stride; launch_mac(a, sm); }
             else {
                 MatArgs a = matrix_mac_args(e, c.base_slot, c.Y2, tc, true); a.y_ch_stride = c.y2_ch_stride;
@@ -1446,7 +1566,8 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
         if (e->pipe3) HIP_TRY(hipStreamWaitEvent(st, e->ev_mac[par], 0));
     }
-    if (c.fade) queue_inv_fade(e, c, st);
+    if (c.fade && e->nup_mask) queue_inv_lfade(e, c, st);
+    else if (c.fade) queue_inv_fade(e, c, st);
     else if (e->nup_tail) queue_inv_tail(e, c, st);
     else if (e->nup_mask) queue_inv_nup(e, c, st);
     else queue_inv(e, p, c, st);
@@ -1465,11 +1586,12 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     return BFIR_OK;
 }
 
-// The fade's work buffers, sized for the chunks it can be cut into: min(chunk, fade_len) blocks.
+// The fade's work buffers, sized for the chunks it can be cut into: min(chunk, fade_len) blocks (the head, a uniform or a
+// matrix engine), or for the launches of a tail level of a fading engine: its chunk, and no planar scratch.
 static int ensure_fade_buffers(bfir_engine *e)
 {
-    const int want = std::min(e->chunk, e->fade_len);
-    const bool need_ft = !e->fade_fused;
+    const int want = e->nup_tail ? e->chunk : std::min(e->chunk, e->fade_len);
+    const bool need_ft = !e->fade_fused && !e->nup_tail;
     if (e->yf_blocks >= want && (!need_ft || e->ft_blocks >= want)) return BFIR_OK;
     HIP_TRY(hipDeviceSynchronize());   // queued fade chunks may still use the old ones
     for (int i = 0; i < 2; i++) {
@@ -1485,6 +1607,149 @@ static int ensure_fade_buffers(bfir_engine *e)
         e->ft_blocks = want;
     }
     return BFIR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// crossfaded coefficient change on a two-level or multi-level engine (the schedule: bfir_engine, "lf_mode")
+// ---------------------------------------------------------------------------
+// floor(a / b), b > 0
+static long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
+
+static int set_coeff_split_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale, int fade_blocks)
+{
+    long long cap = (long long)e->B * e->L;
+    for (int i = 0; i < e->n_tail; i++) cap += (long long)e->tail[i]->B * e->tail[i]->L;
+    if (!coeffs || n_coeffs < 0 || length < 0 || (long long)length > cap) return BFIR_ERR_ARG;
+    // m = 0 .. K L - 1 must be exact as a float (fftw_convolver.cpp:302 multiplies by (float)n)
+    if (fade_blocks < 1 || (long long)fade_blocks * e->L > (1ll << 24)) return BFIR_ERR_ARG;
+    if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
+    if (n_coeffs > e->C) n_coeffs = e->C;
+    for (int n = 0; n < n_coeffs; n++) if (!coeffs[n]) return BFIR_ERR_ARG;
+    // the split of set_coeff_split
+    const int len_h = (int)std::min<long long>(length, (long long)e->B * e->L);
+    const int nb_h = std::min(e->B, std::max(1, (len_h + e->L - 1) / e->L));
+    int len_lv[BFIR_MAX_LEVELS - 1], nb_lv[BFIR_MAX_LEVELS - 1];
+    for (int i = 0; i < e->n_tail; i++) {
+        const bfir_engine *t = e->tail[i];
+        const long long D = (long long)e->lv_D[i] * e->L;
+        len_lv[i] = (int)std::max(0ll, std::min((long long)length - D, (long long)t->B * t->L));
+        nb_lv[i] = len_lv[i] > 0 ? std::min(t->B, (len_lv[i] + t->L - 1) / t->L) : 0;
+        // a level the old set does not reach runs no forward transforms: it has no delay line to fade on
+        if (len_lv[i] > 0 && !e->lv_active[i]) {
+            bfir_logf("bfir engine: the new filters reach level %d, the active ones do not: load the first set zero-padded to the "
+                      "longest length that will be faded to.", i + 1);
+            return BFIR_ERR_UNSUPPORTED;
+        }
+    }
+    // a NaN / Inf tap at any level is refused before anything is uploaded at any level: the engine keeps running the old set
+    for (int n = 0; n < n_coeffs; n++) {
+        bool finite = true;
+        if (e->s == 4) {
+            const float *src = (const float *)coeffs[n];
+            const float sc = (float)scale;
+            for (int i = 0; i < length; i++) finite &= std::isfinite((double)(src[i] * sc));
+        } else {
+            const double *src = (const double *)coeffs[n];
+            for (int i = 0; i < length; i++) finite &= std::isfinite(src[i] * scale);
+        }
+        if (!finite) {
+            bfir_logf("NaN or Inf value among coefficients.");
+            bfir_logf("Error preprocessing coefficient %d", n);
+            return BFIR_ERR_COEFF;
+        }
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    // queued work may still read what was H before the last fade's swap, and the catch-up below reads the delay lines: the
+    // device is idle from here to the end of the call
+    HIP_TRY(hipDeviceSynchronize());
+    // H2, the second ring and Yf of every level: allocated at the first fade
+    bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
+    for (bfir_engine *l : lv) {
+        if (!l || l->H2) continue;
+        HIP_TRY(hipMalloc(&l->H2, (size_t)l->C * l->B * cbuf_bytes(l)));
+        HIP_TRY(hipMalloc((void **)&l->d_nblk2, sizeof(int) * l->GC));
+    }
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        if (!t->zring2) HIP_TRY(hipMalloc(&t->zring2, (size_t)t->GC * t->zblocks * t->L * t->s));
+    }
+    e->fade_fused = e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L);
+    if (e->fade_fused && !e->plan2.tw && fft_plan_create(&e->plan2, 2 * e->L, 4) != 0) return BFIR_ERR_HIP;   // an odd channel count: direct mode has none yet
+    int rc = load_filters(e, e->H2, 0, e->C, coeffs, n_coeffs, len_h, nb_h, scale, false);
+    if (rc != BFIR_OK) return rc;
+    e->nblk2.assign(e->nblk.size(), nb_h);
+    HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        if (!e->lv_active[i]) continue;
+        if (len_lv[i] > 0) {
+            std::vector<const void *> rest((size_t)n_coeffs);
+            for (int n = 0; n < n_coeffs; n++) rest[n] = (const char *)coeffs[n] + (size_t)e->lv_D[i] * e->L * e->s;
+            rc = load_filters(t, t->H2, 0, t->C, rest.data(), n_coeffs, len_lv[i], nb_lv[i], scale, false);
+            if (rc != BFIR_OK) return rc;
+        } else {   // the new set does not reach the level: one all-zero partition, so its products with the new set are zero
+            HIP_TRY(hipMemset(t->H2, 0, (size_t)t->C * t->B * cbuf_bytes(t)));
+            nb_lv[i] = 1;
+        }
+        t->nblk2.assign(t->nblk.size(), nb_lv[i]);
+        HIP_TRY(hipMemcpy(t->d_nblk2, t->nblk2.data(), sizeof(int) * t->C, hipMemcpyHostToDevice));
+    }
+    // Catch-up: the blocks a level has run with the old set that the fade's first head block, or a later one, reads under
+    // the new set.  Their spectra are still in the delay line; a level that restarted mid-stream less than that many blocks
+    // ago (bfir_engine_set_coeff_levels) has only those since, the ones before read as zero under the new set.
+    const long long a_f = (long long)e->blockcounter;
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        if (!e->lv_active[i]) continue;
+        const int r = e->lv_r[i];
+        rc = ensure_fade_buffers(t);
+        if (rc != BFIR_OK) return rc;
+        HIP_TRY(hipMemsetAsync(t->zring2, 0, (size_t)t->GC * t->zblocks * t->L * t->s, e->stream));
+        long long j0 = std::max(t->z_from, floor_div(a_f - e->lv_D[i], r));
+        j0 = std::max(j0, t->z_next - std::min<long long>((long long)t->blockcounter, t->ring_extra));
+        for (long long j = j0; j < t->z_next;) {
+            const int n = (int)std::min<long long>(t->z_next - j, t->yf_blocks);
+            const long long bc = (long long)t->blockcounter - (t->z_next - j);   // the level's own count of block j
+            MacArgs a = mac_args(t, (int)(bc % t->ring), t->Yf[0], n, true);
+            a.y_ch_stride = (long)t->yf_blocks * t->N;
+            launch_mac(a, e->stream);
+            inv_to_ring(t, t->Yf[0], a.y_ch_stride, t->zring2, j, n, e->stream);
+            j += n;
+        }
+        t->lf_j1 = floor_div(a_f + fade_blocks - 1 - e->lv_D[i], r);
+        t->lf_stop = len_lv[i] == 0;
+        t->lf_mode = 1;
+        if (t->z_next > t->lf_j1) { tail_swap_sets(t); t->lf_mode = 2; }   // every old block the fade reads has run
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    e->fade_f = (float)(1.0 / (double)(float)(fade_blocks * e->L - 1));
+    e->fade_d = 1.0 / (double)(fade_blocks * e->L - 1);
+    e->fade_len = fade_blocks; e->fade_pos = 0;
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_set_coeff_nup_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
+                                              int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->nup || e->levels) return BFIR_ERR_UNSUPPORTED;
+    return set_coeff_split_fade(e, coeffs, n_coeffs, length, scale, fade_blocks);
+}
+
+extern "C" int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
+                                                 int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->levels) return BFIR_ERR_UNSUPPORTED;
+    return set_coeff_split_fade(e, coeffs, n_coeffs, length, scale, fade_blocks);
+}
+
+extern "C" int bfir_engine_fade_remaining_levels(const bfir_engine *e)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->nup) return BFIR_ERR_UNSUPPORTED;
+    return e->fade_len > 0 ? e->fade_len - e->fade_pos : 0;
 }
 
 // The frames of head blocks [lo, hi) of this call (the head block at frame_off is call0) -> pbuf, but for those that
@@ -1523,6 +1788,7 @@ static int nup_tail_ahead(bfir_engine *e, const void *d_in, long frame_off, long
         if (!e->lv_active[i]) continue;
         for (const long long j_end = a1 / r; t->z_next < j_end;) {
             const long long j = t->z_next;
+            if (t->lf_mode == 1) { const int rc = ensure_fade_buffers(t); if (rc != BFIR_OK) return rc; }
             if (j * r < call0) {   // began before this call: the rest of its frames join the ones kept in pbuf
                 int rc = nup_keep(e, d_in, frame_off, call0, j * r, (j + 1) * r, st, input_ready);
                 if (rc != BFIR_OK) return rc;
@@ -1531,7 +1797,8 @@ static int nup_tail_ahead(bfir_engine *e, const void *d_in, long frame_off, long
                                e->inline_launch ? nullptr : e->ev_nup);
                 if (rc != BFIR_OK) return rc;
             } else {
-                const int nt = (int)std::min<long long>(j_end - j, t->chunk);
+                int nt = (int)std::min<long long>(j_end - j, t->chunk);
+                if (t->lf_mode == 1) nt = (int)std::min<long long>(nt, t->lf_j1 - j + 1);   // a launch's blocks are all of one kind
                 const int rc = run_chunk(t, d_in, 0, nullptr, 0, frame_off + (long)(j * r - call0) * e->L, nt, 0, st, input_ready);
                 if (rc != BFIR_OK) return rc;
             }
@@ -1871,6 +2138,7 @@ extern "C" int bfir_engine_run(bfir_engine *e, const void *inbuf, void *outbuf, 
 static void nup_reset(bfir_engine *e)
 {
     (void)hipDeviceSynchronize();
+    if (e->fade_len > 0) fade_swap_sets(e);   // a fade ends at once, with the new set active at every level
     bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
     for (bfir_engine *l : lv) {
         if (!l) continue;

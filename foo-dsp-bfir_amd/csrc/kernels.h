@@ -323,6 +323,38 @@ struct LevelsCombineArgs {
 };
 void launch_levels_combine(const LevelsCombineArgs &a, hipStream_t s);
 
+// lfade.hip: the back end of a crossfaded coefficient change on a two-level or multi-level engine
+// (bfir_engine_set_coeff_nup_fade / _levels_fade) for a chunk to which one to three tail levels contribute.  The head's MAC
+// has run twice (y_old, y_new as in FadeInvArgs) and every contributing level keeps two time rings of ONE geometry: ring[r]
+// describes it and points at the level's output under the old set, z_new[r] at its output under the new set.  Sample n of
+// block t is  fade_blend(S_old, S_new),  S_x = ((y_x[n] + z_0,x[m_0]) + z_1,x[m_1]) + z_2,x[m_2]  as in LevelsInvArgs, the
+// blend as in FadeInvArgs with m = m0 + t L + n.
+// k_inv_lfade, the fused form: k_inv_fade's rule (fp32, (re, im) pairs, FLOAT_LE frames, 512 <= L <= 8192, any n_ch; `plan`
+// is the plan of 2L points) with n_rings = 1, 2 or 3 additions per set and sample.
+struct LfadeInvArgs {
+    const float *y_old; long y_old_ch_stride;            // [n_ch][..][N] product spectra, (re, im) pairs
+    const float *y_new; long y_new_ch_stride;
+    LevelRing ring[BFIR_LEVEL_RINGS]; const void *z_new[BFIR_LEVEL_RINGS]; int n_rings;
+    float *raw; long frame_off;                          // output frames of ONE engine, n_ch channels wide
+    int n_ch, n_t;
+    float scale, max;
+    float f; int m0;                                     // the ramp: 1 / (K L - 1), and m of sample 0 of block 0
+    DevOverflow *overflow; long of_shard_stride;
+    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+};
+void launch_inv_lfade(const FftPlan &plan, const LfadeInvArgs &a, hipStream_t s);
+// k_lfade_sum, the general form's middle step: y_old[c][i] <- blend(y_old[c][i] + old rings, y_new[c][i] + new rings) on
+// planar time buffers [n_ch][..] (i < n: the chunk's n_t L samples of a channel) in one pass; launch_inv fills them,
+// launch_stage_out follows.
+struct LfadeSumArgs {
+    void *y_old; const void *y_new; long ch_stride;      // in reals
+    LevelRing ring[BFIR_LEVEL_RINGS]; const void *z_new[BFIR_LEVEL_RINGS]; int n_rings;
+    int n_ch; long n;
+    double f; int m0;                                    // as in FadeBlendArgs
+    int realsize;
+};
+void launch_lfade_sum(const LfadeSumArgs &a, hipStream_t s);
+
 // mixnscale with one buffer (a7 / a11) on half-complex data, for the stage API.
 void launch_reorder(const void *in, void *out, int n_fft, double scale, int to_grouped, int realsize,
                     hipStream_t s);

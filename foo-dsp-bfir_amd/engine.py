@@ -307,6 +307,20 @@ class BrutefirNup(Brutefir):
     def set_coeff_fade(self, *args, **kwargs):
         raise BfirError(_lib.ERR_UNSUPPORTED, "bfir_engine_set_coeff_fade")
 
+    def fade_to(self, coeffs, fade_blocks, scale=1.0):
+        """bfir_engine_set_coeff_nup_fade: fade to coeffs (as set_coeff takes them) over the next `fade_blocks` blocks of filter_length
+        frames, every level consistently (the ramp of fftw_convolver::convolver_crossfade_inplace).  Returns 0 or an ERR_*
+        code: ERR_COEFF (a NaN / Inf tap) leaves the engine running the old filters, ERR_UNSUPPORTED means the new set reaches
+        a level the old one does not (load the first set zero-padded to the longest length that will be faded to)."""
+        rd = _real_dtype(self.s)
+        arrs = [np.ascontiguousarray(c, dtype=rd) for c in coeffs]
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return self._lib.bfir_engine_set_coeff_nup_fade(self._h, ptrs, len(arrs), arrs[0].size, float(scale), int(fade_blocks))
+
+    def fade_remaining(self):
+        """Head blocks of a pending or running fade_to still to be processed; 0 = none."""
+        return self._lib.bfir_engine_fade_remaining_levels(self._h)
+
     def coeff_block(self, level, channel, block):
         """Partition spectrum `block` of `channel` on level 0 (head, 2 L reals) or 1 (tail, 2 tail_ratio L reals)."""
         n = 2 * self.L * (self.tail_ratio if level else 1)
@@ -360,6 +374,20 @@ class BrutefirLevels(Brutefir):
 
     def set_coeff_fade(self, *args, **kwargs):
         raise BfirError(_lib.ERR_UNSUPPORTED, "bfir_engine_set_coeff_fade")
+
+    def fade_to(self, coeffs, fade_blocks, scale=1.0):
+        """bfir_engine_set_coeff_levels_fade: fade to coeffs (as set_coeff takes them) over the next `fade_blocks` blocks of filter_length
+        frames, every level consistently (the ramp of fftw_convolver::convolver_crossfade_inplace).  Returns 0 or an ERR_*
+        code: ERR_COEFF (a NaN / Inf tap) leaves the engine running the old filters, ERR_UNSUPPORTED means the new set reaches
+        a level the old one does not (load the first set zero-padded to the longest length that will be faded to)."""
+        rd = _real_dtype(self.s)
+        arrs = [np.ascontiguousarray(c, dtype=rd) for c in coeffs]
+        ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
+        return self._lib.bfir_engine_set_coeff_levels_fade(self._h, ptrs, len(arrs), arrs[0].size, float(scale), int(fade_blocks))
+
+    def fade_remaining(self):
+        """Head blocks of a pending or running fade_to still to be processed; 0 = none."""
+        return self._lib.bfir_engine_fade_remaining_levels(self._h)
 
     def coeff_block(self, level, channel, block):
         """Partition spectrum `block` of `channel` on `level`: 2 L_level reals."""

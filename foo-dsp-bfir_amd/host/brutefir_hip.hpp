@@ -90,6 +90,21 @@ public:
         return bfir_engine_set_coeff_levels(m_e, (const void *const *)coeffs, n_coeffs, length, scale);
     }
 
+    // The same two with a crossfade over the next fade_blocks blocks of filter_length frames, every level consistently
+    // (bfir_engine_set_coeff_nup_fade / _levels_fade): 0, -2 (a NaN/Inf tap: the old filters stay), or a BFIR_ERR_* code.
+    int set_coeff_nup_fade(void **coeffs, int n_coeffs, int length, double scale, int fade_blocks)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_nup_fade(m_e, (const void *const *)coeffs, n_coeffs, length, scale, fade_blocks);
+    }
+    int set_coeff_levels_fade(void **coeffs, int n_coeffs, int length, double scale, int fade_blocks)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_levels_fade(m_e, (const void *const *)coeffs, n_coeffs, length, scale, fade_blocks);
+    }
+    // head blocks of such a fade still to be processed; 0 = none
+    int fade_remaining_levels() { return m_e ? bfir_engine_fade_remaining_levels(m_e) : -1; }
+
     // brutefir.cpp:244-343: one block of filter_length interleaved frames; 0 or -1.
     int run(void *inbuf, void *outbuf) { return run_blocks(inbuf, outbuf, 1); }
 

@@ -147,7 +147,8 @@ bfir_engine *bfir_engine_create_matrix(int filter_length, int filter_blocks, int
  * engine -- both delay lines, both time histories, the tail's partial input block and its queued output -- and zeroes
  * the counters; the engine then behaves as newly created with the same coefficients.  (The plain engine keeps
  * input_timecbuf across a reset, a quirk of the reference with no two-level meaning.)
- * bfir_engine_set_coeff, _set_coeff_at, _read_coeff, the matrix calls and the fade calls return BFIR_ERR_UNSUPPORTED on
+ * bfir_engine_set_coeff, _set_coeff_at, _read_coeff, the matrix calls and the uniform fade calls (the fade of such an engine is
+ * bfir_engine_set_coeff_nup_fade) return BFIR_ERR_UNSUPPORTED on
  * it; the three nup calls the same on every other kind of engine. */
 bfir_engine *bfir_engine_create_nup(int filter_length, int head_blocks, int tail_ratio, int tail_blocks, int realsize,
                                     int channels, int in_format, int out_format, int device, int *err);
@@ -176,7 +177,8 @@ int bfir_engine_read_coeff_nup(bfir_engine *e, int level, int channel, int block
  * power of two >= 2; a blocks[k] < 1; D_k < L_k for some k >= 1 (a block of level k must be complete before it is read:
  * for two levels, head_blocks >= tail_ratio).  BFIR_ERR_UNSUPPORTED: an L_k outside what bfir_engine_create takes for
  * realsize; a frame format other than FLOAT_LE / FLOAT64_LE.  Arguments are checked before the device.
- * Such an engine is a kind of its own: bfir_engine_set_coeff, _set_coeff_at, _read_coeff, the matrix calls, the fade calls
+ * Such an engine is a kind of its own: bfir_engine_set_coeff, _set_coeff_at, _read_coeff, the matrix calls, the uniform fade calls
+ * (its fade is bfir_engine_set_coeff_levels_fade)
  * and the three nup calls return BFIR_ERR_UNSUPPORTED on it, the three levels calls the same on every other kind of
  * engine (one from bfir_engine_create_nup included). */
 #define BFIR_MAX_LEVELS 4
@@ -243,6 +245,40 @@ int bfir_engine_set_coeff_matrix_fade(bfir_engine *e, const void *const *coeffs,
                                       int coeff_blocks, double scale, int fade_blocks);
 /* Blocks of a pending or running fade still to be processed; 0 = none.  < 0: error. */
 int bfir_engine_fade_remaining(const bfir_engine *e);
+
+/* The same crossfade (fftw_convolver::convolver_crossfade_inplace, brutefir/fftw_convolver.cpp:275-321, stretched over
+ * fade_blocks blocks of the head length L) on an engine from bfir_engine_create_nup: `length` taps per channel, split at D
+ * as bfir_engine_set_coeff_nup splits them.  With a_f the engine's block counter at the call and K = fade_blocks, sample m =
+ * 0 .. K L - 1 of the fade, at absolute sample a_f L + m, is blend(S_old[m], S_new[m]) with the blend, f and d of
+ * bfir_engine_set_coeff_fade and S_x = ((y_head,x + z_1,x) + z_2,x) + z_3,x: the sums of the levels under the filters active
+ * at the call (x = old) and under the filters of the call (x = new), in working precision, head first, levels in order.
+ * Both sets act on the whole signal history: there is no transient.  Format conversion, overflow statistics and the NaN
+ * guard act on the blended sample.  Before block a_f the engine is an engine that never faded, from block a_f + K on one
+ * that has had the new filters all along; the output does not depend on how the blocks arrive.
+ * BFIR_ERR_ARG: a null engine or `coeffs`, negative counts, `length` above the engine's capacity, fade_blocks < 1 or
+ * K L > 2^24.  BFIR_ERR_STATE: no coefficients yet, or a fade is pending or running (poll
+ * bfir_engine_fade_remaining_levels).  BFIR_ERR_COEFF: a NaN or Inf tap at any level, refused before anything is uploaded
+ * at any level: the engine stays initialised and keeps running the old filters (unlike bfir_engine_set_coeff_nup).
+ * BFIR_ERR_UNSUPPORTED: an engine of another kind; or the new set reaches a level the old set does not -- that level runs
+ * no forward transforms and so has no delay line to fade on; nothing changes.  The way round it: load the first set
+ * zero-padded to the longest length that will ever be faded to (a level is active by `length`, not by the tap values).
+ * A new set that is shorter is allowed: the level runs through the fade with no partitions for the new set and then stops
+ * as a bfir_engine_set_coeff_nup of that length would stop it.
+ * bfir_engine_set_coeff_nup / _levels during a fade ends it (fade_remaining 0) and behaves as it does mid-stream;
+ * bfir_engine_reset ends it with the new set active at every level and all signal state gone; bfir_engine_read_coeff_nup /
+ * _levels reads the head's old set while the fade remains (which set the other levels read is unspecified) and the new set
+ * at every level once it is done.
+ * Memory: the first fade allocates, per level, a second filter set, a second time ring and a second product buffer. */
+int bfir_engine_set_coeff_nup_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
+                                   int fade_blocks);
+/* ... and on an engine from bfir_engine_create_levels (two levels included): the crossfade of
+ * fftw_convolver::convolver_crossfade_inplace (brutefir/fftw_convolver.cpp:275-321) as bfir_engine_set_coeff_nup_fade
+ * defines it above, the taps split at every D_k as bfir_engine_set_coeff_levels splits them. */
+int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
+                                      int fade_blocks);
+/* Head blocks of a pending or running fade (fftw_convolver.cpp:275-321 over fade_blocks blocks) of an engine from
+ * bfir_engine_create_nup or _levels still to be processed; 0 = none.  BFIR_ERR_UNSUPPORTED on every other kind of engine. */
+int bfir_engine_fade_remaining_levels(const bfir_engine *e);
 
 /* brutefir::run (brutefir.cpp:244-343) for n_blocks consecutive blocks.
  * inbuf/outbuf: HOST memory, n_blocks * filter_length interleaved frames in
