@@ -1,9 +1,10 @@
 """The transform-size matrix: one row per (kernel family, realsize, L) the engine supports, the channel count, frame
 formats and switches that make the engine take that family, and what its creation log line must then report.
 
-NUP_CELLS, FADE_CELLS and MATRIX_CELLS are the same for the engine kinds built on top of the plain diagonal engine:
-two-level engines (csrc/nup.hip and the tail level in engine.hip), crossfaded coefficient changes (csrc/fade.hip) and
-matrix engines (csrc/matrix.hip).
+NUP_CELLS, FADE_CELLS, MATRIX_CELLS, LEVELS_CELLS and LFADE_CELLS are the same for the engine kinds built on top of the
+plain diagonal engine: two-level engines (csrc/nup.hip and the tail level in engine.hip), crossfaded coefficient changes
+(csrc/fade.hip), matrix engines (csrc/matrix.hip), multi-level engines (csrc/levels.hip) and crossfaded coefficient changes
+on two-level and multi-level engines (csrc/lfade.hip).
 
 Plain data, importable without a GPU: tests/test_size_matrix.py checks on the CPU that the lists cover exactly the set
 the sources in csrc/ support; tests/test_size_matrix_gpu.py and tests/test_size_matrix_kinds_gpu.py run every row on
@@ -60,7 +61,29 @@ def source_limits():
         "nup_log2n": _macro_list(_read("nup.hip"), "BFIR_FOR_NUP_LOG2N"),
         "fade_log2n": _macro_list(_read("fade.hip"), "BFIR_FOR_FADE_LOG2N"),
         "mat_small_max": _const(kh, "BFIR_MAT_SMALL_MAX"),
+        "levels_log2n": _macro_list(_read("levels.hip"), "BFIR_FOR_LEVELS_LOG2N"),
+        "lfade_log2n": _macro_list(_read("lfade.hip"), "BFIR_FOR_LFADE_LOG2N"),
+        "level_rings": _const(kh, "BFIR_LEVEL_RINGS"),
+        "max_levels": _max_levels(),
     }
+
+
+def _max_levels():
+    """BFIR_MAX_LEVELS of the public header."""
+    with open(os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "bfir_hip.h")) as f:
+        m = re.search(r"#define\s+BFIR_MAX_LEVELS\s+(\d+)", f.read())
+    assert m
+    return int(m.group(1))
+
+
+def reachable_instances(lim, log2n, nr_min):
+    """{(LOG2N, NR)} of k_inv_levels (nr_min = 2: one ring of a non-fading chunk is k_inv_nup's) or k_inv_lfade (nr_min = 1)
+    that an engine can launch, and the instances the sources build.  NR counts the contributing tails; bfir_engine_create_levels
+    wants ratios >= 2 and every L_k supported, so NR tails on a head of L = 2^(LOG2N - 1) need 2^(LOG2N - 1) 2^NR <= the
+    largest supported fp32 length."""
+    top = max(supported_lengths(lim, 4))
+    built = {(lg, nr) for lg in log2n for nr in range(nr_min, lim["level_rings"] + 1)}
+    return {(lg, nr) for lg, nr in built if (1 << (lg - 1)) << nr <= top}, built
 
 
 def fade_fused_rule():
@@ -116,6 +139,15 @@ def supported_set(lim):
         "fade_general64": (8, f64),
         "matrix32": (4, f32),
         "matrix64": (8, f64),
+        # multi-level engines: the head's L with three levels of ratio 2 (the smallest) that the precision takes; the fused
+        # back end where k_inv_levels has an instance of 2L points
+        "levels_fused": (4, [L for L in [1 << (n - 1) for n in lim["levels_log2n"]] if 4 * L in f32]),
+        "levels_general32": (4, [L for L in f32 if 4 * L in f32]),
+        "levels_general64": (8, [L for L in f64 if 4 * L in f64]),
+        # fades on split engines: from two levels (a tail of 2L) up
+        "lfade_fused": (4, [L for L in [1 << (n - 1) for n in lim["lfade_log2n"]] if 2 * L in f32]),
+        "lfade_general32": (4, [L for L in f32 if 2 * L in f32]),
+        "lfade_general64": (8, [L for L in f64 if 2 * L in f64]),
     }
     return {(f, s, L) for f, (s, Ls) in fams.items() for L in Ls}
 
@@ -187,7 +219,7 @@ REFUSALS = [(8, 16384, "ERR_UNSUPPORTED"), (4, 8, "ERR_UNSUPPORTED"), (8, 8, "ER
 
 
 # ---- the engine kinds on top of the plain diagonal engine ---------------------------------------------------------------
-# Same recipe as above for all three: flat_ir filters (a distinct one per channel or per (output, input) pair) cast to the
+# Same recipe as above for all of them: flat_ir filters (a distinct one per channel or per (output, input) pair) cast to the
 # working precision, uniform noise with the odd channels (inputs) at 1/8, the float64 / long-double reference, the
 # per-block, per-channel norm of block_errors and the tolerance of tolerance() -- the project's own, nothing new.
 def _kind_cell(family, s, L, C, fin, fout, tag, **more):
@@ -278,13 +310,103 @@ def _build_matrix_cells():
     return cells
 
 
+# Multi-level engines (csrc/levels.hip) and fades on two-level and multi-level engines (csrc/lfade.hip): the smallest
+# geometry bfir_engine_create_levels accepts, ratios of 2 throughout and every D_k = L_k, so a cell costs as little as its
+# transform sizes allow.  Two levels are BrutefirNup(L, 2, 2, 2).
+LEVEL_BLOCKS = {2: (2, 2), 3: (2, 1, 2), 4: (2, 1, 1, 2)}
+
+
+def level_geometry(L, blocks, ratios):
+    """([L_k], [D_k] with D_n = capacity appended) in samples."""
+    Ls, D = [], [0]
+    for b, r in zip(blocks, ratios):
+        Ls.append(L if not Ls else Ls[-1] * r)
+        D.append(D[-1] + b * Ls[-1])
+    return Ls, D
+
+
+def _levels_cell(family, s, L, C, fin, fout, n, fade=None):
+    """n levels; taps end RAGGED short of the capacity (the last level's last partition is ragged).  Without a fade,
+    nb = D_last / L + r_last (blocks_last + 2) + 3 blocks: the deepest delay line and its ring both wrap.  With one (fade,
+    added to lg + C in the gain rule of FADE_CELLS) it starts at t0 = D_last / L + r_last + 1, where every ring contributes
+    (NR of k_inv_lfade = n - 1) and which is odd, so inside a block of every level: every level catches up; K = FADE_K blocks
+    and 2 r_last + 1 more."""
+    blocks, ratios = LEVEL_BLOCKS[n], (1,) + (2,) * (n - 1)
+    Ls, D = level_geometry(L, blocks, ratios)
+    r_last = Ls[-1] // L
+    more = {"blocks": blocks, "ratios": ratios, "taps": D[-1] - RAGGED}
+    tag = "-%dlv" % n
+    if fade is None:
+        more["nb"] = D[-2] // L + r_last * (blocks[-1] + 2) + 3
+        more["back"] = "fused" if family == "levels_fused" else "general"
+    else:
+        lg = L.bit_length() - 1
+        more["new_gain"] = 0.125 if (lg + C + fade) % 2 == 0 else 8.0
+        more["t0"] = D[-2] // L + r_last + 1
+        more["nb"] = more["t0"] + FADE_K + 2 * r_last + 1
+        tag += "-g%g" % more["new_gain"]
+    return _kind_cell(family, s, L, C, fin, fout, tag, **more)
+
+
+def _build_levels_cells():
+    cells = []
+    add = lambda *a: cells.append(_levels_cell(*a))
+    for n, Ls in ((3, (512, 1024, 2048, 4096)), (4, (512, 1024, 2048))):    # k_inv_levels: fp32, float frames, an even count;
+        for L in Ls:                                  # a run of n levels passes through 0 .. n - 1 contributing rings
+            add("levels_fused", 4, L, 2, FLOAT_LE, FLOAT_LE, n)
+        add("levels_fused", 4, Ls[1], 8, FLOAT_LE, FLOAT_LE, n)
+    for L in [1 << lg for lg in range(4, 13)]:        # k_levels_combine<float>: an odd count anywhere, any count below the pair plans
+        add("levels_general32", 4, L, 3, FLOAT_LE, FLOAT_LE, 3)
+        if L < 512:
+            add("levels_general32", 4, L, 2, FLOAT_LE, FLOAT_LE, 3)
+        if L in (16, 256, 2048):                      # four levels: the smallest and the largest head there is, one between
+            add("levels_general32", 4, L, 3, FLOAT_LE, FLOAT_LE, 4)
+    for L in [1 << lg for lg in range(4, 12)]:        # k_levels_combine<double>
+        for C in (2, 3):
+            add("levels_general64", 8, L, C, FLOAT64_LE, FLOAT64_LE, 3)
+        if L in (16, 1024):                           # four levels: the smallest and the largest head there is
+            add("levels_general64", 8, L, 2, FLOAT64_LE, FLOAT64_LE, 4)
+        if L in (64, 1024):                           # the plug-in's shape: fp64 arithmetic, float32 stereo frames
+            add("levels_general64", 8, L, 2, FLOAT_LE, FLOAT_LE, 3)
+    return cells
+
+
+def _build_lfade_cells():
+    cells = []
+    add = lambda *a: cells.append(_levels_cell(*a))
+    # k_inv_lfade<LOG2N, NR>: NR = n - 1 rings at every size n levels fit, any channel count.  C alternates with the size, so
+    # lg + C is the same all along a row; half the index in the row takes its place in the gain rule: the direction changes
+    # every second size, and each channel count meets both
+    for n, Ls in ((2, (512, 1024, 2048, 4096, 8192)), (3, (512, 1024, 2048, 4096)), (4, (512, 1024, 2048))):
+        for i, L in enumerate(Ls):
+            add("lfade_fused", 4, L, 2 + (i + n) % 2, FLOAT_LE, FLOAT_LE, n, i // 2)
+    for L in (16, 32, 64, 128, 256):                  # k_lfade_sum<float>: below the pair plans
+        lg = L.bit_length() - 1
+        add("lfade_general32", 4, L, 2, FLOAT_LE, FLOAT_LE, 3, 0)
+        add("lfade_general32", 4, L, 3, FLOAT_LE, FLOAT_LE, 4 if lg % 2 == 0 else 2, 0)
+    for L, n in ((512, 2), (1024, 3), (2048, 4), (4096, 3), (8192, 2)):     # ... and inside them where the output frames are not FLOAT_LE
+        add("lfade_general32", 4, L, 2, FLOAT_LE, FLOAT64_LE, n, 0)
+    for L in [1 << lg for lg in range(4, 12)]:        # k_lfade_sum<double>
+        add("lfade_general64", 8, L, 2, FLOAT64_LE, FLOAT64_LE, 3, 0)
+        if L in (64, 1024):
+            add("lfade_general64", 8, L, 3, FLOAT_LE, FLOAT_LE, 3, 0)
+    add("lfade_general64", 8, 4096, 2, FLOAT64_LE, FLOAT64_LE, 2, 0)       # a tail of 8192, the largest fp64 transform
+    add("lfade_general64", 8, 1024, 3, FLOAT64_LE, FLOAT64_LE, 4, 0)       # four levels, 8192 again
+    return cells
+
+
 NUP_CELLS = _build_nup_cells()
 FADE_CELLS = _build_fade_cells()
 MATRIX_CELLS = _build_matrix_cells()
-KIND_CELLS = NUP_CELLS + FADE_CELLS + MATRIX_CELLS
+LEVELS_CELLS = _build_levels_cells()
+LFADE_CELLS = _build_lfade_cells()
+KIND_CELLS = NUP_CELLS + FADE_CELLS + MATRIX_CELLS + LEVELS_CELLS + LFADE_CELLS
 
 # bfir_engine_create_nup must fail: (realsize, L, tail_ratio, error name) -- the tail's partition is past the range
 NUP_REFUSALS = [(4, 16384, 2, "ERR_UNSUPPORTED"), (8, 8192, 2, "ERR_UNSUPPORTED")]
+
+# bfir_engine_create_levels must fail: (realsize, L, levels, error name) -- the first shape past each limit
+LEVELS_REFUSALS = [(4, 8192, 3, "ERR_UNSUPPORTED"), (4, 4096, 4, "ERR_UNSUPPORTED"), (8, 4096, 3, "ERR_UNSUPPORTED")]
 
 
 # ---- test data and the float64 reference ------------------------------------------------------------------------
@@ -388,14 +510,14 @@ def reference(orc, x, h):
 
 
 def nup_data(orc, cell):
-    """(h, x) of a two-level cell: taps in the working precision, frames in the input format."""
+    """(h, x) of a two-level or multi-level cell: taps in the working precision, frames in the input format."""
     rng = _rng(cell)
     h = [v.astype(orc.real_dtype(cell["s"])) for v in flat_ir(rng, cell["C"], cell["taps"])]
     return h, _noise(orc, rng, cell)
 
 
 def fade_data(orc, cell):
-    """(h_old, h_new, x) of a fade cell."""
+    """(h_old, h_new, x) of a fade cell (FADE_CELLS, LFADE_CELLS)."""
     rng = _rng(cell)
     dt = orc.real_dtype(cell["s"])
     g_old, g_new = (1.0, 0.125) if cell["new_gain"] < 1.0 else (0.125, 1.0)

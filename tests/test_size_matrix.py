@@ -20,9 +20,10 @@ def test_matrix_covers_exactly_what_the_sources_support():
     assert sorted(want - have) == [], "sizes the build supports that no cell runs"
     assert sorted(have - want) == [], "cells at sizes the build does not support"
     # ... list by list: a family's cells are in the list of its kind and nowhere else
-    for prefix, cells in (("nup_", SM.NUP_CELLS), ("fade_", SM.FADE_CELLS), ("matrix", SM.MATRIX_CELLS)):
+    for prefix, cells in (("nup_", SM.NUP_CELLS), ("fade_", SM.FADE_CELLS), ("matrix", SM.MATRIX_CELLS),
+                          ("levels_", SM.LEVELS_CELLS), ("lfade_", SM.LFADE_CELLS)):
         assert {k for k in want if k[0].startswith(prefix)} == {(c["family"], c["s"], c["L"]) for c in cells}
-    assert not [c["id"] for c in SM.CELLS if c["family"].startswith(("nup_", "fade_", "matrix"))]
+    assert not [c["id"] for c in SM.CELLS if c["family"].startswith(("nup_", "fade_", "matrix", "levels_", "lfade_"))]
 
 
 def test_matrix_refusals_are_the_unsupported_neighbours():
@@ -42,6 +43,9 @@ def test_source_limits_parse():
     # pair_supported for both), one instance per plan
     assert lim["nup_log2n"] == lim["pair_log2n"] and lim["fade_log2n"] == lim["pair_log2n"]
     assert max(SM.MATRIX_CALLS[0], 1) <= lim["mat_small_max"] < SM.MATRIX_CALLS[1]
+    # ... and so do the fused back ends of the multi-level engines and of the fades on split engines; one ring per tail
+    assert lim["levels_log2n"] == lim["lfade_log2n"] == lim["pair_log2n"]
+    assert lim["level_rings"] == lim["max_levels"] - 1 and max(SM.LEVEL_BLOCKS) == lim["max_levels"]
 
 
 def test_cells_set_every_path_switch_and_are_unique():
@@ -104,6 +108,17 @@ def test_kind_cells_are_the_ones_the_sweep_is_made_of():
         "matrix32": len(f32) + 3,
         "matrix64": len(f64) + 1,
     }
+    # multi-level engines and fades on split engines: heads that take n levels of ratio 2
+    fit = lambda Ls, full, n: [L for L in Ls if (L << (n - 1)) in full]
+    want.update({
+        "levels_fused": len(fit(fused, f32, 3)) + len(fit(fused, f32, 4)) + 2,     # C = 2 per depth and size; C = 8 once per depth
+        # C = 3; C = 2 below the pair plans; four levels at three sizes
+        "levels_general32": len(fit(f32, f32, 3)) + len([L for L in fit(f32, f32, 3) if L < min(fused)]) + 3,
+        "levels_general64": 2 * len(fit(f64, f64, 3)) + 2 + 2,             # C = 2, 3; four levels twice; the plug-in's frames twice
+        "lfade_fused": sum(len(fit(fused, f32, n)) for n in (2, 3, 4)),    # one per reachable (LOG2N, NR)
+        "lfade_general32": 2 * len([L for L in fit(f32, f32, 2) if L < min(fused)]) + len(fit(fused, f32, 2)),
+        "lfade_general64": len(fit(f64, f64, 3)) + 2 + 1 + 1,               # the plug-in's frames twice; the 8192 tail; four levels
+    })
     assert dict(collections.Counter(c["family"] for c in SM.KIND_CELLS)) == want
 
 
@@ -139,6 +154,94 @@ def test_fade_cells_follow_the_engines_rule():
         assert {c["new_gain"] for c in SM.FADE_CELLS if c["family"] == "fade_fused" and c["C"] == Cn} == {0.125, 8.0}
 
 
+def _cell_instances(cell):
+    """(LOG2N, NR) of the fused inverse kernels a cell runs: a non-fading run of n levels passes through 0 .. n - 1 contributing
+    rings, of which k_inv_levels takes 2 and up; a fade cell starts its fade with all n - 1 contributing."""
+    lg, tails = cell["L"].bit_length(), len(cell["blocks"]) - 1             # the transform has 2 L points
+    return {(lg, nr) for nr in range(2, tails + 1)} if cell["family"] == "levels_fused" else {(lg, tails)}
+
+
+def test_fused_level_cells_run_exactly_the_reachable_instances():
+    """k_inv_levels<LOG2N, NR> and k_inv_lfade<LOG2N, NR>: every instance an engine can launch is run by a cell, and the ones
+    no engine can launch are the three largest of each kernel.  Relaxing bfir_engine_create_levels (or adding a size to either
+    macro) fails here until cells follow."""
+    lim = SM.source_limits()
+    for fam, cells, log2n, nr_min in (("levels_fused", SM.LEVELS_CELLS, lim["levels_log2n"], 2),
+                                      ("lfade_fused", SM.LFADE_CELLS, lim["lfade_log2n"], 1)):
+        reach, built = SM.reachable_instances(lim, log2n, nr_min)
+        run = set().union(*[_cell_instances(c) for c in cells if c["family"] == fam])
+        assert run == reach, (fam, sorted(reach - run), sorted(run - reach))
+        assert built - reach == {(14, 2), (14, 3), (13, 3)}, fam
+        assert len(built) == len(log2n) * (lim["level_rings"] + 1 - nr_min)
+
+
+def test_level_cells_follow_the_rules_of_create_levels():
+    """bfir_engine_create_levels: ratios[0] = 1, the others powers of two >= 2, D_k >= L_k, every L_k supported and at most
+    16384; the geometry and run lengths the cells are made with; the back end each family name stands for."""
+    lim = SM.source_limits()
+    pair_plans = [1 << (n - 1) for n in lim["pair_log2n"]]
+    for c in SM.LEVELS_CELLS + SM.LFADE_CELLS:
+        n, L, blocks, ratios = len(c["blocks"]), c["L"], c["blocks"], c["ratios"]
+        assert 2 <= n <= lim["max_levels"] and (n >= 3 or c in SM.LFADE_CELLS), c["id"]
+        assert blocks == SM.LEVEL_BLOCKS[n] and ratios == (1,) + (2,) * (n - 1), c["id"]
+        Ls, D = SM.level_geometry(L, blocks, ratios)
+        ok = SM.supported_lengths(lim, c["s"])
+        assert all(Lk in ok and Lk <= 16384 for Lk in Ls), c["id"]
+        assert all(D[k] >= Ls[k] for k in range(1, n)), c["id"]
+        assert c["in_fmt"] in (SM.FLOAT_LE, SM.FLOAT64_LE) and c["out_fmt"] in (SM.FLOAT_LE, SM.FLOAT64_LE)
+        assert 0 < D[-1] - c["taps"] < Ls[-1], c["id"]                   # ends inside the last partition of the last level
+        r_last = Ls[-1] // L
+        if c in SM.LEVELS_CELLS:
+            assert c["nb"] == D[-2] // L + r_last * (blocks[-1] + 2) + 3
+            # engine.hip, choose_path: e->pair of the head (channel pairs; a split engine has no pairs in time)
+            pair = c["s"] == 4 and c["in_fmt"] == c["out_fmt"] == SM.FLOAT_LE and c["C"] % 2 == 0 and L in pair_plans
+            assert pair == (c["back"] == "fused") == (c["family"] == "levels_fused"), c["id"]
+        else:
+            assert c["t0"] == D[-2] // L + r_last + 1 and all(c["t0"] % (Lk // L) for Lk in Ls[1:]), c["id"]
+            assert c["nb"] == c["t0"] + SM.FADE_K + 2 * r_last + 1
+            assert SM.fade_is_fused(lim, c["s"], L, c["out_fmt"]) == (c["family"] == "lfade_fused"), c["id"]
+    # the coverage the families are there for
+    def have(cells, fam, **kv):
+        return {c["L"] for c in cells if c["family"] == fam and all(
+            (len(c["blocks"]) if k == "n" else c[k]) == v for k, v in kv.items())}
+    f32, f64 = SM.supported_lengths(lim, 4), SM.supported_lengths(lim, 8)
+    fit = lambda Ls, full, n: {L for L in Ls if (L << (n - 1)) in full}
+    lo32 = {L for L in f32 if L < min(pair_plans)}
+    LV, LF = SM.LEVELS_CELLS, SM.LFADE_CELLS
+    assert all(c["C"] % 2 == 0 for c in LV if c["family"] == "levels_fused")
+    for n in (3, 4):
+        assert have(LV, "levels_fused", n=n, C=2) == fit(pair_plans, f32, n)
+        assert len(have(LV, "levels_fused", n=n, C=8)) == 1
+    assert have(LV, "levels_general32", n=3, C=3) == fit(f32, f32, 3) and have(LV, "levels_general32", n=3, C=2) == lo32
+    four = have(LV, "levels_general32", n=4)
+    assert len(four) == 3 and {min(f32), max(fit(f32, f32, 4))} <= four
+    for Cn in (2, 3):
+        assert have(LV, "levels_general64", n=3, C=Cn, out_fmt=SM.FLOAT64_LE) == fit(f64, f64, 3)
+    assert have(LV, "levels_general64", n=4) == {min(f64), max(fit(f64, f64, 4))}
+    assert len(have(LV, "levels_general64", out_fmt=SM.FLOAT_LE, in_fmt=SM.FLOAT_LE)) == 2
+    for n in (2, 3, 4):
+        assert have(LF, "lfade_fused", n=n) == fit(pair_plans, f32, n)
+        assert {c["new_gain"] for c in LF if c["family"] == "lfade_fused" and len(c["blocks"]) == n} == {0.125, 8.0}
+        row = [c["C"] for c in LF if c["family"] == "lfade_fused" and len(c["blocks"]) == n]
+        assert set(row) == {2, 3} and all(a != b for a, b in zip(row, row[1:]))
+        both = {(c["C"], c["new_gain"]) for c in LF if c["family"] == "lfade_fused" and len(c["blocks"]) == n}
+        assert len(both) == min(4, len(row)), (n, both)                  # each channel count fades both ways where the row has four sizes
+        for fam in ("lfade_general32", "lfade_general64"):
+            assert have(LF, fam, n=n), (fam, n)
+    for fam in ("lfade_fused", "lfade_general32", "lfade_general64"):
+        assert {c["new_gain"] for c in LF if c["family"] == fam} == {0.125, 8.0}
+    for Cn in (2, 3):
+        assert have(LF, "lfade_general32", C=Cn, out_fmt=SM.FLOAT_LE) == lo32
+    assert have(LF, "lfade_general32", out_fmt=SM.FLOAT64_LE) == fit(pair_plans, f32, 2)
+    assert have(LF, "lfade_general64", n=3, out_fmt=SM.FLOAT64_LE) == fit(f64, f64, 3)
+    assert max(f64) // 2 in have(LF, "lfade_general64", n=2)
+    assert len(have(LF, "lfade_general64", out_fmt=SM.FLOAT_LE, in_fmt=SM.FLOAT_LE)) == 2
+    # the refusals: the first shape past each limit
+    assert SM.LEVELS_REFUSALS == [(4, 2 * max(fit(f32, f32, 3)), 3, "ERR_UNSUPPORTED"),
+                                  (4, 2 * max(fit(f32, f32, 4)), 4, "ERR_UNSUPPORTED"),
+                                  (8, 2 * max(fit(f64, f64, 3)), 3, "ERR_UNSUPPORTED")]
+
+
 def _oracle_uniform(orc, cell, h, x):
     L = cell["L"]
     o = orc.Engine(L, -(-cell["taps"] // L), cell["s"], cell["C"], cell["in_fmt"], cell["out_fmt"])
@@ -154,13 +257,13 @@ def test_kind_cell_leaves_a_margin(orc, cell):
     """No cell sits at the edge of its tolerance because of its own data: the oracle's uniform engine on the cell's data
     is within half the tolerance of the float64 reference, in the norm the GPU test uses."""
     L, s = cell["L"], cell["s"]
-    if cell in SM.NUP_CELLS:
+    if cell in SM.NUP_CELLS or cell in SM.LEVELS_CELLS:
         h, x = SM.nup_data(orc, cell)
         y, ref = _oracle_uniform(orc, cell, h, x), SM.reference(orc, x, h)
-    elif cell in SM.FADE_CELLS:
+    elif cell in SM.FADE_CELLS or cell in SM.LFADE_CELLS:
         h_old, h_new, x = SM.fade_data(orc, cell)
-        y, _, _ = fade_expected(orc, L, SM.B, s, cell["C"], h_old, h_new, x, cell["t0"], SM.FADE_K, cell["in_fmt"],
-                                cell["out_fmt"])
+        y, _, _ = fade_expected(orc, L, -(-cell["taps"] // L), s, cell["C"], h_old, h_new, x, cell["t0"], SM.FADE_K,
+                                cell["in_fmt"], cell["out_fmt"])
         ref = SM.fade_reference(orc, cell, h_old, h_new, x)
     else:
         rows, x = SM.matrix_data(orc, cell)

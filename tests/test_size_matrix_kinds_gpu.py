@@ -1,8 +1,9 @@
 """The size matrix for the engine kinds on top of the plain diagonal engine (tests/size_matrix.py: NUP_CELLS, FADE_CELLS,
-MATRIX_CELLS): two-level engines, crossfaded coefficient changes and matrix engines at every transform size their kernels
-have, with flat-envelope filters, odd channels at 1/8 and the per-block, per-channel norm, each against a float64 /
-long-double reference computed here from the frames and taps actually sent -- and against the oracle, as the plain sweep
-does (tests/test_size_matrix_gpu.py)."""
+MATRIX_CELLS, LEVELS_CELLS, LFADE_CELLS): two-level engines, crossfaded coefficient changes, matrix engines, multi-level
+engines and crossfaded coefficient changes on split engines at every transform size their kernels have, with
+flat-envelope filters, odd channels at 1/8 and the per-block, per-channel norm, each against a float64 / long-double
+reference computed here from the frames and taps actually sent -- and against the oracle, as the plain sweep does
+(tests/test_size_matrix_gpu.py)."""
 import numpy as np
 import pytest
 
@@ -53,7 +54,7 @@ def _run_calls(eng, x, L, cuts):
 
 
 def _engine_lines(creation_log):
-    made = [ln for ln in creation_log if ln.startswith("bfir engine: ") and "two levels" not in ln]
+    made = [ln for ln in creation_log if ln.startswith("bfir engine: ") and "two levels" not in ln and " levels, " not in ln]
     return [dict(kv.split("=") for kv in ln.split(". ")[-1].split()) for ln in made]
 
 
@@ -165,3 +166,97 @@ def test_matrix_size_matrix(orc, bfir, creation_log, cell):
     assert y.shape == (cell["nb"] * L, n_out)
 
     _check(cell, y, SM.matrix_reference_conv(orc, rows, x), matrix_reference(orc, L, SM.B, s, rows, x))
+
+
+# ---- multi-level engines ---------------------------------------------------------------------------------------------
+def _oracle_uniform(orc, cell, h, x):
+    L = cell["L"]
+    o = orc.Engine(L, -(-cell["taps"] // L), cell["s"], cell["C"], cell["in_fmt"], cell["out_fmt"])
+    assert o.set_coeff(h) == 0
+    rc, y = o.run(x)
+    assert rc == 0
+    o.close()
+    return y
+
+
+@pytest.mark.parametrize("cell", SM.LEVELS_CELLS, ids=[c["id"] for c in SM.LEVELS_CELLS])
+def test_levels_size_matrix(orc, bfir, creation_log, cell):
+    s, L, Cn, blocks, ratios, nb = cell["s"], cell["L"], cell["C"], cell["blocks"], cell["ratios"], cell["nb"]
+    Ls, D = SM.level_geometry(L, blocks, ratios)
+    h, x = SM.nup_data(orc, cell)
+
+    with env_override(**cell["env"]):
+        del creation_log[:]
+        eng = bfir.BrutefirLevels(L, blocks, ratios, s, Cn, cell["in_fmt"], cell["out_fmt"])
+        made = [ln for ln in creation_log if " levels, " in ln]
+        names = ", ".join("%d x %d" % (Lk, b) for Lk, b in zip(Ls, blocks))
+        assert made == ["bfir engine: %d levels, %s; back end %s." % (len(blocks), names, cell["back"])], creation_log
+        assert len(_engine_lines(creation_log)) == len(blocks), creation_log     # one diagonal engine per level, no more
+        eng.set_chunk(3)
+        assert eng.set_coeff(h) == 0
+        # partition spectra of every level, the ragged last partition of the last level included, in the grouped layout
+        for level, (Lp, Bp) in enumerate(zip(Ls, blocks)):
+            for c in range(Cn):
+                for b in range(Bp):
+                    want = SM.grouped_spectrum(h[c][D[level] + b * Lp:D[level] + (b + 1) * Lp], Lp, 1.0)
+                    got = eng.coeff_block(level, c, b).astype(np.float64)
+                    assert np.abs(got - want).max() <= TOL[s] * np.abs(want).max(), (level, c, b)
+        # a call that ends inside a block of the last level, one block alone (the latency path), then the rest
+        r_last = Ls[-1] // L
+        y = _run_calls(eng, x, L, (0, r_last + 1, r_last + 2, nb))
+        eng.close()
+
+    _check(cell, y, SM.reference(orc, x, h), _oracle_uniform(orc, cell, h, x))
+
+
+@pytest.mark.parametrize("s,L,n,err", SM.LEVELS_REFUSALS)
+def test_levels_refuses_size(bfir, s, L, n, err):
+    with pytest.raises(bfir.BfirError) as ei:
+        bfir.BrutefirLevels(L, SM.LEVEL_BLOCKS[n], (1,) + (2,) * (n - 1), s, 2)
+    assert ei.value.code == getattr(bfir, err)
+    # nothing left behind: the device still makes and runs a three-level engine of a supported size
+    dt = np.float32 if s == 4 else np.float64
+    eng = bfir.BrutefirLevels(1024, SM.LEVEL_BLOCKS[3], (1, 2, 2), s, 2)
+    taps = 4 * 1024 + 10                                                    # ten taps into the last level
+    assert eng.set_coeff([np.ones(taps, dt) / 8192] * 2) == 0
+    rc, y = eng.run(np.ones((16 * 1024, 2), dt))
+    assert rc == 0 and np.all(np.isfinite(y))
+    assert abs(float(y[-1, 0]) - taps / 8192) <= 1e-5                       # all taps under a constant input: their sum
+    eng.close()
+
+
+# ---- crossfaded coefficient changes on two-level and multi-level engines --------------------------------------------------
+@pytest.mark.parametrize("cell", SM.LFADE_CELLS, ids=[c["id"] for c in SM.LFADE_CELLS])
+def test_lfade_size_matrix(orc, bfir, creation_log, cell):
+    s, L, Cn, blocks, ratios = cell["s"], cell["L"], cell["C"], cell["blocks"], cell["ratios"]
+    t0, nb, K = cell["t0"], cell["nb"], SM.FADE_K
+    fused = cell["family"] == "lfade_fused"
+    h_old, h_new, x = SM.fade_data(orc, cell)
+
+    with env_override(**cell["env"]):
+        if len(blocks) == 2:
+            eng = bfir.BrutefirNup(L, blocks[0], ratios[1], blocks[1], s, Cn, cell["in_fmt"], cell["out_fmt"])
+        else:
+            eng = bfir.BrutefirLevels(L, blocks, ratios, s, Cn, cell["in_fmt"], cell["out_fmt"])
+        eng.set_chunk(2)                     # the fade's K = 3 blocks are cut into 2 + 1: the second part starts at m0 = 2 L
+        assert eng.set_coeff(h_old) == 0
+        rc, y0 = eng.run(x[:t0 * L])
+        assert rc == 0
+        assert eng.fade_to(h_new, K) == 0 and eng.fade_remaining() == K
+        # the first chunk of the fade on its own, profiled: the fused fade stores the frames itself, the general one ends in
+        # k_stage_out (outside a fade the general back end of a split engine stages its output as well, so only the fade counts)
+        eng.set_profiling(True)
+        rc, y1 = eng.run(x[t0 * L:(t0 + 2) * L])
+        assert rc == 0 and eng.fade_remaining() == K - 2
+        staged = eng.profile()["k_stage_out"][1]
+        assert (staged == 0) if fused else (staged > 0), staged
+        eng.set_profiling(False)
+        # the fade's last block (m0 = 2 L), the swap of the sets and the blocks after it in one call
+        rc, y2 = eng.run(x[(t0 + 2) * L:])
+        assert rc == 0 and eng.fade_remaining() == 0
+        eng.close()
+    y = np.concatenate([y0, y1, y2])
+    assert y.shape == (nb * L, Cn)
+
+    want, _, _ = fade_expected(orc, L, -(-cell["taps"] // L), s, Cn, h_old, h_new, x, t0, K, cell["in_fmt"], cell["out_fmt"])
+    _check(cell, y, SM.fade_reference(orc, cell, h_old, h_new, x), want)
