@@ -194,6 +194,14 @@ struct bfir_engine {
     // D_k = lv_D[i] L on; output = ((y_head + z_1[n - D_1]) + z_2[n - D_2]) + z_3[n - D_3].  Two levels are n_tail = 1.
     bool nup = false, nup_tail = false;
     bool levels = false;                   // created by bfir_engine_create_levels: a kind of its own at the C ABI
+    // created by bfir_engine_create_matrix_levels, a kind of its own too: the head and every tail are matrix engines -- the
+    // delay lines, raw tails and pbuf count by the C inputs; the products, the time rings, tout, the overflow shards and the
+    // output frames by the Co outputs -- and every level's MAC is k_mac_matrix
+    bool mlevels = false;
+    // the head of a split engine: its contributing chunks take the fused back end (nup.hip, levels.hip, mlevels.hip).  A
+    // diagonal engine's is its pair path; a matrix engine's is chosen by the output side alone (choose_path), whatever the
+    // front end does
+    bool back_fused = false;
     int n_tail = 0;
     bfir_engine *tail[BFIR_MAX_LEVELS - 1] = {nullptr, nullptr, nullptr};
     int lv_r[BFIR_MAX_LEVELS - 1] = {0, 0, 0}, lv_D[BFIR_MAX_LEVELS - 1] = {0, 0, 0};   // L_k / L and D_k / L (head blocks)
@@ -291,7 +299,7 @@ static int alloc_work(bfir_engine *e, int chunk)
     HIP_TRY(hipMalloc(&X, (size_t)e->GC * ring * cb));
     HIP_TRY(hipMalloc(&Y0, (size_t)e->GCo * chunk * cb));
     HIP_TRY(hipMalloc(&Y1, (size_t)e->GCo * chunk * cb));
-    if (e->nup && !e->pair) HIP_TRY(hipMalloc(&tout, (size_t)e->GCo * chunk * e->L * e->s));   // the general nup back end's planar sum
+    if (e->nup && !e->back_fused) HIP_TRY(hipMalloc(&tout, (size_t)e->GCo * chunk * e->L * e->s));   // the general nup back end's planar sum
     if (!e->pair && !e->direct) {   // the pair and direct paths have no planar time buffers
         HIP_TRY(hipMalloc(&tin0, (size_t)e->GC * chunk * e->L * e->s));
         HIP_TRY(hipMalloc(&tin1, (size_t)e->GC * chunk * e->L * e->s));
@@ -332,7 +340,10 @@ static void choose_path(bfir_engine *e)
     if (e->matrix) {
         // channel pairs on both sides or direct mode: time pairs transform blocks t, t + 1 together, so where a launch
         // starts would change the bits of its blocks (a matrix engine's outputs do not depend on the chunking)
-        e->pair = e->pair && e->C % 2 == 0 && e->Co % 2 == 0;
+        // A level of a multi-level matrix engine pairs by its INPUT side alone: its forward kernel touches nothing else, a
+        // tail's back end is a planar inverse, and the head's back ends take an odd output count (queue_inv, queue_inv_nup)
+        const bool split = e->nup || e->nup_tail;
+        e->pair = e->pair && e->C % 2 == 0 && (split || e->Co % 2 == 0);
         e->pair_tp = false;
         e->pair_cap = e->pair;
     }
@@ -356,6 +367,10 @@ static void choose_path(bfir_engine *e)
         e->pair = e->pair && !e->pair_tp;
         e->pair_tp = false;
         e->direct = !e->pair;
+        // the fused back ends read Y as (re, im) pairs and write FLOAT_LE frames: nothing in them depends on the front end,
+        // so a matrix head takes them by its output side alone (an odd count: the last output through k_inv_lone)
+        e->back_fused = e->nup && (e->matrix ? e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L)
+                                             : e->pair);
     }
     // fp64 engines whose transforms the run kernels take keep their spectra -- delay line, filter partitions, products --
     // as (re, im) PAIRS like the fp32 engines, not in the reference's groups of four: one 16-byte access per bin in the
@@ -436,7 +451,7 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
     if (rc != 0) { *err = (rc == -1) ? BFIR_ERR_UNSUPPORTED : BFIR_ERR_HIP; delete e; return nullptr; }
     auto fail = [&](int code) { *err = code; bfir_engine_destroy(e); return (bfir_engine *)nullptr; };
     if (e->pair || e->direct) {
-        if (e->pair && fft_plan_create(&e->plan2, 2 * filter_length, 4) != 0) return fail(BFIR_ERR_HIP);
+        if ((e->pair || e->back_fused) && fft_plan_create(&e->plan2, 2 * filter_length, 4) != 0) return fail(BFIR_ERR_HIP);
         const size_t tb = (size_t)e->n_eng * e->L * e->C * e->in_bytes;     // raw input frames of one block
         for (int st = 0; st < 2; st++)
             for (int i = 0; i < 2; i++) {
@@ -545,13 +560,13 @@ static int alloc_zring(bfir_engine *e, int i, int chunk)
     for (void **zr : rings) {
         if (zr == &t->zring2 && !t->zring2) continue;
         void *z = nullptr;
-        HIP_TRY(hipMalloc(&z, (size_t)t->GC * zb * blk));
-        HIP_TRY(hipMemset(z, 0, (size_t)t->GC * zb * blk));
+        HIP_TRY(hipMalloc(&z, (size_t)t->GCo * zb * blk));
+        HIP_TRY(hipMemset(z, 0, (size_t)t->GCo * zb * blk));
         if (*zr) {
             const long long lo = std::max(t->z_from, t->z_next - t->zblocks);
             for (long long j = lo; j < t->z_next; j++)
                 HIP_TRY(hipMemcpy2D((char *)z + (size_t)(j % zb) * blk, (size_t)zb * blk, (char *)*zr + (size_t)(j % t->zblocks) * blk,
-                                    (size_t)t->zblocks * blk, blk, t->GC, hipMemcpyDeviceToDevice));
+                                    (size_t)t->zblocks * blk, blk, t->GCo, hipMemcpyDeviceToDevice));
             HIP_TRY(hipDeviceSynchronize());
             (void)hipFree(*zr);
         }
@@ -562,19 +577,20 @@ static int alloc_zring(bfir_engine *e, int i, int chunk)
 }
 
 // The head (level 0) and its tails, for arguments that have passed the checks of the two entry points below.
+// matrix: `channels` inputs and `channels_out` outputs at every level (bfir_engine_create_matrix_levels); else the two are equal
 static bfir_engine *create_split(int filter_length, int n_levels, const int *blocks, const int *ratios, int realsize, int channels,
-                                 int in_format, int out_format, int device, int *err)
+                                 int channels_out, bool matrix, int in_format, int out_format, int device, int *err)
 {
-    bfir_engine *e = engine_create(1, filter_length, blocks[0], realsize, channels, channels, false, in_format, out_format, 44100,
-                                   0, device, err, 1);
+    bfir_engine *e = engine_create(1, filter_length, blocks[0], realsize, channels, channels_out, matrix, in_format, out_format,
+                                   44100, 0, device, err, 1);
     if (!e) return nullptr;
     auto fail = [&](int code) { *err = code; bfir_engine_destroy(e); return (bfir_engine *)nullptr; };
     int r = 1, D = blocks[0];
     for (int k = 1; k < n_levels; k++) {
         r *= ratios[k];
         // ceil(D_k / r) + 1 slots on top: the blocks a fade's catch-up runs again (at most that many) and their history
-        bfir_engine *t = engine_create(1, r * filter_length, blocks[k], realsize, channels, channels, false, in_format, out_format,
-                                       44100, 0, device, err, 2, (D + r - 1) / r + 1);
+        bfir_engine *t = engine_create(1, r * filter_length, blocks[k], realsize, channels, channels_out, matrix, in_format,
+                                       out_format, 44100, 0, device, err, 2, (D + r - 1) / r + 1);
         if (!t) return fail(*err);
         e->tail[k - 1] = t; e->lv_r[k - 1] = r; e->lv_D[k - 1] = D; e->n_tail = k;
         D += blocks[k] * r;
@@ -607,11 +623,35 @@ extern "C" bfir_engine *bfir_engine_create_nup(int filter_length, int head_block
     // float frames only (no staging kernels, no dither)
     if (!fmt_is_native(in_format) || !fmt_is_native(out_format)) return nullptr;
     const int blocks[2] = {head_blocks, tail_blocks}, ratios[2] = {1, tail_ratio};
-    bfir_engine *e = create_split(filter_length, 2, blocks, ratios, realsize, channels, in_format, out_format, device, err);
+    bfir_engine *e = create_split(filter_length, 2, blocks, ratios, realsize, channels, channels, false, in_format, out_format, device, err);
     if (!e) return nullptr;
     bfir_logf("bfir engine: two levels, head %d x %d, tail %d x %d; back end %s.", e->L, e->B, e->tail[0]->L, e->tail[0]->B,
               e->pair ? "fused" : "general");
     return e;
+}
+
+// what bfir_engine_create_levels and _create_matrix_levels ask of their arguments, the channel counts apart; no device is touched
+static int check_levels_args(int filter_length, int n_levels, const int *blocks, const int *ratios, int realsize, int in_format,
+                             int out_format)
+{
+    if (realsize != 4 && realsize != 8) { bfir_logf("Invalid real size %d.", realsize); return BFIR_ERR_ARG; }
+    if (filter_length < 1 || (filter_length & (filter_length - 1))) { bfir_logf("Invalid length %d.", filter_length); return BFIR_ERR_ARG; }
+    if (n_levels < 2 || n_levels > BFIR_MAX_LEVELS || !blocks || !ratios || ratios[0] != 1) return BFIR_ERR_ARG;
+    // L_k and D_k in samples, as doubles: exact at every size a transform could have, and no overflow at any other
+    double Lk[BFIR_MAX_LEVELS], Dk = 0.0;
+    for (int k = 0; k < n_levels; k++) {
+        if (blocks[k] < 1) return BFIR_ERR_ARG;
+        if (k > 0 && (ratios[k] < 2 || (ratios[k] & (ratios[k] - 1)))) return BFIR_ERR_ARG;
+        Lk[k] = k == 0 ? (double)filter_length : Lk[k - 1] * ratios[k];
+        // a block of level k is first read D_k samples after it began: it must be complete by then
+        if (k > 0 && Dk < Lk[k]) return BFIR_ERR_ARG;
+        Dk += blocks[k] * Lk[k];
+    }
+    for (int k = 0; k < n_levels; k++)
+        if (Lk[k] > 16384.0 || !length_supported((int)Lk[k], realsize)) return BFIR_ERR_UNSUPPORTED;
+    // float frames only (no staging kernels, no dither)
+    if (!fmt_is_native(in_format) || !fmt_is_native(out_format)) return BFIR_ERR_UNSUPPORTED;
+    return BFIR_OK;
 }
 
 extern "C" bfir_engine *bfir_engine_create_levels(int filter_length, int n_levels, const int *blocks, const int *ratios,
@@ -624,31 +664,41 @@ extern "C" bfir_engine *bfir_engine_create_levels(int filter_length, int n_level
         bfir_logf("Number of channels (%d) exceeds limit (%d).", channels, BFIR_MAXCHANNELS);
         return nullptr;
     }
-    if (realsize != 4 && realsize != 8) { bfir_logf("Invalid real size %d.", realsize); return nullptr; }
-    if (filter_length < 1 || (filter_length & (filter_length - 1))) { bfir_logf("Invalid length %d.", filter_length); return nullptr; }
-    if (n_levels < 2 || n_levels > BFIR_MAX_LEVELS || !blocks || !ratios || ratios[0] != 1) return nullptr;
-    // L_k and D_k in samples, as doubles: exact at every size a transform could have, and no overflow at any other
-    double Lk[BFIR_MAX_LEVELS], Dk = 0.0;
-    for (int k = 0; k < n_levels; k++) {
-        if (blocks[k] < 1) return nullptr;
-        if (k > 0 && (ratios[k] < 2 || (ratios[k] & (ratios[k] - 1)))) return nullptr;
-        Lk[k] = k == 0 ? (double)filter_length : Lk[k - 1] * ratios[k];
-        // a block of level k is first read D_k samples after it began: it must be complete by then
-        if (k > 0 && Dk < Lk[k]) return nullptr;
-        Dk += blocks[k] * Lk[k];
-    }
-    *err = BFIR_ERR_UNSUPPORTED;
-    for (int k = 0; k < n_levels; k++)
-        if (Lk[k] > 16384.0 || !length_supported((int)Lk[k], realsize)) return nullptr;
-    // float frames only (no staging kernels, no dither)
-    if (!fmt_is_native(in_format) || !fmt_is_native(out_format)) return nullptr;
-    bfir_engine *e = create_split(filter_length, n_levels, blocks, ratios, realsize, channels, in_format, out_format, device, err);
+    *err = check_levels_args(filter_length, n_levels, blocks, ratios, realsize, in_format, out_format);
+    if (*err != BFIR_OK) return nullptr;
+    bfir_engine *e = create_split(filter_length, n_levels, blocks, ratios, realsize, channels, channels, false, in_format, out_format, device,
+                                   err);
     if (!e) return nullptr;
     e->levels = true;
     char desc[160];
     int n = snprintf(desc, sizeof(desc), "%d x %d", e->L, e->B);
     for (int i = 0; i < e->n_tail; i++) n += snprintf(desc + n, sizeof(desc) - n, ", %d x %d", e->tail[i]->L, e->tail[i]->B);
     bfir_logf("bfir engine: %d levels, %s; back end %s.", n_levels, desc, e->pair ? "fused" : "general");
+    return e;
+}
+
+extern "C" bfir_engine *bfir_engine_create_matrix_levels(int filter_length, int n_levels, const int *blocks, const int *ratios,
+                                                         int realsize, int n_inputs, int n_outputs, int in_format, int out_format,
+                                                         int device, int *err)
+{
+    int dummy;
+    if (!err) err = &dummy;
+    *err = BFIR_ERR_ARG;
+    if (n_inputs < 1 || n_inputs > BFIR_MAXCHANNELS || n_outputs < 1 || n_outputs > BFIR_MAXCHANNELS) {
+        bfir_logf("Number of channels (%d -> %d) exceeds limit (%d).", n_inputs, n_outputs, BFIR_MAXCHANNELS);
+        return nullptr;
+    }
+    *err = check_levels_args(filter_length, n_levels, blocks, ratios, realsize, in_format, out_format);
+    if (*err != BFIR_OK) return nullptr;
+    bfir_engine *e = create_split(filter_length, n_levels, blocks, ratios, realsize, n_inputs, n_outputs, true, in_format, out_format,
+                                  device, err);
+    if (!e) return nullptr;
+    e->mlevels = true;
+    char desc[160];
+    int n = snprintf(desc, sizeof(desc), "%d x %d", e->L, e->B);
+    for (int i = 0; i < e->n_tail; i++) n += snprintf(desc + n, sizeof(desc) - n, ", %d x %d", e->tail[i]->L, e->tail[i]->B);
+    bfir_logf("bfir engine: matrix %d -> %d, %d levels, %s; back end %s.", e->C, e->Co, n_levels, desc,
+              e->back_fused ? "fused" : "general");
     return e;
 }
 
@@ -696,9 +746,10 @@ extern "C" int bfir_engine_set_chunk(bfir_engine *e, int blocks_per_launch)
 // coeff::preprocess_coeff + convolver_coeffs2cbuf for n_rows filters, rows row0 .. of H: coeffs[n] (n < n_coeffs <= n_rows)
 // goes to row row0 + n, nb partitions each.  A NULL entry is an error (null_ok = false) or an all-zero filter, as are the
 // rows past n_coeffs.  Nothing is uploaded before every filter has passed the finite check.  Hdst: the filter buffer that
-// takes them, H or (a fade's second set) H2.
+// takes them, H or (a fade's second set) H2.  lengths: the tap count of every filter where they differ (a filter without
+// taps is one without a path); else all have `length`.
 static int load_filters(bfir_engine *e, void *Hdst, int row0, int n_rows, const void *const *coeffs, int n_coeffs, int length, int nb,
-                        double scale, bool null_ok)
+                        double scale, bool null_ok, const int *lengths = nullptr)
 {
     const size_t taps_pad = (size_t)nb * e->L;
     const size_t cb = cbuf_bytes(e);
@@ -707,15 +758,16 @@ static int load_filters(bfir_engine *e, void *Hdst, int row0, int n_rows, const 
     // (coeff.cpp:315-339), taps are scaled in working precision (fftw_convolver.cpp:491,507)
     std::vector<char> host((size_t)n_rows * taps_pad * e->s, 0);
     for (int n = 0; n < n_coeffs; n++) {
-        if (!coeffs[n]) { if (null_ok) continue; return BFIR_ERR_ARG; }
+        if (!coeffs[n] || (lengths && lengths[n] <= 0)) { if (null_ok) continue; return BFIR_ERR_ARG; }
+        const size_t cnt_n = lengths ? std::min((size_t)lengths[n], taps_pad) : cnt;
         bool finite = true;
         if (e->s == 4) {
             const float *src = (const float *)coeffs[n];
             const float sc = (float)scale;
-            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite((double)(src[i] * sc));
+            for (size_t i = 0; i < cnt_n; i++) finite &= std::isfinite((double)(src[i] * sc));
         } else {
             const double *src = (const double *)coeffs[n];
-            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite(src[i] * scale);
+            for (size_t i = 0; i < cnt_n; i++) finite &= std::isfinite(src[i] * scale);
         }
         if (!finite) {
             bfir_logf("NaN or Inf value among coefficients.");
@@ -723,7 +775,7 @@ static int load_filters(bfir_engine *e, void *Hdst, int row0, int n_rows, const 
             else bfir_logf("Error preprocessing coefficient %d", n);
             return BFIR_ERR_COEFF;
         }
-        memcpy(host.data() + (size_t)n * taps_pad * e->s, coeffs[n], cnt * e->s);
+        memcpy(host.data() + (size_t)n * taps_pad * e->s, coeffs[n], cnt_n * e->s);
     }
     void *d_taps = nullptr;
     void *rows = (char *)Hdst + (size_t)row0 * e->B * cb;
@@ -779,6 +831,26 @@ extern "C" int bfir_engine_set_coeff(bfir_engine *e, const void *const *coeffs, 
 
 static void lfade_finish(bfir_engine *e, bool take_new);
 
+// Level i + 1 of a split engine gets taps it did not have: it starts (again) with its next block that begins.  Its signal
+// state is cleared, the blocks it did not compute read as zero, and its first blocks lack the input from before (a
+// transient like the one of a new engine).  Output queued before it stopped is still in the ring.
+static int level_start(bfir_engine *e, int i)
+{
+    bfir_engine *t = e->tail[i];
+    const int r = e->lv_r[i];
+    const size_t blk = (size_t)t->L * t->s;
+    const long long j0 = (long long)((e->blockcounter + r - 1) / r);
+    HIP_TRY(hipMemset(t->X, 0, (size_t)t->GC * t->ring * cbuf_bytes(t)));
+    for (int st = 0; st < 2; st++) for (int h = 0; h < 2; h++) HIP_TRY(hipMemset(t->tails[st][h], 0, (size_t)t->L * t->C * t->in_bytes));
+    const long long oldest = std::max(0ll, ((long long)e->blockcounter - e->lv_D[i]) / r);   // the oldest block of the level still to be read
+    if (t->z_next <= oldest || t->z_next == t->z_from) t->z_from = j0;
+    else for (long long j = t->z_next; j < j0; j++)   // fewer than D_k / L_k + 2 <= zblocks of them
+        HIP_TRY(hipMemset2D((char *)t->zring + (size_t)(j % t->zblocks) * blk, (size_t)t->zblocks * blk, 0, blk, t->GCo));
+    t->z_next = j0;
+    t->blockcounter = 0; t->curbuf = 0;
+    return BFIR_OK;
+}
+
 // The filters of a two-level or multi-level engine, split at every D_k: taps [0, D_1) to the head, [D_k, D_(k+1)) to level
 // k.  Mid-stream every delay line is kept: the head takes the new filters from the next block, level k from its next
 // block that completes; what a level has already put into its time ring still plays.
@@ -813,24 +885,9 @@ static int set_coeff_split(bfir_engine *e, const void *const *coeffs, int n_coef
     HIP_TRY(hipMemcpy(e->d_nblk, e->nblk.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
     for (int i = 0; i < e->n_tail; i++) {
         bfir_engine *t = e->tail[i];
-        const int r = e->lv_r[i];
         for (int n = 0; n < e->C; n++) t->nblk[n] = nb_lv[i];
         HIP_TRY(hipMemcpy(t->d_nblk, t->nblk.data(), sizeof(int) * t->C, hipMemcpyHostToDevice));
-        if (len_lv[i] > 0 && !e->lv_active[i]) {
-            // The level starts (again) with its next block that begins: its signal state is cleared, the blocks it did
-            // not compute read as zero, and its first blocks lack the input from before (a transient like the one of a new
-            // engine).  Output queued before it stopped is still in the ring.
-            const size_t blk = (size_t)t->L * t->s;
-            const long long j0 = (long long)((e->blockcounter + r - 1) / r);
-            HIP_TRY(hipMemset(t->X, 0, (size_t)t->GC * t->ring * cbuf_bytes(t)));
-            for (int st = 0; st < 2; st++) for (int h = 0; h < 2; h++) HIP_TRY(hipMemset(t->tails[st][h], 0, (size_t)t->L * t->C * t->in_bytes));
-            const long long oldest = std::max(0ll, ((long long)e->blockcounter - e->lv_D[i]) / r);   // the oldest block of the level still to be read
-            if (t->z_next <= oldest || t->z_next == t->z_from) t->z_from = j0;
-            else for (long long j = t->z_next; j < j0; j++)   // fewer than D_k / L_k + 2 <= zblocks of them
-                HIP_TRY(hipMemset2D((char *)t->zring + (size_t)(j % t->zblocks) * blk, (size_t)t->zblocks * blk, 0, blk, t->GC));
-            t->z_next = j0;
-            t->blockcounter = 0; t->curbuf = 0;
-        }
+        if (len_lv[i] > 0 && !e->lv_active[i]) { rc = level_start(e, i); if (rc != BFIR_OK) return rc; }
         e->lv_active[i] = len_lv[i] > 0;
         t->eng_init[0] = 1;
     }
@@ -841,7 +898,7 @@ static int set_coeff_split(bfir_engine *e, const void *const *coeffs, int n_coef
 extern "C" int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
 {
     if (!e) return BFIR_ERR_ARG;
-    if (!e->nup || e->levels) return BFIR_ERR_UNSUPPORTED;
+    if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
     return set_coeff_split(e, coeffs, n_coeffs, length, scale);
 }
 
@@ -878,7 +935,7 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
                                             double scale)
 {
     if (!e) return BFIR_ERR_ARG;
-    if (!e->matrix) return BFIR_ERR_UNSUPPORTED;
+    if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;   // bfir_engine_set_coeff_matrix_levels
     if (!coeffs || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -890,6 +947,89 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
     if (rc != BFIR_OK) return rc;
     for (int n = 0; n < P; n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
     if (e->pair_cap) matrix_take_path(e, every_input_read(e, e->nblk));
+    e->eng_init[0] = 1;
+    return BFIR_OK;
+}
+
+// The n_out x n_in filters of a multi-level matrix engine, each of its own length, split at every D_k as set_coeff_split
+// splits them: level k gets taps [D_k, D_(k+1)) of every filter that reaches past D_k, with that filter's own partition
+// count (0: skipped on that level, never multiplied by zero).  Mid-stream the rules of set_coeff_split hold per level.
+extern "C" int bfir_engine_set_coeff_matrix_levels(bfir_engine *e, const void *const *coeffs, const int *lengths, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || !lengths) return BFIR_ERR_ARG;
+    const int P = e->Co * e->C;                                 // filters, [o][i]
+    long long cap = (long long)e->B * e->L;
+    for (int i = 0; i < e->n_tail; i++) cap += (long long)e->tail[i]->B * e->tail[i]->L;
+    for (int n = 0; n < P; n++)
+        if (coeffs[n] && (lengths[n] < 0 || (long long)lengths[n] > cap)) return BFIR_ERR_ARG;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    e->eng_init[0] = 0;
+    // a NaN / Inf tap anywhere is refused before anything is uploaded at any level
+    for (int n = 0; n < P; n++) {
+        if (!coeffs[n]) continue;
+        bool finite = true;
+        if (e->s == 4) {
+            const float *src = (const float *)coeffs[n];
+            const float sc = (float)scale;
+            for (int i = 0; i < lengths[n]; i++) finite &= std::isfinite((double)(src[i] * sc));
+        } else {
+            const double *src = (const double *)coeffs[n];
+            for (int i = 0; i < lengths[n]; i++) finite &= std::isfinite(src[i] * scale);
+        }
+        if (!finite) {
+            bfir_logf("NaN or Inf value among coefficients.");
+            bfir_logf("Error preprocessing coefficient %d (output %d, input %d)", n, n / e->C, n % e->C);
+            return BFIR_ERR_COEFF;
+        }
+    }
+    // the head, then level after level: the part of every filter that falls into the level and its partitions there
+    bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
+    std::vector<const void *> part((size_t)P);
+    std::vector<int> len((size_t)P);
+    bool active[BFIR_MAX_LEVELS] = {false, false, false, false};
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = lv[k];
+        const long long D = k == 0 ? 0 : (long long)e->lv_D[k - 1] * e->L;
+        int nb_max = 0;
+        for (int n = 0; n < P; n++) {
+            const long long rest = coeffs[n] ? std::min((long long)lengths[n] - D, (long long)l->B * l->L) : 0;
+            len[n] = (int)std::max(0ll, rest);
+            part[n] = len[n] > 0 ? (const char *)coeffs[n] + (size_t)D * e->s : nullptr;
+            l->nblk[n] = (len[n] + l->L - 1) / l->L;
+            nb_max = std::max(nb_max, l->nblk[n]);
+        }
+        active[k] = nb_max > 0;
+        if (nb_max > 0) {   // a level on which no filter has taps does no work at all (the head: its MAC stores zeros)
+            const int rc = load_filters(l, l->H, 0, P, part.data(), P, 0, nb_max, scale, true, len.data());
+            if (rc != BFIR_OK) return rc;
+        }
+    }
+    for (int i = 0; i < e->n_tail; i++) {
+        if (active[i + 1] && !e->lv_active[i]) { const int rc = level_start(e, i); if (rc != BFIR_OK) return rc; }
+        e->lv_active[i] = active[i + 1];
+        e->tail[i]->eng_init[0] = 1;
+    }
+    // An input is read if any filter of its column has taps on any level; while one is not, no level pairs channels (a
+    // pair is ONE transform: a NaN on the unread input would reach the spectra of its partner)
+    bool all_read = true;
+    for (int i = 0; i < e->C; i++) {
+        bool read = false;
+        for (int o = 0; o < e->Co; o++) read = read || (coeffs[o * e->C + i] && lengths[o * e->C + i] > 0);
+        all_read = all_read && read;
+    }
+    for (int i = 0; i < e->n_tail; i++) if (e->tail[i]->pair_cap) matrix_take_path(e->tail[i], all_read);
+    // While no level beyond the head has taps the engine IS bfir_engine_create_matrix(L, blocks[0], ...) and takes its path,
+    // which pairs channels only with an even count on both sides: so it gives that engine's bytes
+    const bool any_tail = active[1] || active[2] || active[3];
+    if (e->pair_cap) {
+        if (all_read && !any_tail && (e->Co & 1)) {
+            if (e->pair) bfir_logf("bfir matrix engine: no level beyond the head has taps: path=direct from the next block on.");
+            e->pair = false; e->direct = true;
+        } else matrix_take_path(e, all_read);
+    }
     e->eng_init[0] = 1;
     return BFIR_OK;
 }
@@ -987,7 +1127,7 @@ extern "C" int bfir_engine_set_coeff_matrix_fade(bfir_engine *e, const void *con
                                                  double scale, int fade_blocks)
 {
     if (!e) return BFIR_ERR_ARG;
-    if (!e->matrix) return BFIR_ERR_UNSUPPORTED;
+    if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;
     return set_coeff_fade(e, coeffs, 0, length, coeff_blocks, scale, fade_blocks);
 }
 
@@ -1030,7 +1170,7 @@ extern "C" int bfir_engine_read_coeff(bfir_engine *e, int channel, int block, vo
 extern "C" int bfir_engine_read_coeff_nup(bfir_engine *e, int level, int channel, int block, void *dst)
 {
     if (!e) return BFIR_ERR_ARG;
-    if (!e->nup || e->levels) return BFIR_ERR_UNSUPPORTED;
+    if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
     if (level < 0 || level > 1 || !dst) return BFIR_ERR_ARG;
     bfir_engine *lv = level ? e->tail[0] : e;
     if (channel < 0 || channel >= lv->GC || block < 0 || block >= lv->B) return BFIR_ERR_ARG;
@@ -1050,9 +1190,19 @@ extern "C" int bfir_engine_read_coeff_levels(bfir_engine *e, int level, int chan
 extern "C" int bfir_engine_read_coeff_matrix(bfir_engine *e, int output, int input, int block, void *dst)
 {
     if (!e) return BFIR_ERR_ARG;
-    if (!e->matrix) return BFIR_ERR_UNSUPPORTED;
+    if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;   // bfir_engine_read_coeff_matrix_levels
     if (output < 0 || output >= e->Co || input < 0 || input >= e->C || block < 0 || block >= e->B || !dst) return BFIR_ERR_ARG;
     return read_spectrum(e, output * e->C + input, block, dst);
+}
+
+extern "C" int bfir_engine_read_coeff_matrix_levels(bfir_engine *e, int level, int output, int input, int block, void *dst)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (level < 0 || level > e->n_tail || !dst) return BFIR_ERR_ARG;
+    bfir_engine *lv = level ? e->tail[level - 1] : e;
+    if (output < 0 || output >= lv->Co || input < 0 || input >= lv->C || block < 0 || block >= lv->B) return BFIR_ERR_ARG;
+    return read_spectrum(lv, output * lv->C + input, block, dst);
 }
 
 // ---------------------------------------------------------------------------
@@ -1198,8 +1348,10 @@ static int matrix_chunk_ok(const bfir_engine *e, int tc)
 // what the path's kernels ask of the caller's frame buffers (the staging kernels: nothing)
 static int chunk_aligned(const bfir_engine *e, Path p, const Chunk &c)
 {
+    // a multi-level matrix engine with an odd output count stores its frame pairs at 4-byte alignment
+    const uintptr_t out_mask = (e->pair_tp || (e->matrix && (e->Co & 1))) ? 3 : 7;
     if (p == Path::Pair &&
-        (((uintptr_t)c.d_in | (uintptr_t)c.d_out | (uintptr_t)c.in_stride | (uintptr_t)c.out_stride) & (e->pair_tp ? 3 : 7))) {
+        ((((uintptr_t)c.d_in | (uintptr_t)c.in_stride) & (e->pair_tp ? 3 : 7)) || (((uintptr_t)c.d_out | (uintptr_t)c.out_stride) & out_mask))) {
         bfir_logf("bfir engine: frame buffers of the float fast path must be 8-byte aligned (4 with an odd channel count).");
         return BFIR_ERR_ARG;
     }
@@ -1277,6 +1429,20 @@ static void queue_inv(bfir_engine *e, Path p, const Chunk &c, hipStream_t st)
         a.scale = (float)e->out_scale; a.max = (float)e->of_max;
         a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
         a.tp = e->pair_tp;
+        if (e->matrix && (e->Co & 1)) {
+            // the head of a multi-level matrix engine with an odd output count, in a chunk to which no level contributes: the
+            // pairs below it through the pair kernel, frames Co floats apart, then the last output alone (k_inv_lone, no ring)
+            a.C = e->Co & ~1; a.frame_stride = e->Co;
+            LoneInvArgs b;
+            b.y = (const float *)c.Y + (long)a.C * e->chunk * e->N;
+            b.ring[0] = b.ring[1] = b.ring[2] = LevelRing{nullptr, 0, 0, 0, 0, 0};
+            b.n_rings = 0;
+            b.raw = (float *)c.d_out; b.frame_off = c.frame_off;
+            b.frame_stride = e->Co; b.ch = a.C; b.n_t = c.tc;
+            b.scale = a.scale; b.max = a.max;
+            b.overflow = e->d_of; b.of_shard_stride = e->GCo; b.bad_block = e->d_bad; b.block_base = c.block_base; b.bad_host = e->bad_host_cur;
+            launch_inv_lone(e->plan2, b, st);
+        }
         launch_inv_pair(e->plan2, a, st);
         return;
     }
@@ -1357,7 +1523,7 @@ static void inv_to_ring(bfir_engine *e, const void *Y, long y_ch_stride, void *z
         InvArgs a;
         a.src = (const char *)Y + (size_t)t0 * cbuf_bytes(e); a.src_ch_stride = y_ch_stride;
         a.dst = (char *)zring + (size_t)slot * e->L * e->s; a.dst_ch_stride = (long)e->zblocks * e->L;
-        a.n_t = n; a.n_ch = e->GC;
+        a.n_t = n; a.n_ch = e->GCo;
         a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
         launch_inv(e->plan, a, st);
         t0 += n;
@@ -1389,15 +1555,28 @@ static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
         g.m0 = ((long long)e->blockcounter - e->lv_D[i]) * e->L; g.m_min = t->z_from * (long long)t->L;
         g.m0r = (long)(((g.m0 % g.zlen) + g.zlen) % g.zlen);
     }
-    if (e->pair) {   // one inverse per channel pair and block, the sum, statistics and frame store in one kernel
+    if (e->back_fused) {   // one inverse per channel pair and block, the sum, statistics and frame store in one kernel
         ProfScope ps(e, BFIR_K_INV, st);
+        // a matrix engine with an odd output count: the pairs below it, frames Co floats apart, then the last output alone
+        const int n_pair = e->Co & ~1, fstride = n_pair == e->Co ? 0 : e->Co;
+        if (n_pair < e->Co) {
+            LoneInvArgs a;
+            a.y = (const float *)c.Y + (long)n_pair * e->chunk * e->N;
+            for (int k = 0; k < BFIR_LEVEL_RINGS; k++) a.ring[k] = ring[k < nr ? k : 0];
+            a.n_rings = nr;
+            a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
+            a.frame_stride = e->Co; a.ch = n_pair; a.n_t = c.tc;
+            a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+            a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
+            launch_inv_lone(e->plan2, a, st);
+        }
         if (nr == 1) {
             NupInvArgs a;
             a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
             a.z = (const float *)ring[0].z; a.z_ch_stride = ring[0].z_ch_stride; a.zlen = ring[0].zlen;
             a.m0 = ring[0].m0; a.m_min = ring[0].m_min; a.m0r = ring[0].m0r;
             a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
-            a.n_ch = e->C; a.n_t = c.tc;
+            a.n_ch = n_pair; a.n_t = c.tc; a.frame_stride = fstride;
             a.scale = (float)e->out_scale; a.max = (float)e->of_max;
             a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
             launch_inv_nup(e->plan2, a, st);
@@ -1407,7 +1586,7 @@ static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
             for (int k = 0; k < BFIR_LEVEL_RINGS; k++) a.ring[k] = ring[k < nr ? k : 0];
             a.n_rings = nr;
             a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
-            a.n_ch = e->C; a.n_t = c.tc;
+            a.n_ch = n_pair; a.n_t = c.tc; a.frame_stride = fstride;
             a.scale = (float)e->out_scale; a.max = (float)e->of_max;
             a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
             launch_inv_levels(e->plan2, a, st);
@@ -1420,7 +1599,7 @@ static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
         ProfScope ps(e, BFIR_K_INV, st);
         InvArgs a;
         a.src = c.Y; a.src_ch_stride = (long)e->chunk * e->N; a.dst = e->tout; a.dst_ch_stride = t_stride;
-        a.n_t = c.tc; a.n_ch = e->GC;
+        a.n_t = c.tc; a.n_ch = e->GCo;
         a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
         launch_inv(e->plan, a, st);
         if (nr == 1) {
@@ -1428,14 +1607,14 @@ static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
             b.y = e->tout; b.y_ch_stride = t_stride;
             b.z = ring[0].z; b.z_ch_stride = ring[0].z_ch_stride; b.zlen = ring[0].zlen;
             b.m0 = ring[0].m0; b.m_min = ring[0].m_min; b.m0r = ring[0].m0r;
-            b.n_ch = e->GC; b.n = (long)c.tc * e->L; b.realsize = e->s;
+            b.n_ch = e->GCo; b.n = (long)c.tc * e->L; b.realsize = e->s;
             launch_nup_combine(b, st);
         } else {
             LevelsCombineArgs b;
             b.y = e->tout; b.y_ch_stride = t_stride;
             for (int k = 0; k < BFIR_LEVEL_RINGS; k++) b.ring[k] = ring[k < nr ? k : 0];
             b.n_rings = nr;
-            b.n_ch = e->GC; b.n = (long)c.tc * e->L; b.realsize = e->s;
+            b.n_ch = e->GCo; b.n = (long)c.tc * e->L; b.realsize = e->s;
             launch_levels_combine(b, st);
         }
     }
@@ -1733,7 +1912,7 @@ extern "C" int bfir_engine_set_coeff_nup_fade(bfir_engine *e, const void *const 
                                               int fade_blocks)
 {
     if (!e) return BFIR_ERR_ARG;
-    if (!e->nup || e->levels) return BFIR_ERR_UNSUPPORTED;
+    if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
     return set_coeff_split_fade(e, coeffs, n_coeffs, length, scale, fade_blocks);
 }
 
@@ -1839,6 +2018,11 @@ static int run_blocks(bfir_engine *e, const void *d_in, long in_stride, void *d_
                       int block_base, hipStream_t st, hipEvent_t input_ready)
 {
     const long long call0 = (long long)e->blockcounter;   // the head block at frame_off (two-level engines)
+    if (e->mlevels) {   // every level's MAC must take its longest launch of this call: refused before anything is queued
+        int rc = matrix_chunk_ok(e, std::min(e->chunk, n));
+        for (int i = 0; i < e->n_tail && rc == BFIR_OK; i++) rc = matrix_chunk_ok(e->tail[i], std::min(e->tail[i]->chunk, n));
+        if (rc != BFIR_OK) return rc;
+    }
     for (int c0 = 0; c0 < n;) {
         int tc = std::min(e->chunk, n - c0);
         if (e->nup) {

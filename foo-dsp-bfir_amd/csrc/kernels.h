@@ -230,6 +230,7 @@ struct InvPairArgs {
     int *bad_host = nullptr;                             // as in StageOutArgs
     long of_shard_stride = 0;
     int tp = 0;                                          // pairs in time, as in FwdPairArgs
+    int frame_stride = 0;                                // channel pairs only: floats between output frames; 0 = C (wider: an odd matrix output beside the pairs)
 };
 void launch_inv_pair(const FftPlan &plan, const InvPairArgs &a, hipStream_t s);
 
@@ -278,6 +279,7 @@ struct NupInvArgs {
     float scale, max;
     DevOverflow *overflow; long of_shard_stride;
     int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+    int frame_stride = 0;                                // floats between output frames; 0 = n_ch (wider: an odd matrix output beside the pairs)
 };
 void launch_inv_nup(const FftPlan &plan, const NupInvArgs &a, hipStream_t s);
 // k_nup_combine, the general form's middle step: y[c][i] <- y[c][i] + z[c][(m0 + i) mod zlen] on a planar time buffer
@@ -311,6 +313,7 @@ struct LevelsInvArgs {
     float scale, max;
     DevOverflow *overflow; long of_shard_stride;
     int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+    int frame_stride = 0;                                // as in NupInvArgs
 };
 void launch_inv_levels(const FftPlan &plan, const LevelsInvArgs &a, hipStream_t s);
 // k_levels_combine, the general form's middle step: y[c][i] <- y[c][i] + z_0 + z_1 (+ z_2) on a planar time buffer
@@ -322,6 +325,22 @@ struct LevelsCombineArgs {
     int realsize;
 };
 void launch_levels_combine(const LevelsCombineArgs &a, hipStream_t s);
+
+// mlevels.hip: the fused back end of a multi-level matrix engine (bfir_engine_create_matrix_levels) with an odd output
+// count.  Outputs (0, 1), (2, 3), ... go through k_inv_nup / k_inv_levels with n_ch = 2 floor(n_out / 2) and frame_stride =
+// n_out; the last output, channel `ch`, through k_inv_lone: fp32, (re, im) pairs, FLOAT_LE frames, 512 <= L <= 8192 (`plan`
+// is the plan of 2L points), one workgroup per block, n_rings = 1, 2 or 3 additions per sample as in LevelsInvArgs; n_rings =
+// 0 for a chunk to which no level contributes (the pairs then go through k_inv_pair_ps with the same frame_stride).
+struct LoneInvArgs {
+    const float *y;                                      // [..][N] product spectra of channel ch, (re, im) pairs
+    LevelRing ring[BFIR_LEVEL_RINGS]; int n_rings;       // planar rings of ALL channels: channel ch is read
+    float *raw; long frame_off;                          // output frames of ONE engine, frame_stride floats apart
+    int frame_stride, ch, n_t;
+    float scale, max;
+    DevOverflow *overflow; long of_shard_stride;         // [n_out] per shard: channel ch is updated
+    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+};
+void launch_inv_lone(const FftPlan &plan, const LoneInvArgs &a, hipStream_t s);
 
 // lfade.hip: the back end of a crossfaded coefficient change on a two-level or multi-level engine
 // (bfir_engine_set_coeff_nup_fade / _levels_fade) for a chunk to which one to three tail levels contribute.  The head's MAC

@@ -39,6 +39,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_inv_levels(LevelsInvArgs 
     const int pairs = a.n_ch >> 1;
     const int t = w / pairs, gc = 2 * (w - t * pairs);
     typedef float f32x4 __attribute__((ext_vector_type(4)));
+    struct __attribute__((packed, aligned(4))) frame2 { float x, y; };   // both channels of a frame, one store
     const f32x4 *__restrict__ ya = (const f32x4 *)(a.y + (long)gc * a.y_ch_stride + (long)t * N);
     const f32x4 *__restrict__ yb = (const f32x4 *)(a.y + (long)(gc + 1) * a.y_ch_stride + (long)t * N);
 
@@ -76,7 +77,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_inv_levels(LevelsInvArgs 
     // first L samples are the valid half: Re z = channel gc, Im z = channel gc + 1.  The block's L samples of a ring are
     // contiguous (zlen, m0 and m_min are multiples of L): a ring wraps between blocks only, and a block has all of a
     // ring's samples or none.  A ring without samples for this block is read at its start and its samples dropped.
-    const int C = a.n_ch;
+    const int C = a.frame_stride ? a.frame_stride : a.n_ch;   // floats between frames
     float *__restrict__ out = a.raw + (a.frame_off + (long)t * L) * C + gc;
     const float *__restrict__ za[NR];
     bool has_z[NR];
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_inv_levels(LevelsInvArgs 
                 v.x = has_z[r] ? v.x + z0 : v.x;
                 v.y = has_z[r] ? v.y + z1 : v.y;
             }
-            *(float2 *)(out + (long)n * C) = v;                          // gc and C even, frames 8-byte aligned
+            *(frame2 *)(out + (long)n * C) = frame2{v.x, v.y};                         // gc even; C even: 8-byte aligned, odd (a matrix engine's lone output beside the pairs): 4
             // real2raw.cpp:321-336 with symmetric limits: |v| > max, NaN never counts (k_inv_pair_ps)
             c0 += (fabsf(v.x) > rmax) ? 1u : 0u;
             c1 += (fabsf(v.y) > rmax) ? 1u : 0u;

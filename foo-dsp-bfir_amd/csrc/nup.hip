@@ -36,6 +36,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_inv_nup(NupInvArgs a, con
     const int pairs = a.n_ch >> 1;
     const int t = w / pairs, gc = 2 * (w - t * pairs);
     typedef float f32x4 __attribute__((ext_vector_type(4)));
+    struct __attribute__((packed, aligned(4))) frame2 { float x, y; };   // both channels of a frame, one store
     const f32x4 *__restrict__ ya = (const f32x4 *)(a.y + (long)gc * a.y_ch_stride + (long)t * N);
     const f32x4 *__restrict__ yb = (const f32x4 *)(a.y + (long)(gc + 1) * a.y_ch_stride + (long)t * N);
 
@@ -72,7 +73,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_inv_nup(NupInvArgs a, con
 
     // first L samples are the valid half: Re z = channel gc, Im z = channel gc + 1.  The block's L tail samples are
     // contiguous in the ring (zlen is a multiple of L, m a multiple of L at n = 0): it wraps between blocks only.
-    const int C = a.n_ch;
+    const int C = a.frame_stride ? a.frame_stride : a.n_ch;   // floats between frames
     float *__restrict__ out = a.raw + (a.frame_off + (long)t * L) * C + gc;
     const long long m_blk = a.m0 + (long long)t * L;
     const bool has_z = m_blk >= a.m_min;
@@ -90,7 +91,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT) void k_inv_nup(NupInvArgs a, con
             float2 v;
             v.x = has_z ? re[e] + za[n] : re[e];
             v.y = has_z ? im[e] + zb[n] : im[e];
-            *(float2 *)(out + (long)n * C) = v;                          // gc and C even, frames 8-byte aligned
+            *(frame2 *)(out + (long)n * C) = frame2{v.x, v.y};                         // gc even; C even: 8-byte aligned, odd (a matrix engine's lone output beside the pairs): 4
             // real2raw.cpp:321-336 with symmetric limits: |v| > max, NaN never counts (k_inv_pair_ps)
             c0 += (fabsf(v.x) > rmax) ? 1u : 0u;
             c1 += (fabsf(v.y) > rmax) ? 1u : 0u;

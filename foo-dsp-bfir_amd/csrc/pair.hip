@@ -509,6 +509,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
     const int rr = w / pairs, pp = w - rr * pairs;
     const int g = pp / half_c, cp = pp - g * half_c;
     const int C = a.C;
+    const int FS = a.frame_stride ? a.frame_stride : C;                  // floats between output frames
     const int gc = g * C + 2 * cp;
     const int t0 = rr * run_len, t1 = min(a.n_t, t0 + run_len);
     if (t0 >= t1) return;
@@ -517,9 +518,9 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
     F::load_bases(B, ldsb, twb, tid);
 
     const float *__restrict__ ya0 = a.y + (long)gc * a.y_ch_stride;
-    float *__restrict__ out0 = a.raw + (long)g * a.eng_stride + a.frame_off * C + 2 * cp;
-    const unsigned blk_bytes = (unsigned)L * C * 4u;
-    const unsigned cio = (unsigned)C;                                    // floats between a pair's consecutive frames
+    float *__restrict__ out0 = a.raw + (long)g * a.eng_stride + a.frame_off * FS + 2 * cp;
+    const unsigned blk_bytes = (unsigned)L * FS * 4u;
+    const unsigned cio = (unsigned)FS;                                   // floats between a pair's consecutive frames
     static_assert(Q == 4, "the prefetch statement moves four 16-byte pieces per thread and spectrum");
     u32x4 qa[Q], qb[Q];
     {
@@ -592,7 +593,7 @@ __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void 
         });
 
         // first L samples are the valid half (the taps sit in the upper half of their blocks)
-        const __amdgpu_buffer_rsrc_t ro = make_rsrc(out0 + (long)t * L * C, blk_bytes);
+        const __amdgpu_buffer_rsrc_t ro = make_rsrc(out0 + (long)t * L * FS, blk_bytes);
         int to = tid; asm volatile("" : "+v"(to));
 #pragma unroll
         for (int e = 0; e < P; e++) {

@@ -397,3 +397,72 @@ class BrutefirLevels(Brutefir):
         if rc != 0:
             raise BfirError(rc, "bfir_engine_read_coeff_levels")
         return dst
+
+
+class BrutefirMatrixLevels(BrutefirMatrix):
+    """BrutefirMatrix on the partition lengths of BrutefirLevels (bfir_engine_create_matrix_levels): n_in inputs -> n_out
+    outputs, one filter per (output, input) pair, every filter split at every D[k] between two to four levels -- long
+    impulse responses in a crossover, room-correction or reverb matrix at a short block length, with sum(blocks)
+    partitions of MAC work per pair and sample instead of ceil(taps / filter_length).  blocks, ratios, lengths, D and
+    max_taps are BrutefirLevels'.  Frames are FLOAT_LE or FLOAT64_LE; the default is the working precision's.
+
+    run / run_device / sync / reset / overflow / check_overflows / set_chunk / set_profiling / profile / close are
+    BrutefirMatrix's; reset() discards all signal state of all levels.  There is no crossfade on this kind."""
+
+    def __init__(self, filter_length, blocks, ratios, realsize, n_in, n_out, in_format=None, out_format=None, device=0):
+        dflt = SAMPLE_FORMAT_FLOAT_LE if realsize == 4 else SAMPLE_FORMAT_FLOAT64_LE
+        blocks, ratios = [int(b) for b in blocks], [int(r) for r in ratios]
+        assert len(blocks) == len(ratios)
+        self.L, self.B, self.s = filter_length, blocks[0] if blocks else 0, realsize
+        self.n_in, self.n_out = n_in, n_out
+        self.C = n_in
+        self.blocks, self.ratios = tuple(blocks), tuple(ratios)
+        self.lengths, self.D, self.max_taps = self.geometry(filter_length, blocks, ratios)
+        self.in_format = dflt if in_format is None else in_format
+        self.out_format = dflt if out_format is None else out_format
+        self.n_engines, self.device = 1, device
+        self._lib = _lib.load()
+        err = C.c_int(0)
+        n = len(blocks)
+        self._h = self._lib.bfir_engine_create_matrix_levels(filter_length, n, (C.c_int * max(1, n))(*blocks),
+                                                             (C.c_int * max(1, n))(*ratios), realsize, n_in, n_out, self.in_format,
+                                                             self.out_format, device, C.byref(err))
+        if not self._h:
+            raise BfirError(err.value, "bfir_engine_create_matrix_levels")
+
+    @staticmethod
+    def geometry(filter_length, blocks, ratios):
+        """([L_k], [D_k], capacity in taps) of the levels, as BrutefirLevels keeps them in lengths, D and max_taps."""
+        lengths, D = [], [0]
+        for b, r in zip(blocks, ratios):
+            lengths.append(filter_length if not lengths else lengths[-1] * r)
+            D.append(D[-1] + b * lengths[-1])
+        return lengths, D[:-1], D[-1]
+
+    def set_coeff(self, rows, scale=1.0):
+        """rows[o][i]: the taps of h_{o,i} (working precision), each of its own length up to max_taps, or None = no path
+        from input i to output o.  Returns 0 or an ERR_* code (ERR_COEFF: a NaN / Inf tap, the engine is uninitialised)."""
+        assert len(rows) == self.n_out and all(len(r) == self.n_in for r in rows)
+        rd = _real_dtype(self.s)
+        arrs = [None if h is None else np.ascontiguousarray(h, dtype=rd) for r in rows for h in r]
+        ptrs = (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
+        lens = (C.c_int * len(arrs))(*[0 if a is None else a.size for a in arrs])
+        return self._lib.bfir_engine_set_coeff_matrix_levels(self._h, ptrs, lens, float(scale))
+
+    def set_coeff_fade(self, *args, **kwargs):
+        raise BfirError(_lib.ERR_UNSUPPORTED, "bfir_engine_set_coeff_fade")
+
+    def fade_to(self, *args, **kwargs):
+        raise BfirError(_lib.ERR_UNSUPPORTED, "bfir_engine_set_coeff_levels_fade")
+
+    def fade_remaining(self):
+        return self._lib.bfir_engine_fade_remaining_levels(self._h)
+
+    def coeff_block(self, level, output, input, block):
+        """Partition spectrum `block` of h_{output,input} on `level`: 2 L_level reals."""
+        n = 2 * self.lengths[level] if 0 <= level < len(self.lengths) else 2 * self.L
+        dst = np.zeros(n, dtype=_real_dtype(self.s))
+        rc = self._lib.bfir_engine_read_coeff_matrix_levels(self._h, level, output, input, block, dst.ctypes.data)
+        if rc != 0:
+            raise BfirError(rc, "bfir_engine_read_coeff_matrix_levels")
+        return dst

@@ -48,6 +48,19 @@ public:
         m_err = err;
         memset(m_last, 0, sizeof(m_last));
     }
+    // The matrix form of the above (bfir_engine_create_matrix_levels): n_inputs -> n_outputs, one filter per (output, input)
+    // pair, every filter on the same two to four partition lengths.  Frames are n_inputs samples in and n_outputs samples
+    // out.  Coefficients: set_coeff_matrix_levels(coeffs, lengths, scale).
+    struct matrix_io { int n_inputs, n_outputs; };
+    brutefir(int filter_length, const multi_level &levels, int realsize, matrix_io io, int in_format, int out_format, int device = 0)
+        : m_channels(io.n_outputs)
+    {
+        int err = 0;
+        m_e = bfir_engine_create_matrix_levels(filter_length, levels.n_levels, levels.blocks, levels.ratios, realsize, io.n_inputs,
+                                               io.n_outputs, in_format, out_format, device, &err);
+        m_err = err;
+        memset(m_last, 0, sizeof(m_last));
+    }
     ~brutefir() { bfir_engine_destroy(m_e); }
     brutefir(const brutefir &) = delete;
     brutefir &operator=(const brutefir &) = delete;
@@ -88,6 +101,20 @@ public:
     {
         if (!m_e) return -1;
         return bfir_engine_set_coeff_levels(m_e, (const void *const *)coeffs, n_coeffs, length, scale);
+    }
+
+    // A multi-level matrix engine's filters: coeffs[o * n_inputs + i] the taps of h_{o,i} or null (no path), lengths[o *
+    // n_inputs + i] its tap count, each filter split between the levels (bfir_engine_set_coeff_matrix_levels).
+    int set_coeff_matrix_levels(void **coeffs, const int *lengths, double scale)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_matrix_levels(m_e, (const void *const *)coeffs, lengths, scale);
+    }
+    // partition spectrum `block` of h_{output,input} on `level` (2 L_level reals, grouped layout)
+    int read_coeff_matrix_levels(int level, int output, int input, int block, void *dst)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_read_coeff_matrix_levels(m_e, level, output, input, block, dst);
     }
 
     // The same two with a crossfade over the next fade_blocks blocks of filter_length frames, every level consistently

@@ -193,6 +193,34 @@ int bfir_engine_set_coeff_levels(bfir_engine *e, const void *const *coeffs, int 
 /* partition spectrum `block` of `channel` on level `level`: 2 L_level reals, grouped layout */
 int bfir_engine_read_coeff_levels(bfir_engine *e, int level, int channel, int block, void *dst);
 
+/* The matrix form of the engine above: n_inputs inputs, n_outputs outputs, one filter h_{o,i} per (output, input) pair, every
+ * filter convolved on the same two to four partition lengths:
+ *   y_o[n] = ((y_0,o[n] + z_1,o[n - D_1]) + z_2,o[n - D_2]) + z_3,o[n - D_3],
+ * y_0,o and z_k,o the sums over the inputs that bfir_engine_create_matrix(L_k, blocks[k], ...) computes from taps
+ * [D_k, D_(k+1)) of every filter.  n_levels is 2 .. BFIR_MAX_LEVELS (there is no separate two-level call); blocks, ratios,
+ * realsize, the frame formats and their errors are those of bfir_engine_create_levels, 1 <= n_inputs, n_outputs <=
+ * BFIR_MAXCHANNELS (else BFIR_ERR_ARG).  Arguments are checked before the device: BFIR_ERR_NO_DEVICE only for valid ones.
+ * Filters that all end at or before D_1 give the bytes of bfir_engine_create_matrix(L_0, blocks[0], ...).  While some level
+ * beyond the first has taps and the rows of outputs 2p and 2p + 1 read every input, the bytes of those two outputs do not
+ * depend on whether further outputs exist.  The output does not depend on bfir_engine_set_chunk or on how the blocks arrive.  Frames: n_inputs samples in,
+ * n_outputs samples out; bfir_engine_get_overflow(e, o, ..) is output o's; bfir_engine_reset discards all signal state.
+ * Such an engine is a kind of its own: every other bfir_engine_set_coeff*, _read_coeff* and fade call returns
+ * BFIR_ERR_UNSUPPORTED on it (it has no crossfade: bfir_engine_fade_remaining_levels returns 0), and the three calls below
+ * the same on every other kind of engine. */
+bfir_engine *bfir_engine_create_matrix_levels(int filter_length, int n_levels, const int *blocks, const int *ratios,
+                                              int realsize, int n_inputs, int n_outputs, int in_format, int out_format,
+                                              int device, int *err);
+/* coeffs[o * n_inputs + i]: the taps of h_{o,i} in working precision, or NULL = no path from input i to output o;
+ * lengths[o * n_inputs + i]: that filter's tap count, 0 .. D_(n_levels) (outside: BFIR_ERR_ARG; 0 taps are no path).  Each
+ * filter is split at every D_k, ragged ends zero-filled; a filter that ends at or before D_k has no partitions on level k
+ * and is skipped there, never multiplied by zero, and a level on which no filter has taps does no work at all.  An input is
+ * read if any filter of its column has taps on any level; a NaN on an input that is not read reaches no output and no
+ * verdict (while there is one, every level transforms one channel at a time).  A NaN/Inf tap: BFIR_ERR_COEFF, nothing is
+ * uploaded and the engine is uninitialised.  Mid-stream the rules of bfir_engine_set_coeff_levels hold per level. */
+int bfir_engine_set_coeff_matrix_levels(bfir_engine *e, const void *const *coeffs, const int *lengths, double scale);
+/* partition spectrum `block` of h_{output,input} on level `level`: 2 L_level reals, grouped layout */
+int bfir_engine_read_coeff_matrix_levels(bfir_engine *e, int level, int output, int input, int block, void *dst);
+
 void bfir_engine_destroy(bfir_engine *e);
 
 /* brutefir::is_initialized */
