@@ -83,6 +83,7 @@ SIGNATURES = {
     "bfir_engine_read_coeff_matrix_levels": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp]),
     "bfir_engine_set_coeff_nup_fade": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd, _ci]),
     "bfir_engine_set_coeff_levels_fade": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd, _ci]),
+    "bfir_engine_set_coeff_matrix_levels_fade": (_ci, [_vp, C.POINTER(_vp), _pi, _cd, _ci]),
     "bfir_engine_fade_remaining_levels": (_ci, [_vp]),
     "bfir_convolver_create": (_vp, [_ci, _ci, _ci, _pi]),
     "bfir_convolver_destroy": (None, [_vp]),

@@ -234,6 +234,9 @@ struct bfir_engine {
     void *zring2 = nullptr;                // on a tail: allocated, like H2 and Yf, at the first fade
     int lf_mode = 0; long long lf_j1 = -1;
     bool lf_stop = false;                  // on a tail: the new set does not reach this level, it stops when the fade ends
+    // Every level of a multi-level matrix engine: a launch that needs both sets of a fade runs k_mac_duo (mfade.hip) instead
+    // of k_mac_matrix twice.  BFIR_MFADE_DUO=0|1, read at creation (choose_path)
+    bool mfade_duo = true;
     // profiling
     bool profiling = false;
     struct Span { int k; hipEvent_t a, b; };
@@ -385,6 +388,9 @@ static void choose_path(bfir_engine *e)
             !(fp && atoi(fp) == 0))
             e->ilv = true;
     }
+    // both sets of a fading multi-level matrix engine in one MAC launch (k_mac_duo), the default: lower than two launches of
+    // k_mac_matrix in every paired run ("Crossfades on multi-level matrix engines"); BFIR_MFADE_DUO=0 keeps the two
+    if (const char *mv = getenv("BFIR_MFADE_DUO")) e->mfade_duo = atoi(mv) != 0;
     if (const char *pm = getenv("BFIR_PIPE")) { e->pipe3 = atoi(pm) >= 3; e->serial = atoi(pm) == 1; }
     // fp64 engines: one stream.  Their kernels are bound by issue and latency, not by memory, each fills the GPU by itself, and
     // three of them side by side only get into each other's way: the plug-in's shape 42.8 -> 45.9 Gsamples/s, 8 channels 42.5 ->
@@ -966,6 +972,7 @@ extern "C" int bfir_engine_set_coeff_matrix_levels(bfir_engine *e, const void *c
         if (coeffs[n] && (lengths[n] < 0 || (long long)lengths[n] > cap)) return BFIR_ERR_ARG;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
+    if (e->fade_len > 0) { e->fade_len = e->fade_pos = 0; lfade_finish(e, false); }   // a plain change during a fade cancels it: a hard cut
     e->eng_init[0] = 0;
     // a NaN / Inf tap anywhere is refused before anything is uploaded at any level
     for (int n = 0; n < P; n++) {
@@ -1054,6 +1061,7 @@ static void lfade_finish(bfir_engine *e, bool take_new)
 {
     for (int i = 0; i < e->n_tail; i++) {
         bfir_engine *t = e->tail[i];
+        if (take_new && e->mlevels && t->pair_cap) matrix_take_path(t, t->pair_new);   // after the fade the new set decides
         if (!t->lf_mode) continue;
         if (take_new && t->lf_mode == 1) tail_swap_sets(t);
         if (take_new || t->lf_mode == 2) std::swap(t->zring, t->zring2);
@@ -1340,6 +1348,30 @@ static int matrix_chunk_ok(const bfir_engine *e, int tc)
 {
     if (e->matrix && !mac_matrix_supported(matrix_mac_args(e, 0, nullptr, tc))) {
         bfir_logf("bfir engine: %d blocks per launch are past the matrix MAC's grid.", tc);
+        return BFIR_ERR_UNSUPPORTED;
+    }
+    return BFIR_OK;
+}
+
+// Both sets of a fading level of a multi-level matrix engine in one launch (k_mac_duo, mfade.hip): the old set as
+// matrix_mac_args gives it, the new set into Y2.
+static bool chunk_takes_duo(const bfir_engine *e) { return e->matrix && e->mfade_duo && (e->mlevels || e->nup_tail); }
+
+static MatDuoArgs matrix_duo_args(const bfir_engine *e, int base_slot, void *Y, void *Y2, long y2_ch_stride, int tc)
+{
+    MatDuoArgs d;
+    d.a = matrix_mac_args(e, base_slot, Y, tc);
+    d.h2 = e->H2;
+    for (int j = 0; j < BFIR_MAT_MAX * BFIR_MAT_MAX; j++) d.nblk2[j] = j < (int)e->nblk2.size() ? e->nblk2[j] : 0;
+    d.y2 = Y2; d.y2_ch_stride = y2_ch_stride;
+    return d;
+}
+
+// ... whose grid differs from k_mac_matrix's (other time tiles): refused before anything is queued, as matrix_chunk_ok
+static int matrix_fade_chunk_ok(const bfir_engine *e, int tc)
+{
+    if (chunk_takes_duo(e) && !mac_duo_supported(matrix_duo_args(e, 0, nullptr, nullptr, 0, tc))) {
+        bfir_logf("bfir engine: %d fading blocks per launch are past the matrix MAC's grid.", tc);
         return BFIR_ERR_UNSUPPORTED;
     }
     return BFIR_OK;
@@ -1647,7 +1679,7 @@ static void queue_inv_lfade(bfir_engine *e, const Chunk &c, hipStream_t st)
         for (int k = 0; k < BFIR_LEVEL_RINGS; k++) { a.ring[k] = ring[k]; a.z_new[k] = z_new[k]; }
         a.n_rings = nr;
         a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
-        a.n_ch = e->C; a.n_t = c.tc;
+        a.n_ch = e->Co; a.n_t = c.tc;                      // a matrix engine: its outputs, an odd count included
         a.scale = (float)e->out_scale; a.max = (float)e->of_max;
         a.f = e->fade_f; a.m0 = c.m0;
         a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
@@ -1659,7 +1691,7 @@ static void queue_inv_lfade(bfir_engine *e, const Chunk &c, hipStream_t st)
     {
         ProfScope ps(e, BFIR_K_INV, st);
         InvArgs a;
-        a.n_t = c.tc; a.n_ch = e->GC;
+        a.n_t = c.tc; a.n_ch = e->GCo;
         a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
         a.dst_ch_stride = t_stride;
         a.src = c.Y; a.src_ch_stride = (long)e->chunk * e->N; a.dst = e->ft[0];
@@ -1670,7 +1702,7 @@ static void queue_inv_lfade(bfir_engine *e, const Chunk &c, hipStream_t st)
         b.y_old = e->ft[0]; b.y_new = e->ft[1]; b.ch_stride = t_stride;
         for (int k = 0; k < BFIR_LEVEL_RINGS; k++) { b.ring[k] = ring[k]; b.z_new[k] = z_new[k]; }
         b.n_rings = nr;
-        b.n_ch = e->GC; b.n = (long)c.tc * e->L;
+        b.n_ch = e->GCo; b.n = (long)c.tc * e->L;
         b.f = e->s == 4 ? (double)e->fade_f : e->fade_d; b.m0 = c.m0; b.realsize = e->s;
         launch_lfade_sum(b, st);
     }
@@ -1709,6 +1741,8 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     c.fade = e->fade_len > 0;
     const bool both = c.fade || e->lf_mode == 1;   // ... or, a tail level of a fading engine, all up to its last old block: both sets
     if (both) { c.Y2 = e->Yf[e->pipe3 ? par : 0]; c.y2_ch_stride = (long)e->yf_blocks * e->N; c.m0 = e->fade_pos * e->L; }
+    const bool duo = both && chunk_takes_duo(e);
+    if (duo) { rc = matrix_fade_chunk_ok(e, tc); if (rc != BFIR_OK) return rc; }
     rc = chunk_aligned(e, p, c);
     if (rc != BFIR_OK) return rc;
     if (c.fade && e->fade_fused && (((uintptr_t)d_out | (uintptr_t)out_stride) & 3)) {
@@ -1731,9 +1765,12 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     }
     {
         ProfScope ps(e, BFIR_K_MAC, sm);
-        if (!e->matrix) launch_mac(mac_args(e, c.base_slot, c.Y, tc), sm);
+        if (duo) {   // a multi-level matrix engine: both sets in one pass over the delay line
+            if (launch_mac_duo(matrix_duo_args(e, c.base_slot, c.Y, c.Y2, c.y2_ch_stride, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
+        }
+        else if (!e->matrix) launch_mac(mac_args(e, c.base_slot, c.Y, tc), sm);
         else if (launch_mac_matrix(matrix_mac_args(e, c.base_slot, c.Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
-        if (both) {   // the same delay line through the same kernels with the new set, behind the first
+        if (both && !duo) {   // the same delay line through the same kernels with the new set, behind the first
             if (!e->matrix) { MacArgs a = mac_args(e, c.base_slot, c.Y2, tc, true); a.y_ch_stride = c.y2_ch_stride; launch_mac(a, sm); }
             else {
                 MatArgs a = matrix_mac_args(e, c.base_slot, c.Y2, tc, true); a.y_ch_stride = c.y2_ch_stride;
@@ -1924,6 +1961,152 @@ extern "C" int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *con
     return set_coeff_split_fade(e, coeffs, n_coeffs, length, scale, fade_blocks);
 }
 
+// The crossfade of a multi-level matrix engine: the schedule of set_coeff_split_fade (catch-up, lf_mode, second rings,
+// lfade_finish) with the split of bfir_engine_set_coeff_matrix_levels -- every filter of its own length, cut at every D_k,
+// partition counts per filter and level (0: skipped there) -- and the front-end rule of bfir_engine_set_coeff_matrix_fade.
+extern "C" int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const void *const *coeffs, const int *lengths, double scale,
+                                                        int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || !lengths) return BFIR_ERR_ARG;
+    const int P = e->Co * e->C;                                 // filters, [o][i]
+    long long cap = (long long)e->B * e->L;
+    for (int i = 0; i < e->n_tail; i++) cap += (long long)e->tail[i]->B * e->tail[i]->L;
+    for (int n = 0; n < P; n++)
+        if (coeffs[n] && (lengths[n] < 0 || (long long)lengths[n] > cap)) return BFIR_ERR_ARG;
+    // m = 0 .. K L - 1 must be exact as a float (fftw_convolver.cpp:302 multiplies by (float)n)
+    if (fade_blocks < 1 || (long long)fade_blocks * e->L > (1ll << 24)) return BFIR_ERR_ARG;
+    if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
+    // the split of bfir_engine_set_coeff_matrix_levels: per level, the part of every filter that falls into it
+    bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
+    std::vector<const void *> part[BFIR_MAX_LEVELS];
+    std::vector<int> len[BFIR_MAX_LEVELS], nb2[BFIR_MAX_LEVELS];
+    int nb_max[BFIR_MAX_LEVELS] = {0, 0, 0, 0};
+    for (int k = 0; k <= e->n_tail; k++) {
+        const bfir_engine *l = lv[k];
+        const long long D = k == 0 ? 0 : (long long)e->lv_D[k - 1] * e->L;
+        part[k].assign((size_t)P, nullptr); len[k].assign((size_t)P, 0); nb2[k].assign(l->nblk.size(), 0);
+        for (int n = 0; n < P; n++) {
+            const long long rest = coeffs[n] ? std::min((long long)lengths[n] - D, (long long)l->B * l->L) : 0;
+            len[k][n] = (int)std::max(0ll, rest);
+            part[k][n] = len[k][n] > 0 ? (const char *)coeffs[n] + (size_t)D * e->s : nullptr;
+            nb2[k][n] = (len[k][n] + l->L - 1) / l->L;
+            nb_max[k] = std::max(nb_max[k], nb2[k][n]);
+        }
+        // a level no filter of the old set reaches runs no forward transforms: it has no delay line to fade on (per level,
+        // not per filter: a filter that is new on a running level fades in)
+        if (k > 0 && nb_max[k] > 0 && !e->lv_active[k - 1]) {
+            bfir_logf("bfir engine: the new filters reach level %d, the active ones do not: load the first set zero-padded to the "
+                      "longest length that will be faded to.", k);
+            return BFIR_ERR_UNSUPPORTED;
+        }
+    }
+    // a NaN / Inf tap at any level is refused before anything is uploaded at any level: the engine keeps running the old set
+    for (int n = 0; n < P; n++) {
+        if (!coeffs[n]) continue;
+        bool finite = true;
+        if (e->s == 4) {
+            const float *src = (const float *)coeffs[n];
+            const float sc = (float)scale;
+            for (int i = 0; i < lengths[n]; i++) finite &= std::isfinite((double)(src[i] * sc));
+        } else {
+            const double *src = (const double *)coeffs[n];
+            for (int i = 0; i < lengths[n]; i++) finite &= std::isfinite(src[i] * scale);
+        }
+        if (!finite) {
+            bfir_logf("NaN or Inf value among coefficients.");
+            bfir_logf("Error preprocessing coefficient %d (output %d, input %d)", n, n / e->C, n % e->C);
+            return BFIR_ERR_COEFF;
+        }
+    }
+    // the catch-up's launches (up to a tail's chunk) must fit the matrix MAC's grid: refused before anything changes
+    for (int i = 0; i < e->n_tail; i++)
+        if (e->lv_active[i]) { const int rc = matrix_chunk_ok(e->tail[i], e->tail[i]->chunk); if (rc != BFIR_OK) return rc; }
+    HIP_TRY(hipSetDevice(e->device));
+    // queued work may still read what was H before the last fade's swap, and the catch-up below reads the delay lines: the
+    // device is idle from here to the end of the call
+    HIP_TRY(hipDeviceSynchronize());
+    // H2 with its per-filter counts, the second ring and Yf of every level: allocated at the first fade
+    for (bfir_engine *l : lv) {
+        if (!l || l->H2) continue;
+        HIP_TRY(hipMalloc(&l->H2, (size_t)P * l->B * cbuf_bytes(l)));
+        HIP_TRY(hipMalloc((void **)&l->d_nblk2, sizeof(int) * l->GC));   // not read by the matrix MAC; swapped with d_nblk
+    }
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        if (!t->zring2) HIP_TRY(hipMalloc(&t->zring2, (size_t)t->GCo * t->zblocks * t->L * t->s));
+    }
+    e->fade_fused = e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L);
+    if (e->fade_fused && !e->plan2.tw && fft_plan_create(&e->plan2, 2 * e->L, 4) != 0) return BFIR_ERR_HIP;
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = lv[k];
+        if (k > 0 && !e->lv_active[k - 1]) continue;
+        if (nb_max[k] > 0) {   // a level the new set does not reach: every count 0, its products with the new set are stored as zeros
+            const int rc = load_filters(l, l->H2, 0, P, part[k].data(), P, 0, nb_max[k], scale, true, len[k].data());
+            if (rc != BFIR_OK) return rc;
+        } else HIP_TRY(hipMemset(l->H2, 0, (size_t)P * l->B * cbuf_bytes(l)));
+        l->nblk2 = nb2[k];
+    }
+    // Front end: a level pairs channels only while every input is read under BOTH sets (an input is read if any filter of
+    // its column has taps on any level); after the fade the new set decides (fade_swap_sets, lfade_finish).  The head of an
+    // engine without taps beyond D_1 and an odd output count is direct, as bfir_engine_set_coeff_matrix_levels has it.
+    bool read_old = true, read_new = true, tail_old = false, tail_new = false;
+    for (int i = 0; i < e->C; i++) {
+        bool ro = false, rn = false;
+        for (int o = 0; o < e->Co; o++) {
+            for (int k = 0; k <= e->n_tail; k++) ro = ro || lv[k]->nblk[o * e->C + i] > 0;
+            rn = rn || (coeffs[o * e->C + i] && lengths[o * e->C + i] > 0);
+        }
+        read_old = read_old && ro; read_new = read_new && rn;
+    }
+    for (int i = 0; i < e->n_tail; i++) { tail_old = tail_old || e->lv_active[i]; tail_new = tail_new || nb_max[i + 1] > 0; }
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        t->pair_new = read_new;
+        if (t->pair_cap) matrix_take_path(t, read_old && read_new);
+    }
+    if (e->pair_cap) {
+        const bool odd = (e->Co & 1) != 0;
+        e->pair_new = read_new && !(odd && !tail_new);
+        matrix_take_path(e, e->pair_new && read_old && !(odd && !tail_old));
+    }
+    // Catch-up, as set_coeff_split_fade: the blocks a level has run with the old set that the fade's first head block, or a
+    // later one, reads under the new set -- their MAC again, with the new set alone, on the delay line the level still holds
+    const long long a_f = (long long)e->blockcounter;
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        if (!e->lv_active[i]) continue;
+        const int r = e->lv_r[i];
+        int rc = ensure_fade_buffers(t);
+        if (rc != BFIR_OK) return rc;
+        HIP_TRY(hipMemsetAsync(t->zring2, 0, (size_t)t->GCo * t->zblocks * t->L * t->s, e->stream));
+        long long j0 = std::max(t->z_from, floor_div(a_f - e->lv_D[i], r));
+        j0 = std::max(j0, t->z_next - std::min<long long>((long long)t->blockcounter, t->ring_extra));
+        for (long long j = j0; j < t->z_next;) {
+            const int n = (int)std::min<long long>(t->z_next - j, t->yf_blocks);
+            const long long bc = (long long)t->blockcounter - (t->z_next - j);   // the level's own count of block j
+            MatArgs a = matrix_mac_args(t, (int)(bc % t->ring), t->Yf[0], n, true);
+            a.y_ch_stride = (long)t->yf_blocks * t->N;
+            if (launch_mac_matrix(a, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;   // checked above: not reached
+            inv_to_ring(t, t->Yf[0], a.y_ch_stride, t->zring2, j, n, e->stream);
+            j += n;
+        }
+        t->lf_j1 = floor_div(a_f + fade_blocks - 1 - e->lv_D[i], r);
+        t->lf_stop = nb_max[i + 1] == 0;
+        t->lf_mode = 1;
+        if (t->z_next > t->lf_j1) { tail_swap_sets(t); t->lf_mode = 2; }   // every old block the fade reads has run
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    e->fade_f = (float)(1.0 / (double)(float)(fade_blocks * e->L - 1));
+    e->fade_d = 1.0 / (double)(fade_blocks * e->L - 1);
+    e->fade_len = fade_blocks; e->fade_pos = 0;
+    bfir_logf("bfir matrix engine: crossfade over %d blocks on %d levels; a launch that needs both sets runs %s.", fade_blocks,
+              e->n_tail + 1, chunk_takes_duo(e) ? "k_mac_duo" : "k_mac_matrix twice");
+    return BFIR_OK;
+}
+
 extern "C" int bfir_engine_fade_remaining_levels(const bfir_engine *e)
 {
     if (!e) return BFIR_ERR_ARG;
@@ -2021,6 +2204,11 @@ static int run_blocks(bfir_engine *e, const void *d_in, long in_stride, void *d_
     if (e->mlevels) {   // every level's MAC must take its longest launch of this call: refused before anything is queued
         int rc = matrix_chunk_ok(e, std::min(e->chunk, n));
         for (int i = 0; i < e->n_tail && rc == BFIR_OK; i++) rc = matrix_chunk_ok(e->tail[i], std::min(e->tail[i]->chunk, n));
+        if (rc == BFIR_OK && e->fade_len > 0) {   // ... and, fading, the launches that take both sets
+            rc = matrix_fade_chunk_ok(e, std::min(e->chunk, n));
+            for (int i = 0; i < e->n_tail && rc == BFIR_OK; i++)
+                if (e->tail[i]->lf_mode == 1) rc = matrix_fade_chunk_ok(e->tail[i], std::min(e->tail[i]->chunk, n));
+        }
         if (rc != BFIR_OK) return rc;
     }
     for (int c0 = 0; c0 < n;) {

@@ -179,6 +179,20 @@ struct MatArgs {
 bool mac_matrix_supported(const MatArgs &a);               // the grid of the launch fits
 int launch_mac_matrix(const MatArgs &a, hipStream_t s);    // 0, or -1 if !mac_matrix_supported(a) (nothing launched)
 
+// mfade.hip: k_mac_duo, the matrix MAC of a chunk that needs BOTH filter sets of a crossfaded coefficient change on a
+// multi-level matrix engine (bfir_engine_set_coeff_matrix_levels_fade): one pass over the delay line computes
+//   Y [o][t] = sum_i sum_{p < a.nblk[o][i]} X[i][slot(t - p)] * H [o][i][p]     (a: the old set, exactly launch_mac_matrix(a))
+//   Y2[o][t] = sum_i sum_{p < nblk2[o][i]}  X[i][slot(t - p)] * H2[o][i][p]     (the new set: h2, nblk2, y2, y2_ch_stride)
+// with k_mac_matrix's fma chain per (set, output, bin, block): the bits of two launch_mac_matrix calls.
+struct MatDuoArgs {
+    MatArgs a;                                               // the old set and everything both sets share
+    const void *h2;                                          // [n_out][n_in][B][N], pairs a.h_pair_stride apart as in a.h
+    int nblk2[BFIR_MAT_MAX * BFIR_MAT_MAX];                  // [o n_in + i], by value
+    void *y2; long y2_ch_stride;                             // [n_out][..][N]
+};
+bool mac_duo_supported(const MatDuoArgs &d);               // the grid of the launch fits
+int launch_mac_duo(const MatDuoArgs &d, hipStream_t s);    // 0, or -1 if !mac_duo_supported(d) (nothing launched)
+
 // a11 + a12: inverse real FFT of Y[gc][t] (grouped layout, times in_scale),
 // first L samples to dst + gc*dst_ch_stride + t*L.
 struct InvArgs {

@@ -20,37 +20,11 @@
 #include <climits>
 
 #include "fft_lds.h"
+#include "mat_ops.h"
 
 namespace bfir {
 
 namespace {
-
-// one complex multiply-add of k_mac_small's order; DCNY: lane k == 0 keeps two real sums instead
-template <bool DCNY, typename T>
-__device__ __forceinline__ void mat_cmac(T &ar, T &ai, T xr, T xi, T hr, T hi, bool k0)
-{
-    const T r1 = fma(xr, hr, ar);
-    const T r2 = fma(-xi, hi, r1);
-    const T i2 = fma(xi, hr, fma(xr, hi, ai));
-    if constexpr (DCNY) {
-        const T ny = fma(xi, hi, ai);
-        ar = k0 ? r1 : r2; ai = k0 ? ny : i2;
-    } else {
-        ar = r2; ai = i2;
-    }
-}
-
-template <typename T, bool ILV>
-__device__ __forceinline__ void mat_ld(const T *__restrict__ s, int ore, int oim, T &re, T &im)
-{
-    if constexpr (ILV) {
-        using V2 = typename Vec2<T>::type;
-        const V2 v = *(const V2 *)(s + ore);
-        re = v.x; im = v.y;
-    } else {
-        re = s[ore]; im = s[oim];
-    }
-}
 
 template <typename T, bool ILV, int NO, int TT, bool DCNY>
 __device__ __forceinline__ void mat_tile(const MatArgs &a, int o0, int t0, int ore, int oim, bool k0,

@@ -407,7 +407,7 @@ class BrutefirMatrixLevels(BrutefirMatrix):
     max_taps are BrutefirLevels'.  Frames are FLOAT_LE or FLOAT64_LE; the default is the working precision's.
 
     run / run_device / sync / reset / overflow / check_overflows / set_chunk / set_profiling / profile / close are
-    BrutefirMatrix's; reset() discards all signal state of all levels.  There is no crossfade on this kind."""
+    BrutefirMatrix's; reset() discards all signal state of all levels.  The crossfade of this kind is fade_to_rows."""
 
     def __init__(self, filter_length, blocks, ratios, realsize, n_in, n_out, in_format=None, out_format=None, device=0):
         dflt = SAMPLE_FORMAT_FLOAT_LE if realsize == 4 else SAMPLE_FORMAT_FLOAT64_LE
@@ -455,7 +455,22 @@ class BrutefirMatrixLevels(BrutefirMatrix):
     def fade_to(self, *args, **kwargs):
         raise BfirError(_lib.ERR_UNSUPPORTED, "bfir_engine_set_coeff_levels_fade")
 
+    def fade_to_rows(self, rows, fade_blocks, scale=1.0):
+        """bfir_engine_set_coeff_matrix_levels_fade: fade to rows (as set_coeff takes them: per-filter lengths, None = no
+        path) over the next `fade_blocks` blocks of filter_length frames, every level and every output consistently (the ramp
+        of fftw_convolver::convolver_crossfade_inplace).  A filter that is None or shorter in one set fades in or out.
+        Returns 0 or an ERR_* code: ERR_COEFF (a NaN / Inf tap) leaves the engine running the old filters, ERR_UNSUPPORTED
+        means the new set has taps on a level on which no filter of the old set has any (load the first set zero-padded).
+        fade_to and set_coeff_fade, the calls of the other kinds, keep raising ERR_UNSUPPORTED on this class."""
+        assert len(rows) == self.n_out and all(len(r) == self.n_in for r in rows)
+        rd = _real_dtype(self.s)
+        arrs = [None if h is None else np.ascontiguousarray(h, dtype=rd) for r in rows for h in r]
+        ptrs = (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
+        lens = (C.c_int * len(arrs))(*[0 if a is None else a.size for a in arrs])
+        return self._lib.bfir_engine_set_coeff_matrix_levels_fade(self._h, ptrs, lens, float(scale), int(fade_blocks))
+
     def fade_remaining(self):
+        """Head blocks of a pending or running fade_to_rows still to be processed; 0 = none."""
         return self._lib.bfir_engine_fade_remaining_levels(self._h)
 
     def coeff_block(self, level, output, input, block):

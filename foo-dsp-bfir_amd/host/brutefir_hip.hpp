@@ -129,6 +129,13 @@ public:
         if (!m_e) return -1;
         return bfir_engine_set_coeff_levels_fade(m_e, (const void *const *)coeffs, n_coeffs, length, scale, fade_blocks);
     }
+    // ... and a multi-level matrix engine's, coeffs / lengths as set_coeff_matrix_levels takes them
+    // (bfir_engine_set_coeff_matrix_levels_fade): a filter that is null or shorter in one set fades in or out.
+    int set_coeff_matrix_levels_fade(void **coeffs, const int *lengths, double scale, int fade_blocks)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_matrix_levels_fade(m_e, (const void *const *)coeffs, lengths, scale, fade_blocks);
+    }
     // head blocks of such a fade still to be processed; 0 = none
     int fade_remaining_levels() { return m_e ? bfir_engine_fade_remaining_levels(m_e) : -1; }
 

@@ -205,8 +205,8 @@ int bfir_engine_read_coeff_levels(bfir_engine *e, int level, int channel, int bl
  * depend on whether further outputs exist.  The output does not depend on bfir_engine_set_chunk or on how the blocks arrive.  Frames: n_inputs samples in,
  * n_outputs samples out; bfir_engine_get_overflow(e, o, ..) is output o's; bfir_engine_reset discards all signal state.
  * Such an engine is a kind of its own: every other bfir_engine_set_coeff*, _read_coeff* and fade call returns
- * BFIR_ERR_UNSUPPORTED on it (it has no crossfade: bfir_engine_fade_remaining_levels returns 0), and the three calls below
- * the same on every other kind of engine. */
+ * BFIR_ERR_UNSUPPORTED on it, and the three calls below the same on every other kind of engine.  Its crossfade is
+ * bfir_engine_set_coeff_matrix_levels_fade; bfir_engine_fade_remaining_levels reports it (0 while none is pending). */
 bfir_engine *bfir_engine_create_matrix_levels(int filter_length, int n_levels, const int *blocks, const int *ratios,
                                               int realsize, int n_inputs, int n_outputs, int in_format, int out_format,
                                               int device, int *err);
@@ -304,8 +304,41 @@ int bfir_engine_set_coeff_nup_fade(bfir_engine *e, const void *const *coeffs, in
  * defines it above, the taps split at every D_k as bfir_engine_set_coeff_levels splits them. */
 int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
                                       int fade_blocks);
+/* ... and on an engine from bfir_engine_create_matrix_levels: the same crossfade (fftw_convolver::convolver_crossfade_inplace,
+ * brutefir/fftw_convolver.cpp:275-321, stretched over fade_blocks head blocks) per output.  coeffs / lengths are
+ * [o * n_inputs + i] as bfir_engine_set_coeff_matrix_levels takes them (NULL or 0 taps: no path).  With a_f the block counter
+ * at the call and K = fade_blocks, sample m = 0 .. K L - 1 of output o is fade_blend(S_old,o[m], S_new,o[m], f, m) with the
+ * blend, f and d of bfir_engine_set_coeff_fade and S_x,o = ((y_0,o + z_1,o) + z_2,o) + z_3,o under the filters active at the
+ * call (old) and those of the call (new), each term the sum over the inputs that the matrix engine of that level computes.
+ * Both sets act on the whole signal history: there is no transient.  Overflow statistics, the NaN guard and the frame store
+ * act on the blended sample.
+ * Errors.  BFIR_ERR_ARG: a null engine, `coeffs` or `lengths`; a length outside 0 .. D_(n_levels); fade_blocks < 1; K L >
+ * 2^24.  BFIR_ERR_STATE: no coefficients yet, or a fade is pending or running.  BFIR_ERR_COEFF: a NaN / Inf tap in any filter
+ * at any level, refused before anything is uploaded; the engine stays initialised on the old set.  BFIR_ERR_UNSUPPORTED: every
+ * other kind of engine (this kind keeps refusing the five other fade calls); and a new set with taps on a level on which no
+ * filter of the old set has any -- per level, not per filter; nothing changes.  The way round it: load the first set
+ * zero-padded, as for bfir_engine_set_coeff_levels_fade.
+ * Per-filter reach.  A filter that is NULL or shorter in one set and present or longer in the other fades in or out; on a
+ * level it has partition count 0 in the set where it does not reach that level and is skipped there, never multiplied by
+ * zero.  A new set that reaches no active tail level at all stops that level after the fade, as a
+ * bfir_engine_set_coeff_matrix_levels of those lengths would.  If neither set has taps beyond D_1 the fade is the one of
+ * bfir_engine_set_coeff_matrix_fade on bfir_engine_create_matrix(L_0, blocks[0], ...).
+ * Front end: the rule of bfir_engine_set_coeff_matrix_fade.  During the fade a level pairs channels only while every input
+ * is read under BOTH sets (an input is read if any filter of its column has taps on any level of that set); after the fade
+ * the new set decides.  A level that changes mode does so as after a bfir_engine_set_coeff_matrix_levels mid-stream.
+ * Byte identities.  Blocks before a_f are those of an engine that never faded.  If both sets read every input, or the engine
+ * cannot pair channels at all, blocks from a_f + K on are those of an engine that has had the new filters all along; else
+ * they agree with it to rounding (pair and direct transforms round differently).  The output does not depend on
+ * bfir_engine_set_chunk or on how the blocks arrive.
+ * bfir_engine_set_coeff_matrix_levels during a fade ends it and cuts hard; bfir_engine_reset ends it with the new set active
+ * at every level; bfir_engine_read_coeff_matrix_levels reads the head's old set while the fade remains and the new set
+ * afterwards.  Memory: the first fade allocates, per level, a second filter set with its per-filter partition counts, a
+ * second time ring and a second product buffer, sized by n_outputs where the first ones are. */
+int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const void *const *coeffs, const int *lengths, double scale,
+                                             int fade_blocks);
 /* Head blocks of a pending or running fade (fftw_convolver.cpp:275-321 over fade_blocks blocks) of an engine from
- * bfir_engine_create_nup or _levels still to be processed; 0 = none.  BFIR_ERR_UNSUPPORTED on every other kind of engine. */
+ * bfir_engine_create_nup, _levels or _matrix_levels still to be processed; 0 = none.  BFIR_ERR_UNSUPPORTED on every other kind
+ * of engine. */
 int bfir_engine_fade_remaining_levels(const bfir_engine *e);
 
 /* brutefir::run (brutefir.cpp:244-343) for n_blocks consecutive blocks.
