@@ -13,6 +13,7 @@ SAMPLE_FORMAT_FLOAT64_LE = 10
 MIXMODE_INPUT, MIXMODE_INPUT_ADD, MIXMODE_OUTPUT = 1, 2, 3
 OK, ERR_NONFINITE, ERR_COEFF, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_STATE, ERR_UNSUPPORTED, ERR_IO = (
     0, -1, -2, -3, -4, -5, -6, -7, -8)
+DELAY_INPUT, DELAY_OUTPUT = 0, 1
 K_STAGE_IN, K_FWD, K_MAC, K_INV, K_STAGE_OUT = range(5)
 KERNEL_NAMES = ("k_stage_in", "k_fwd", "k_mac", "k_inv", "k_stage_out")
 
@@ -85,6 +86,11 @@ SIGNATURES = {
     "bfir_engine_set_coeff_levels_fade": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd, _ci]),
     "bfir_engine_set_coeff_matrix_levels_fade": (_ci, [_vp, C.POINTER(_vp), _pi, _cd, _ci]),
     "bfir_engine_fade_remaining_levels": (_ci, [_vp]),
+    "bfir_subdelay_filter": (_ci, [_ci, _ci, _ci, _cd, _ci, _vp]),
+    "bfir_engine_delay_init": (_ci, [_vp, _ci, _ci, _ci, _ci, _cd]),
+    "bfir_engine_set_delay": (_ci, [_vp, _ci, _pi, _pi, _ci]),
+    "bfir_engine_get_delay": (_ci, [_vp, _ci, _pi, _pi, _ci]),
+    "bfir_engine_delay_latency": (_ci, [_vp, _ci]),
     "bfir_convolver_create": (_vp, [_ci, _ci, _ci, _pi]),
     "bfir_convolver_destroy": (None, [_vp]),
     "bfir_convolver_cbufsize": (_ci, [_vp]),

@@ -244,9 +244,35 @@ struct bfir_engine {
     std::vector<hipEvent_t> ev_pool;
     double prof_ms[BFIR_K_COUNT] = {0, 0, 0, 0, 0};
     long prof_n[BFIR_K_COUNT] = {0, 0, 0, 0, 0};
+    // Per-channel delays on the input frames (side 0: the engine proper reads the delayed stream) and on the output frames
+    // (side 1: the caller receives it); bfir_engine_delay_init, delay.hip.  A side keeps the last H = max_delay + 2 h raw
+    // frames of its stream in hist[cur] -- every launch writes the next history into the other buffer -- one piece
+    // (e->chunk blocks) of scratch frames between its kernels and the engine proper, and the table its kernels read.
+    struct DelaySide {
+        bool on = false;
+        int max_delay = 0, steps = 0, h = 0;
+        double beta = 0.0;
+        long H = 0;
+        void *hist[2] = {nullptr, nullptr}; int cur = 0;
+        void *scratch = nullptr; size_t scratch_bytes = 0;
+        void *d_tab = nullptr;             // DelayTab, then the taps
+        std::vector<int> delay, sub;       // host copy: what bfir_engine_get_delay returns
+    };
+    DelaySide dly[2];
+    hipEvent_t ev_dly = nullptr;           // the delayed input piece is in scratch: the front waits for this
+    hipEvent_t ev_dly_done = nullptr; hipStream_t dly_stream = nullptr;   // the last call's launches, and the stream they went to
 };
 
 static size_t cbuf_bytes(const bfir_engine *e) { return (size_t)e->N * (size_t)e->s; }
+
+// everything a delayed side owns (the device is idle)
+static void delay_free(bfir_engine *e, int side)
+{
+    bfir_engine::DelaySide &d = e->dly[side];
+    void *bufs[] = {d.hist[0], d.hist[1], d.scratch, d.d_tab};
+    for (void *b : bufs) if (b) (void)hipFree(b);
+    d = bfir_engine::DelaySide();
+}
 
 // Copy the two history blocks into the engine-owned `saved` buffers so they
 // survive the work buffers they may point into.  A reference only ever points
@@ -718,6 +744,9 @@ extern "C" void bfir_engine_destroy(bfir_engine *e)
     if (e->zring) (void)hipFree(e->zring);
     if (e->zring2) (void)hipFree(e->zring2);
     if (e->ev_nup) (void)hipEventDestroy(e->ev_nup);
+    for (int side = 0; side < 2; side++) delay_free(e, side);
+    if (e->ev_dly) (void)hipEventDestroy(e->ev_dly);
+    if (e->ev_dly_done) (void)hipEventDestroy(e->ev_dly_done);
     free_work(e);
     fft_plan_destroy(&e->plan);
     fft_plan_destroy(&e->plan2);
@@ -2232,6 +2261,190 @@ static int run_blocks(bfir_engine *e, const void *d_in, long in_stride, void *d_
     return BFIR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Per-channel input and output delays (delay.cpp:27-140, 148-265, 552-600; kernels in delay.hip)
+// ---------------------------------------------------------------------------
+static int delay_channels(const bfir_engine *e, int side) { return side == BFIR_DELAY_INPUT ? e->C : e->Co; }
+static int delay_sample_bytes(const bfir_engine *e, int side) { return side == BFIR_DELAY_INPUT ? e->in_bytes : e->out_bytes; }
+static bool delay_side_ok(int side) { return side == BFIR_DELAY_INPUT || side == BFIR_DELAY_OUTPUT; }
+
+// The side's table as its kernels read it: the delays, which channels have a filter, the filters.  The device is idle.
+static int delay_upload(bfir_engine *e, int side, const int *delay, const int *sub)
+{
+    bfir_engine::DelaySide &d = e->dly[side];
+    const int n_taps = 2 * d.h + 1, C = delay_channels(e, side);
+    std::vector<unsigned char> host(sizeof(DelayTab) + (size_t)BFIR_DELAY_CH * n_taps * e->s, 0);
+    DelayTab *tab = (DelayTab *)host.data();
+    for (int c = 0; c < C; c++) {
+        tab->delay[c] = delay[c];
+        tab->sub[c] = sub[c] != 0;
+        if (sub[c] != 0) {
+            const int rc = bfir_subdelay_filter(d.h, sub[c], d.steps, d.beta, e->s, host.data() + sizeof(DelayTab) + (size_t)c * n_taps * e->s);
+            if (rc != BFIR_OK) return rc;
+        }
+    }
+    HIP_TRY(hipMemcpy(d.d_tab, host.data(), host.size(), hipMemcpyHostToDevice));
+    d.delay.assign(delay, delay + C);
+    d.sub.assign(sub, sub + C);
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_delay_init(bfir_engine *e, int side, int max_delay, int step_count, int half_filter_length,
+                                      double kaiser_beta)
+{
+    if (!e || !delay_side_ok(side) || max_delay < 0 || max_delay > (1 << 24) || step_count < 0 || step_count == 1) return BFIR_ERR_ARG;
+    if (step_count >= 2 && (half_filter_length < 1 || half_filter_length > 128)) return BFIR_ERR_ARG;
+    if (e->n_eng > 1) return BFIR_ERR_UNSUPPORTED;
+    if (step_count >= 2 && !fmt_is_native(side == BFIR_DELAY_INPUT ? e->in_fmt : e->out_fmt)) return BFIR_ERR_UNSUPPORTED;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    e->async_pending = false;
+    delay_free(e, side);
+    bfir_engine::DelaySide &d = e->dly[side];
+    d.max_delay = max_delay; d.steps = step_count; d.h = step_count >= 2 ? half_filter_length : 0; d.beta = kaiser_beta;
+    d.H = (long)max_delay + 2 * d.h;
+    const size_t hist_bytes = (size_t)std::max(1L, d.H) * delay_channels(e, side) * delay_sample_bytes(e, side);
+    const size_t tab_bytes = sizeof(DelayTab) + (size_t)BFIR_DELAY_CH * (2 * d.h + 1) * e->s;
+    bool ok = hipMalloc(&d.hist[0], hist_bytes) == hipSuccess && hipMalloc(&d.hist[1], hist_bytes) == hipSuccess &&
+              hipMalloc(&d.d_tab, tab_bytes) == hipSuccess;
+    ok = ok && hipMemset(d.hist[0], 0, hist_bytes) == hipSuccess && hipMemset(d.hist[1], 0, hist_bytes) == hipSuccess;
+    ok = ok && (e->ev_dly || hipEventCreateWithFlags(&e->ev_dly, hipEventDisableTiming) == hipSuccess);
+    ok = ok && (e->ev_dly_done || hipEventCreateWithFlags(&e->ev_dly_done, hipEventDisableTiming) == hipSuccess);
+    const std::vector<int> zero(BFIR_DELAY_CH, 0);
+    int rc = ok ? delay_upload(e, side, zero.data(), zero.data()) : BFIR_ERR_HIP;
+    if (rc == BFIR_OK && hipDeviceSynchronize() != hipSuccess) rc = BFIR_ERR_HIP;
+    if (rc != BFIR_OK) { (void)hipGetLastError(); delay_free(e, side); return rc; }
+    d.on = true;
+    bfir_logf("bfir engine: %s delays up to %d frames%s.", side == BFIR_DELAY_INPUT ? "input" : "output", max_delay,
+              d.steps ? " and a sub-sample stage" : "");
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_set_delay(bfir_engine *e, int side, const int *delay, const int *subdelay, int n_channels)
+{
+    if (!e || !delay || !delay_side_ok(side)) return BFIR_ERR_ARG;
+    bfir_engine::DelaySide &d = e->dly[side];
+    if (!d.on) return BFIR_ERR_STATE;
+    if (n_channels != delay_channels(e, side)) return BFIR_ERR_ARG;
+    std::vector<int> sub(BFIR_DELAY_CH, 0);
+    for (int c = 0; c < n_channels; c++) {
+        if (delay[c] < 0 || delay[c] > d.max_delay) return BFIR_ERR_ARG;
+        sub[c] = subdelay ? subdelay[c] : 0;   // no array: whole samples
+        if (sub[c] != 0 && (d.steps < 2 || sub[c] <= -d.steps || sub[c] >= d.steps)) return BFIR_ERR_ARG;
+    }
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());   // launches already queued read the table as it is
+    e->async_pending = false;
+    return delay_upload(e, side, delay, sub.data());
+}
+
+extern "C" int bfir_engine_get_delay(const bfir_engine *e, int side, int *delay, int *subdelay, int n_channels)
+{
+    if (!e || !delay || !subdelay || !delay_side_ok(side)) return BFIR_ERR_ARG;
+    const bfir_engine::DelaySide &d = e->dly[side];
+    if (!d.on) return BFIR_ERR_STATE;
+    if (n_channels != delay_channels(e, side)) return BFIR_ERR_ARG;
+    for (int c = 0; c < n_channels; c++) { delay[c] = d.delay[c]; subdelay[c] = d.sub[c]; }
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_delay_latency(const bfir_engine *e, int side)
+{
+    if (!e || !delay_side_ok(side)) return BFIR_ERR_ARG;
+    return e->dly[side].on ? e->dly[side].h : 0;
+}
+
+// bfir_engine_reset: both histories read as silence again, the settings stay (the device is idle)
+static void delay_reset(bfir_engine *e)
+{
+    for (int side = 0; side < 2; side++) {
+        bfir_engine::DelaySide &d = e->dly[side];
+        if (!d.on) continue;
+        const size_t bytes = (size_t)std::max(1L, d.H) * delay_channels(e, side) * delay_sample_bytes(e, side);
+        for (void *h : d.hist) (void)hipMemset(h, 0, bytes);
+    }
+}
+
+// One piece of a side: src (n frames, raw) -> the delayed frames in dst, and the next history.
+static void queue_delay(bfir_engine *e, int side, const void *src, void *dst, long n, hipStream_t st)
+{
+    bfir_engine::DelaySide &d = e->dly[side];
+    const int C = delay_channels(e, side), sb = delay_sample_bytes(e, side);
+    const DelayTab *tab = (const DelayTab *)d.d_tab;
+    // the next history: the last H frames of hist || src, into the other buffer
+    DelayCopyArgs up;
+    up.dst = d.hist[1 ^ d.cur]; up.piece = src; up.hist = d.hist[d.cur]; up.n_frames = d.H; up.m0 = n - d.H; up.H = d.H;
+    up.C = C; up.sample_bytes = sb; up.tab = nullptr;
+    if (d.steps >= 2) {
+        DelaySubArgs a;
+        a.dst = dst; a.piece = src; a.hist = d.hist[d.cur]; a.n_frames = n; a.H = d.H;
+        a.C = C; a.sample_bytes = sb; a.realsize = e->s; a.h = d.h;
+        a.tab = tab; a.taps = (const char *)d.d_tab + sizeof(DelayTab);
+        launch_delay_sub(a, st);
+        launch_delay_copy(up, nullptr, st);
+    } else {   // whole samples: the piece and the history update in one launch
+        DelayCopyArgs a;
+        a.dst = dst; a.piece = src; a.hist = d.hist[d.cur]; a.n_frames = n; a.m0 = 0; a.H = d.H;
+        a.C = C; a.sample_bytes = sb; a.tab = tab;
+        launch_delay_copy(a, d.H > 0 ? &up : nullptr, st);
+    }
+    if (d.H > 0) d.cur ^= 1;
+}
+
+// run_blocks with a delayed side: the call in pieces of at most e->chunk blocks; per piece the input kernels on st, ahead
+// of the event the front waits for, the engine proper between the two scratch buffers, and the output kernels on st behind
+// the back end (every chunk's inverse and frame store run on st, after st has waited for that chunk's MAC and so for its
+// front: a piece's launches have all read the input scratch before the next piece's input kernels overwrite it).
+static int run_blocks_delayed(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride, int n, int block_base,
+                              hipStream_t st, hipEvent_t input_ready)
+{
+    bfir_engine::DelaySide &di = e->dly[BFIR_DELAY_INPUT], &dout = e->dly[BFIR_DELAY_OUTPUT];
+    const size_t fin = (size_t)e->C * e->in_bytes, fout = (size_t)e->Co * e->out_bytes;
+    const size_t want[2] = {(size_t)e->chunk * e->L * fin, (size_t)e->chunk * e->L * fout};
+    for (int side = 0; side < 2; side++) {   // the work buffers grew (ensure_chunk): so does the scratch
+        bfir_engine::DelaySide &d = e->dly[side];
+        if (!d.on || d.scratch_bytes >= want[side]) continue;
+        HIP_TRY(hipDeviceSynchronize());
+        if (d.scratch) (void)hipFree(d.scratch);
+        d.scratch = nullptr; d.scratch_bytes = 0;
+        HIP_TRY(hipMalloc(&d.scratch, want[side]));
+        d.scratch_bytes = want[side];
+    }
+    // a caller that changes streams between calls: the histories and the scratch are the last call's until its launches end
+    if (e->dly_stream && e->dly_stream != st && !e->inline_launch) HIP_TRY(hipStreamWaitEvent(st, e->ev_dly_done, 0));
+    for (int c0 = 0; c0 < n;) {
+        const int tc = std::min(e->chunk, n - c0);
+        const void *src = (const char *)d_in + (size_t)c0 * e->L * fin;
+        void *dst = (char *)d_out + (size_t)c0 * e->L * fout;
+        // Every piece is a run_blocks call of its own, and a tail level's first front of a call runs on that level's own
+        // stream, which has waited for nothing yet: with the input side off every piece gets the caller's event (a wait on
+        // an event that has passed costs nothing), with it on the event recorded behind this piece's input kernels.
+        hipEvent_t ready = input_ready;
+        if (di.on) {
+            if (ready) HIP_TRY(hipStreamWaitEvent(st, ready, 0));
+            queue_delay(e, BFIR_DELAY_INPUT, src, di.scratch, (long)tc * e->L, st);
+            src = di.scratch;
+            ready = nullptr;
+            if (!e->inline_launch) { HIP_TRY(hipEventRecord(e->ev_dly, st)); ready = e->ev_dly; }
+        }
+        const int rc = run_blocks(e, src, in_stride, dout.on ? dout.scratch : dst, out_stride, 0, tc, block_base + c0, st, ready);
+        if (rc != BFIR_OK) return rc;
+        if (dout.on) queue_delay(e, BFIR_DELAY_OUTPUT, dout.scratch, dst, (long)tc * e->L, st);
+        c0 += tc;
+    }
+    e->dly_stream = nullptr;   // the latency path ends with its stream idle: nothing is left to wait for
+    if (!e->inline_launch) { HIP_TRY(hipEventRecord(e->ev_dly_done, st)); e->dly_stream = st; }
+    return BFIR_OK;
+}
+
+// the engine proper, behind its delays where a side has them
+static int run_call(bfir_engine *e, const void *d_in, long in_stride, void *d_out, long out_stride, int n, int block_base,
+                    hipStream_t st, hipEvent_t input_ready)
+{
+    if (e->dly[0].on || e->dly[1].on) return run_blocks_delayed(e, d_in, in_stride, d_out, out_stride, n, block_base, st, input_ready);
+    return run_blocks(e, d_in, in_stride, d_out, out_stride, 0, n, block_base, st, input_ready);
+}
+
 static int ensure_chunk(bfir_engine *e, int n_blocks)
 {
     // automatic: as many blocks per launch as give a launch the work of 4096 blocks of the 8-channel, 4096-sample
@@ -2286,7 +2499,7 @@ extern "C" int bfir_engine_run_device(bfir_engine *e, const void *d_in, int64_t 
     if (rc != BFIR_OK) return rc;
     // whatever produced d_in on the caller's stream must be done before the front reads it
     HIP_TRY(hipEventRecord(e->ev_entry, st));
-    rc = run_blocks(e, d_in, in_stride_bytes, d_out, out_stride_bytes, 0, n_blocks, 0, st, e->ev_entry);
+    rc = run_call(e, d_in, in_stride_bytes, d_out, out_stride_bytes, n_blocks, 0, st, e->ev_entry);
     if (rc != BFIR_OK) return rc;
     HIP_TRY(hipGetLastError());
     e->async_pending = true;
@@ -2420,7 +2633,7 @@ static int run_small(bfir_engine *e, const void *inbuf, void *outbuf, int n_bloc
         src = e->dev_in[0]; dst = e->dev_out[0];
     }
     e->inline_launch = true;
-    rc = run_blocks(e, src, (long)per_in, dst, (long)per_out, 0, n_blocks, 0, e->stream, nullptr);   // the work buffers hold e->chunk blocks
+    rc = run_call(e, src, (long)per_in, dst, (long)per_out, n_blocks, 0, e->stream, nullptr);   // the work buffers hold e->chunk blocks
     e->bad_host_cur = nullptr;
     e->inline_launch = false;
     if (rc != BFIR_OK) return rc;
@@ -2486,7 +2699,7 @@ extern "C" int bfir_engine_run(bfir_engine *e, const void *inbuf, void *outbuf, 
             HIP_TRY(hipMemcpyAsync(e->dev_in[b], e->pin_in[b], per_in * e->n_eng, hipMemcpyHostToDevice, e->s_in));
         }
         HIP_TRY(hipEventRecord(e->ev_h2d[b], e->s_in));
-        rc = run_blocks(e, e->dev_in[b], (long)per_in, e->dev_out[b], (long)per_out, 0, tc, c0, e->stream, e->ev_h2d[b]);
+        rc = run_call(e, e->dev_in[b], (long)per_in, e->dev_out[b], (long)per_out, tc, c0, e->stream, e->ev_h2d[b]);
         if (rc != BFIR_OK) return rc;
         HIP_TRY(hipEventRecord(e->ev_comp[b], e->stream));
         HIP_TRY(hipStreamWaitEvent(e->s_out, e->ev_comp[b], 0));
@@ -2529,6 +2742,7 @@ extern "C" void bfir_engine_reset(bfir_engine *e)
 {
     if (!e) return;
     (void)hipSetDevice(e->device);
+    if (e->dly[0].on || e->dly[1].on) { (void)hipDeviceSynchronize(); delay_reset(e); }
     if (e->nup) { nup_reset(e); return; }
     // brutefir.cpp:346-367: counters only.  procblocks = 0 hides every
     // delay-line slot written before the reset (brutefir.cpp:292), which the

@@ -412,4 +412,33 @@ void launch_check_finite(const void *buf, int n, int realsize, int *bad, hipStre
 void launch_cmul_stage(const void *b, const void *c, void *d, int n_fft, int mode, int realsize,
                        hipStream_t s);
 
+// Per-channel delays on an engine's frame streams (delay.hip; bfir_engine_delay_init / _set_delay).  The source of a
+// launch is `hist || piece`: sample m of the piece when m >= 0, else frame H + m of the history (H frames, raw and
+// interleaved like the piece).  The table lives in HBM and is rewritten by bfir_engine_set_delay: the delay of every
+// channel in frames, whether it has a sub-sample filter, and behind it the filters, [BFIR_DELAY_CH][2 h + 1] reals in
+// working precision.
+constexpr int BFIR_DELAY_CH = 8;
+struct DelayTab { int delay[BFIR_DELAY_CH]; int sub[BFIR_DELAY_CH]; };
+// Whole samples, any sample size: frame f of dst (f < n_frames) takes channel c from source frame m0 + f - delay[c].
+// tab == nullptr: no delays -- with m0 = n - H and n_frames = H this writes the next history, the last H frames of
+// `hist || piece`, also where the piece is shorter than H.
+struct DelayCopyArgs {
+    void *dst; const void *piece; const void *hist;
+    long n_frames, m0, H;
+    int C, sample_bytes;
+    const DelayTab *tab;
+};
+// One launch for `a` and, behind its workgroups, for `b` where given (a side's delayed piece and its history update: they
+// read the same two buffers and write different ones).
+void launch_delay_copy(const DelayCopyArgs &a, const DelayCopyArgs *b, hipStream_t s);
+// The sub-sample stage, FLOAT_LE / FLOAT64_LE frames: w_c[n] = sum_k f_c[k] u_c[n - d_c - k], k = 0 .. 2 h ascending, in
+// working precision from an LDS copy of the source span; a channel without a filter is the raw shift u_c[n - d_c - h].
+struct DelaySubArgs {
+    void *dst; const void *piece; const void *hist;
+    long n_frames, H;
+    int C, sample_bytes, realsize, h;
+    const DelayTab *tab; const void *taps;
+};
+void launch_delay_sub(const DelaySubArgs &a, hipStream_t s);
+
 }  // namespace bfir

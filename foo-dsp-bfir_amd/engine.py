@@ -48,6 +48,17 @@ def pinned_frames(fmt, shape_frames_channels):
     return a
 
 
+def subdelay_filter(half_filter_length, subdelay, step_count, kaiser_beta=9.0, realsize=8):
+    """bfir_subdelay_filter: the 2 * half_filter_length + 1 taps of the filter that delays by half_filter_length +
+    subdelay / step_count samples (delay::sample_sinc + firwindow_kaiser).  Host arithmetic: no device needed."""
+    taps = np.zeros(2 * max(0, int(half_filter_length)) + 1, dtype=_real_dtype(realsize) if realsize in (4, 8) else np.float64)
+    rc = _lib.load().bfir_subdelay_filter(int(half_filter_length), int(subdelay), int(step_count), float(kaiser_beta),
+                                          int(realsize), taps.ctypes.data)
+    if rc != 0:
+        raise BfirError(rc, "bfir_subdelay_filter")
+    return taps
+
+
 class Brutefir:
     """brutefir(filter_length, filter_blocks, realsize, channels, in_format,
     out_format, sampling_rate, apply_dither)  -- brutefir/brutefir.hpp:18-25.
@@ -169,6 +180,39 @@ class Brutefir:
             db = float("-inf") if peak == 0.0 else 20.0 * np.log10(peak / o.max)
             out.append((n, o.n_overflows, db))
         return out
+
+    # -- per-channel delays (the reference's delay class, brutefir/delay.hpp) ----
+    def _side_channels(self, side):
+        return self.C if side == _lib.DELAY_INPUT else getattr(self, "n_out", self.C)
+
+    def delay_init(self, side, max_delay, step_count=0, half_filter_length=0, kaiser_beta=9.0):
+        """bfir_engine_delay_init: per-channel delays of up to max_delay frames on the input (side 0) or output (side 1)
+        frames; step_count >= 2 adds the sub-sample stage (2 * half_filter_length + 1 tap filters, steps of 1 / step_count
+        sample, half_filter_length frames of latency).  Returns 0 or an ERR_* code."""
+        return self._lib.bfir_engine_delay_init(self._h, int(side), int(max_delay), int(step_count), int(half_filter_length),
+                                                float(kaiser_beta))
+
+    def set_delay(self, side, delay, subdelay=None):
+        """bfir_engine_set_delay: delay[c] frames (and subdelay[c] steps) for every channel of the side, from the next block
+        on, as a hard cut.  Returns 0 or an ERR_* code; a refused call changes nothing."""
+        d = [int(v) for v in delay]
+        sd = [0] * len(d) if subdelay is None else [int(v) for v in subdelay]
+        assert len(sd) == len(d)
+        n = len(d)
+        return self._lib.bfir_engine_set_delay(self._h, int(side), (C.c_int * max(1, n))(*d), (C.c_int * max(1, n))(*sd), n)
+
+    def get_delay(self, side):
+        """(delays, subdelays) of the side as lists; raises on an error (a side never initialised: ERR_STATE)."""
+        n = self._side_channels(side)
+        d, sd = (C.c_int * n)(), (C.c_int * n)()
+        rc = self._lib.bfir_engine_get_delay(self._h, int(side), d, sd, n)
+        if rc != 0:
+            raise BfirError(rc, "bfir_engine_get_delay")
+        return list(d), list(sd)
+
+    def delay_latency(self, side):
+        """Frames of fixed latency the side's sub-sample stage adds (half_filter_length, or 0 without one)."""
+        return self._lib.bfir_engine_delay_latency(self._h, int(side))
 
     # -- tuning / introspection --------------------------------------------
     def set_chunk(self, blocks_per_launch):

@@ -139,6 +139,33 @@ public:
     // head blocks of such a fade still to be processed; 0 = none
     int fade_remaining_levels() { return m_e ? bfir_engine_fade_remaining_levels(m_e) : -1; }
 
+    // Per-channel delays on the input (side BFIR_DELAY_INPUT) or output (BFIR_DELAY_OUTPUT) frames: what the reference's delay
+    // class does on its host buffers (brutefir/delay.hpp: delay_allocate_buffer + subsample_init, update, subsample_update).
+    // delay_init once per side (step_count 0: whole samples only), then set_delay with one entry per channel of the side --
+    // the inputs / outputs of a matrix engine -- from the next block on, as a hard cut.  0 or a BFIR_ERR_* code.
+    int delay_init(int side, int max_delay, int step_count = 0, int half_filter_length = 0, double kaiser_beta = 9.0)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_delay_init(m_e, side, max_delay, step_count, half_filter_length, kaiser_beta);
+    }
+    int set_delay(int side, const int *delay, const int *subdelay, int n_channels)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_delay(m_e, side, delay, subdelay, n_channels);
+    }
+    int get_delay(int side, int *delay, int *subdelay, int n_channels)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_get_delay(m_e, side, delay, subdelay, n_channels);
+    }
+    // frames of fixed latency the side's sub-sample stage adds (half_filter_length, or 0 without one)
+    int delay_latency(int side) { return m_e ? bfir_engine_delay_latency(m_e, side) : -1; }
+    // the taps of one sub-sample filter (delay::sample_sinc): host arithmetic, no engine needed
+    static int subdelay_filter(int half_filter_length, int subdelay, int step_count, double kaiser_beta, int realsize, void *taps)
+    {
+        return bfir_subdelay_filter(half_filter_length, subdelay, step_count, kaiser_beta, realsize, taps);
+    }
+
     // brutefir.cpp:244-343: one block of filter_length interleaved frames; 0 or -1.
     int run(void *inbuf, void *outbuf) { return run_blocks(inbuf, outbuf, 1); }
 

@@ -366,6 +366,68 @@ void bfir_engine_reset(bfir_engine *e);
 /* copy of brutefir's overflow[channel] (brutefir.cpp:326-334) */
 int bfir_engine_get_overflow(bfir_engine *e, int channel, bfir_overflow *of);
 
+/* ------------------------------------------------------------------ */
+/* per-channel input and output delays, whole-sample and sub-sample:   */
+/* the reference's delay class (brutefir/delay.hpp, delay.cpp) with    */
+/* firwindow_kaiser (brutefir/firwindow.c)                             */
+/* ------------------------------------------------------------------ */
+#define BFIR_DELAY_INPUT  0
+#define BFIR_DELAY_OUTPUT 1
+
+/* delay::sample_sinc + firwindow_kaiser (delay.cpp:278-306, firwindow.c:89-210): the 2h+1 taps, h = half_filter_length, of
+ * the filter that delays by h + subdelay/step_count samples, in realsize precision (float or double at `taps`).  Pure host
+ * arithmetic, no device.  subdelay 0: a unit tap at index h, no window (delay.cpp:229-240).  Otherwise tap n is
+ * sinc(pi ((n - h) - subdelay/step_count)), rounded to float first for realsize 4, times the Kaiser weights exactly as
+ * firwindow_kaiser applies them for a non-zero offset: every tap is multiplied by its weight twice (firwindow.c:129-130,
+ * 153-158).  Two deviations from the reference: kaiser_beta is honoured (delay::sample_sinc ignores its argument and passes
+ * the literal 9, delay.cpp:304: pass 9.0 for the reference's filters), and |subdelay| >= step_count is BFIR_ERR_ARG (the
+ * reference silently skips the filter, delay.cpp:158-161).  BFIR_ERR_ARG also: a null `taps`, step_count < 2,
+ * half_filter_length outside 1 .. 128, a realsize that is not 4 or 8. */
+int bfir_subdelay_filter(int half_filter_length, int subdelay, int step_count, double kaiser_beta,
+                         int realsize, void *taps);
+
+/* delay_allocate_buffer + delay::subsample_init (delay.cpp:56-140, 182-265) for one side of an engine: side
+ * BFIR_DELAY_INPUT delays the caller's frames before the engine proper reads them, BFIR_DELAY_OUTPUT what the engine
+ * proper writes before the caller receives it.  An engine on which this was never called runs exactly the code it ran
+ * before these calls existed.
+ * With u_c[n] channel c of the side's frame stream, n counted from creation or the last bfir_engine_reset (u_c[n] = 0 for
+ * n < 0), w the delayed stream, and d_c, s_c the values in force when the block that holds n is processed:
+ *   step_count == 0 (no sub-sample stage; half_filter_length and kaiser_beta are ignored):
+ *     w_c[n] = u_c[n - d_c], a copy of the raw sample bytes, so every sample format (1, 2, 3, 4 or 8 bytes) is served;
+ *   step_count >= 2:
+ *     w_c[n] = sum over k = 0 .. 2h of f_{s_c}[k] u_c[n - d_c - k], f from bfir_subdelay_filter(h, s_c, step_count,
+ *     kaiser_beta, realsize): a delay of d_c + h + s_c/step_count samples.  Taps and accumulation in the engine's working
+ *     precision, k ascending; samples are converted from the frame type on load and rounded once on store.  A channel
+ *     with s_c = 0 is copied from u_c[n - d_c - h], not multiplied: its bytes, NaNs included, are a pure shift.
+ * On the output side format conversion, overflow statistics and the NaN guard act on u, before the delay.
+ * bfir_engine_set_delay applies from the next block processed and is a hard cut: the read position jumps, and the history
+ * is that of u, so a longer delay repeats samples already played -- a deviation from the reference, which emits silence
+ * while its buffer refills (delay.cpp:585-596).  The result does not depend on how the blocks arrive (one call or many,
+ * host or device pointers, the latency path, any bfir_engine_set_chunk).  bfir_engine_reset zeroes the histories of both
+ * sides and keeps the settings.  delay_init may be called again: it waits for queued work, discards that side's history
+ * and sets that side's delays to 0.  Works on every kind of engine but a batch, fades included; a dithered integer output
+ * takes whole-sample delays.
+ * BFIR_ERR_ARG: a null engine; a side other than 0 / 1; max_delay < 0 or > 2^24; step_count negative or 1;
+ * half_filter_length outside 1 .. 128 when step_count >= 2.  BFIR_ERR_UNSUPPORTED: a batch (n_engines > 1); step_count >= 2
+ * on a side whose frames are not FLOAT_LE / FLOAT64_LE.  BFIR_ERR_HIP: the device is out of memory; the side is then off.
+ * Memory per side: two histories of max_delay + 2h frames and one scratch buffer of one launch's frames -- the blocks per
+ * launch of bfir_engine_set_chunk times filter_length frames, whatever the length of a call: with the automatic setting and
+ * calls that long, 4096 blocks of the 8-channel, 4096-sample fp32 shape, 512 MiB per delayed side; a call of n blocks never
+ * makes it larger than n blocks. */
+int bfir_engine_delay_init(bfir_engine *e, int side, int max_delay, int step_count,
+                           int half_filter_length, double kaiser_beta);
+
+/* delay::update / change_delay (delay.cpp:27-54, 552-600) + subsample_update (:148-180) for all channels of a side:
+ * delay[c] frames, 0 .. max_delay, and subdelay[c] steps, |subdelay[c]| < step_count (a null subdelay: all 0; non-zero on
+ * a side without the stage: BFIR_ERR_ARG).  n_channels must be the side's channel count: the inputs / outputs of a matrix
+ * engine, else the channels.  Waits for queued work.  BFIR_ERR_STATE on a side never initialised; a refused call changes
+ * nothing.  get_delay returns what was set (both arrays required). */
+int bfir_engine_set_delay(bfir_engine *e, int side, const int *delay, const int *subdelay, int n_channels);
+int bfir_engine_get_delay(const bfir_engine *e, int side, int *delay, int *subdelay, int n_channels);
+
+/* frames of fixed latency the side's sub-sample stage adds (h, or 0 without one); < 0: error */
+int bfir_engine_delay_latency(const bfir_engine *e, int side);
+
 /* tuning: blocks per launch; 0 (the default) = automatic: the work of 4096 blocks of the 8-channel, 4096-sample
  * headline shape (4096 ... 32768 blocks), less when the delay line of that many blocks would pass 4 GiB, at most 512
  * on the host-pointer path; takes effect on the next run */
