@@ -1,10 +1,11 @@
 """The transform-size matrix: one row per (kernel family, realsize, L) the engine supports, the channel count, frame
 formats and switches that make the engine take that family, and what its creation log line must then report.
 
-NUP_CELLS, FADE_CELLS, MATRIX_CELLS, LEVELS_CELLS and LFADE_CELLS are the same for the engine kinds built on top of the
-plain diagonal engine: two-level engines (csrc/nup.hip and the tail level in engine.hip), crossfaded coefficient changes
-(csrc/fade.hip), matrix engines (csrc/matrix.hip), multi-level engines (csrc/levels.hip) and crossfaded coefficient changes
-on two-level and multi-level engines (csrc/lfade.hip).
+NUP_CELLS, FADE_CELLS, MATRIX_CELLS, LEVELS_CELLS, LFADE_CELLS, MLEVELS_CELLS and MFADE_CELLS are the same for the engine
+kinds built on top of the plain diagonal engine: two-level engines (csrc/nup.hip and the tail level in engine.hip),
+crossfaded coefficient changes (csrc/fade.hip), matrix engines (csrc/matrix.hip), multi-level engines (csrc/levels.hip),
+crossfaded coefficient changes on two-level and multi-level engines (csrc/lfade.hip), multi-level matrix engines
+(csrc/mlevels.hip) and their crossfades (csrc/mfade.hip).
 
 Plain data, importable without a GPU: tests/test_size_matrix.py checks on the CPU that the lists cover exactly the set
 the sources in csrc/ support; tests/test_size_matrix_gpu.py and tests/test_size_matrix_kinds_gpu.py run every row on
@@ -20,8 +21,9 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 FLOAT_LE, FLOAT64_LE = 8, 10
 
 # every switch that can move an engine to another family: a cell sets each of them, to a value or to None (unset)
+# (BFIR_MFADE_DUO, read at creation: unset is the default, k_mac_duo; 0 runs k_mac_matrix twice)
 PATH_SWITCHES = ("BFIR_PAIR", "BFIR_PAIR_TIME", "BFIR_DIRECT", "BFIR_RUN64", "BFIR_F64_PAIRS", "BFIR_MAC_SYS",
-                 "BFIR_MAC_BATCHED")
+                 "BFIR_MAC_BATCHED", "BFIR_MFADE_DUO")
 
 B = 3                     # partitions; taps = B*L - 7 (ragged last partition)
 RAGGED = 7
@@ -64,6 +66,7 @@ def source_limits():
         "levels_log2n": _macro_list(_read("levels.hip"), "BFIR_FOR_LEVELS_LOG2N"),
         "lfade_log2n": _macro_list(_read("lfade.hip"), "BFIR_FOR_LFADE_LOG2N"),
         "level_rings": _const(kh, "BFIR_LEVEL_RINGS"),
+        "lone_log2n": _macro_list(_read("mlevels.hip"), "BFIR_FOR_LONE_LOG2N"),
         "max_levels": _max_levels(),
     }
 
@@ -77,10 +80,10 @@ def _max_levels():
 
 
 def reachable_instances(lim, log2n, nr_min):
-    """{(LOG2N, NR)} of k_inv_levels (nr_min = 2: one ring of a non-fading chunk is k_inv_nup's) or k_inv_lfade (nr_min = 1)
-    that an engine can launch, and the instances the sources build.  NR counts the contributing tails; bfir_engine_create_levels
-    wants ratios >= 2 and every L_k supported, so NR tails on a head of L = 2^(LOG2N - 1) need 2^(LOG2N - 1) 2^NR <= the
-    largest supported fp32 length."""
+    """{(LOG2N, NR)} of k_inv_levels (nr_min = 2: one ring of a non-fading chunk is k_inv_nup's), k_inv_lfade (nr_min = 1) or
+    k_inv_lone (nr_min = 0: the chunks before any level contributes) that an engine can launch, and the instances the
+    sources build.  NR counts the contributing tails; bfir_engine_create_levels wants ratios >= 2 and every L_k supported, so
+    NR tails on a head of L = 2^(LOG2N - 1) need 2^(LOG2N - 1) 2^NR <= the largest supported fp32 length."""
     top = max(supported_lengths(lim, 4))
     built = {(lg, nr) for lg in log2n for nr in range(nr_min, lim["level_rings"] + 1)}
     return {(lg, nr) for lg, nr in built if (1 << (lg - 1)) << nr <= top}, built
@@ -97,6 +100,19 @@ def fade_is_fused(lim, s, L, out_fmt):
     """fade_fused_rule() restated: fp32 spectra kept as (re, im) pairs (2L >= 512: choose_path), FLOAT_LE output frames
     and a pair plan of 2L points (pair_supported)."""
     return s == 4 and 2 * L >= 512 and out_fmt == FLOAT_LE and L in [1 << (n - 1) for n in lim["pair_log2n"]]
+
+
+def back_fused_rule():
+    """The right-hand side of `e->back_fused = ...;` in engine.hip: which split engines take the fused back ends."""
+    m = re.search(r"e->back_fused\s*=\s*([^;]+);", _read("engine.hip"))
+    assert m
+    return " ".join(m.group(1).split())
+
+
+def matrix_back_is_fused(lim, s, L, out_fmt):
+    """back_fused_rule() restated for a matrix head: by its output side alone, the conditions of fade_is_fused -- whatever
+    the input count, the input format or the parity of the output count."""
+    return fade_is_fused(lim, s, L, out_fmt)
 
 
 def supported_lengths(lim, s):
@@ -148,6 +164,14 @@ def supported_set(lim):
         "lfade_fused": (4, [L for L in [1 << (n - 1) for n in lim["lfade_log2n"]] if 2 * L in f32]),
         "lfade_general32": (4, [L for L in f32 if 2 * L in f32]),
         "lfade_general64": (8, [L for L in f64 if 2 * L in f64]),
+        # multi-level matrix engines and their fades, from two levels up: the fused back end where the head has a pair plan
+        # (k_inv_nup / k_inv_levels / k_inv_lone, k_inv_lfade), the general one at every head that takes a tail
+        "mlevels_fused": (4, [L for L in pair if 2 * L in f32]),
+        "mlevels_general32": (4, [L for L in f32 if 2 * L in f32]),
+        "mlevels_general64": (8, [L for L in f64 if 2 * L in f64]),
+        "mfade_fused": (4, [L for L in pair if 2 * L in f32]),
+        "mfade_general32": (4, [L for L in f32 if 2 * L in f32]),
+        "mfade_general64": (8, [L for L in f64 if 2 * L in f64]),
     }
     return {(f, s, L) for f, (s, Ls) in fams.items() for L in Ls}
 
@@ -325,27 +349,28 @@ def level_geometry(L, blocks, ratios):
     return Ls, D
 
 
-def _levels_cell(family, s, L, C, fin, fout, n, fade=None):
+def _levels_cell(family, s, L, C, fin, fout, n, fade=None, K=FADE_K, pre="", post="", **extra):
     """n levels; taps end RAGGED short of the capacity (the last level's last partition is ragged).  Without a fade,
     nb = D_last / L + r_last (blocks_last + 2) + 3 blocks: the deepest delay line and its ring both wrap.  With one (fade,
     added to lg + C in the gain rule of FADE_CELLS) it starts at t0 = D_last / L + r_last + 1, where every ring contributes
     (NR of k_inv_lfade = n - 1) and which is odd, so inside a block of every level: every level catches up; K = FADE_K blocks
-    and 2 r_last + 1 more."""
+    and 2 r_last + 1 more.  C counts both sides of a matrix cell in the gain rule (extra: n_in, n_out; the cell's C is n_in)."""
     blocks, ratios = LEVEL_BLOCKS[n], (1,) + (2,) * (n - 1)
     Ls, D = level_geometry(L, blocks, ratios)
     r_last = Ls[-1] // L
     more = {"blocks": blocks, "ratios": ratios, "taps": D[-1] - RAGGED}
-    tag = "-%dlv" % n
+    tag = pre + "-%dlv" % n
     if fade is None:
         more["nb"] = D[-2] // L + r_last * (blocks[-1] + 2) + 3
-        more["back"] = "fused" if family == "levels_fused" else "general"
+        more["back"] = "fused" if family.endswith("levels_fused") else "general"
     else:
         lg = L.bit_length() - 1
         more["new_gain"] = 0.125 if (lg + C + fade) % 2 == 0 else 8.0
         more["t0"] = D[-2] // L + r_last + 1
-        more["nb"] = more["t0"] + FADE_K + 2 * r_last + 1
+        more["nb"] = more["t0"] + K + 2 * r_last + 1
         tag += "-g%g" % more["new_gain"]
-    return _kind_cell(family, s, L, C, fin, fout, tag, **more)
+    more.update(extra)
+    return _kind_cell(family, s, L, extra.get("n_in", C), fin, fout, tag + post, **more)
 
 
 def _build_levels_cells():
@@ -395,18 +420,158 @@ def _build_lfade_cells():
     return cells
 
 
+# Multi-level matrix engines (csrc/mlevels.hip and the matrix levels in engine.hip) and their crossfades (csrc/mfade.hip,
+# csrc/lfade.hip): the geometry of _levels_cell, n_in inputs to n_out outputs, every (output, input) pair a filter of its
+# own length.
+MFADE_WIDE_K = 11         # the whole fade in one launch: time tiles 8 + 3 (fp32), 4 + 4 + 3 (fp64), as MATRIX_CALLS[1]
+
+
+def matrix_level_lengths(L, blocks, ratios, n_in, n_out, null, new=False):
+    """[o][i] tap counts (None at the NULL pair).  Filter j, row-major over the pairs that are not NULL, belongs to level
+    order[j % n], order = [n - 1, 0, 1, .., n - 2], and ends RAGGED + j // n taps short of the end of that level's last
+    partition: the first filter has the D[-1] - RAGGED taps of the diagonal cells, and with n or more filters one ends in
+    every level.  new: the second set of a fade -- the same table with the input columns mirrored (the outputs, where there is
+    one input), the NULL pair with them, and every filter that short of the end of its level's FIRST partition.  Where the
+    mirror leaves the NULL pair where it was (the middle column of three) or some level's partition counts as they were (a
+    level of one partition under a table that is its own mirror image), the outputs are mirrored as well."""
+    n = len(blocks)
+    Ls, D = level_geometry(L, blocks, ratios)
+    order = [n - 1] + list(range(n - 1))
+    table, j = [], 0
+    for o in range(n_out):
+        row = []
+        for i in range(n_in):
+            if (o, i) == null:
+                row.append(None)
+                continue
+            row.append((order[j % n], j // n))
+            j += 1
+        table.append(row)
+    lens = lambda tab, first: [[None if e is None else (D[e[0]] + Ls[e[0]] if first else D[e[0] + 1]) - RAGGED - e[1] for e in r]
+                               for r in tab]
+    old = lens(table, False)
+    if not new:
+        return old
+    table = [r[::-1] for r in table] if n_in > 1 else table[::-1]
+    if n_in > 1 and not sets_differ(L, blocks, ratios, old, lens(table, True)):
+        table = table[::-1]
+    return lens(table, True)
+
+
+def level_counts(L, blocks, ratios, lens):
+    """[level][o][i]: partitions of h_{o,i} on the level, as bfir_engine_set_coeff_matrix_levels splits the filters."""
+    Ls, D = level_geometry(L, blocks, ratios)
+    return [[[0 if n is None else -(-max(0, min(n - D[k], blocks[k] * Ls[k])) // Ls[k]) for n in r] for r in lens]
+            for k in range(len(Ls))]
+
+
+def sets_differ(L, blocks, ratios, old, new):
+    """The two sets of a fade have their NULL pair (if any) in different places and different partition counts at every level."""
+    where = lambda lens: [(o, i) for o, r in enumerate(lens) for i, n in enumerate(r) if n is None]
+    co, cn = level_counts(L, blocks, ratios, old), level_counts(L, blocks, ratios, new)
+    return (not where(old) or where(old) != where(new)) and all(a != b for a, b in zip(co, cn))
+
+
+def _mlevels_cell(family, s, L, n_in, n_out, fin, fout, n, fade=None, K=FADE_K, wide=False):
+    """_levels_cell with a matrix: one NULL pair where there are three pairs or more, by the rule of MATRIX_CELLS and one step
+    on where that is filter 0; lens (and lens_new, the fade's second set) from matrix_level_lengths.  A fade cell's gain rule
+    counts both sides.  wide: K = MFADE_WIDE_K blocks of fade in one call with chunks that long."""
+    lg = L.bit_length() - 1
+    null = None
+    if n_in * n_out >= 3:
+        null = (lg % n_out, lg % n_in)
+        if null == (0, 0):
+            null = (0, 1) if n_in > 1 else (1, 0)
+    extra = {"n_in": n_in, "n_out": n_out, "null": null}
+    if fade is not None:
+        extra.update(chunk=K if wide else 2, wide=wide)
+    cell = _levels_cell(family, s, L, n_in + n_out, fin, fout, n, fade, K, "-to%d" % n_out, "-wide" if wide else "", **extra)
+    cell["lens"] = matrix_level_lengths(L, cell["blocks"], cell["ratios"], n_in, n_out, null)
+    if fade is not None:
+        cell["K"] = K
+        cell["lens_new"] = matrix_level_lengths(L, cell["blocks"], cell["ratios"], n_in, n_out, null, new=True)
+    return cell
+
+
+PAIR_PLANS = (512, 1024, 2048, 4096, 8192)
+
+
+def _build_mlevels_cells():
+    cells = []
+    add = lambda *a: cells.append(_mlevels_cell(*a))
+    # the fused back end: k_inv_pair / k_inv_nup / k_inv_levels on the output pair, frames 3 floats apart, and k_inv_lone<LOG2N, NR>
+    # on the third output -- a run of n levels passes through 0 .. n - 1 contributing rings
+    for n, Ls in ((2, PAIR_PLANS), (3, PAIR_PLANS[:4]), (4, PAIR_PLANS[:3])):
+        for L in Ls:
+            add("mlevels_fused", 4, L, 2, 3, FLOAT_LE, FLOAT_LE, n)
+        add("mlevels_fused", 4, Ls[1], 2, 2, FLOAT_LE, FLOAT_LE, n)    # pair front end, frame stride 0
+        add("mlevels_fused", 4, Ls[1], 1, 2, FLOAT_LE, FLOAT_LE, n)    # direct front end on the fused back end
+        add("mlevels_fused", 4, Ls[1], 2, 1, FLOAT_LE, FLOAT_LE, n)    # the lone kernel alone, NO = 1 in the MAC
+    add("mlevels_fused", 4, 512, 3, 5, FLOAT_LE, FLOAT_LE, 3)          # two output pairs and the lone one, a ragged second MAC tile
+    # the general back end, fp32: below the pair plans ...
+    for L in (16, 32, 64, 128, 256):
+        add("mlevels_general32", 4, L, 2, 3, FLOAT_LE, FLOAT_LE, 3)
+        add("mlevels_general32", 4, L, 3, 2, FLOAT_LE, FLOAT_LE, 3)
+        if L in (16, 256):                            # four levels: the smallest head and the largest below the pair plans
+            add("mlevels_general32", 4, L, 2, 3, FLOAT_LE, FLOAT_LE, 4)
+    for L in PAIR_PLANS:                              # ... and inside them where the output frames are not FLOAT_LE; 8192 x 16384
+        add("mlevels_general32", 4, L, 2, 3, FLOAT_LE, FLOAT64_LE, 2)
+    for L in [1 << lg for lg in range(4, 12)]:        # fp64
+        add("mlevels_general64", 8, L, 2, 3, FLOAT64_LE, FLOAT64_LE, 3)
+        if L in (16, 1024):                           # four levels: the smallest and the largest head there is
+            add("mlevels_general64", 8, L, 2, 3, FLOAT64_LE, FLOAT64_LE, 4)
+        if L in (64, 1024):                           # the plug-in's shape: fp64 arithmetic, float32 stereo frames
+            add("mlevels_general64", 8, L, 2, 2, FLOAT_LE, FLOAT_LE, 3)
+    add("mlevels_general64", 8, 4096, 2, 3, FLOAT64_LE, FLOAT64_LE, 2)  # a tail of 8192, the largest fp64 transform
+    return cells
+
+
+def _build_mfade_cells():
+    cells = []
+    add = lambda *a, **k: cells.append(_mlevels_cell(*a, **k))
+    io = lambda Cn: (2, 3) if Cn == 2 else (3, 2)     # the channel count of an LFADE cell -> (n_in, n_out): 2 -> 3 or 3 -> 2
+    # k_inv_lfade<LOG2N, NR = n - 1> with an odd and an even output count alternating along a row, as lfade_fused alternates C
+    for n, Ls in ((2, PAIR_PLANS), (3, PAIR_PLANS[:4]), (4, PAIR_PLANS[:3])):
+        for i, L in enumerate(Ls):
+            add("mfade_fused", 4, L, *io(2 + (i + n) % 2), FLOAT_LE, FLOAT_LE, n, i // 2)
+    for L in (16, 32, 64, 128, 256):                  # k_lfade_sum<float>: below the pair plans
+        lg = L.bit_length() - 1
+        add("mfade_general32", 4, L, 2, 3, FLOAT_LE, FLOAT_LE, 3, 0)
+        add("mfade_general32", 4, L, 3, 2, FLOAT_LE, FLOAT_LE, 4 if lg % 2 == 0 else 2, 0)
+    for L, n in ((512, 2), (1024, 3), (2048, 4), (4096, 3), (8192, 2)):     # ... and inside them where the output frames are not FLOAT_LE
+        add("mfade_general32", 4, L, 2, 3, FLOAT_LE, FLOAT64_LE, n, 0)
+    for L in [1 << lg for lg in range(4, 12)]:        # k_lfade_sum<double>
+        add("mfade_general64", 8, L, 2, 3, FLOAT64_LE, FLOAT64_LE, 3, 0)
+        if L in (64, 1024):
+            add("mfade_general64", 8, L, 3, 2, FLOAT_LE, FLOAT_LE, 3, 0)
+    add("mfade_general64", 8, 4096, 2, 3, FLOAT64_LE, FLOAT64_LE, 2, 0)     # a tail of 8192, the largest fp64 transform
+    add("mfade_general64", 8, 1024, 3, 2, FLOAT64_LE, FLOAT64_LE, 4, 0)     # four levels, 8192 again
+    # the time-tiled k_mac_duo: one cell per (T, ILV, NO) at the smallest head with that layout, three levels.  The head's one
+    # fading launch has MFADE_WIDE_K blocks; the tails' have one to four (the block a call began inside runs alone), so TT = 1:
+    # with one output, the only NO = 1 launches of the fp32 latency form
+    for s, L, n_out, fmt in ((4, 16, 1, FLOAT_LE), (4, 16, 3, FLOAT_LE), (4, 256, 1, FLOAT_LE), (4, 256, 3, FLOAT_LE),
+                             (8, 16, 3, FLOAT64_LE), (8, 1024, 3, FLOAT64_LE)):
+        add("mfade_general32" if s == 4 else "mfade_general64", s, L, 2, n_out, fmt, fmt, 3, 0, K=MFADE_WIDE_K, wide=True)
+    return cells
+
+
 NUP_CELLS = _build_nup_cells()
 FADE_CELLS = _build_fade_cells()
 MATRIX_CELLS = _build_matrix_cells()
 LEVELS_CELLS = _build_levels_cells()
 LFADE_CELLS = _build_lfade_cells()
-KIND_CELLS = NUP_CELLS + FADE_CELLS + MATRIX_CELLS + LEVELS_CELLS + LFADE_CELLS
+MLEVELS_CELLS = _build_mlevels_cells()
+MFADE_CELLS = _build_mfade_cells()
+KIND_CELLS = NUP_CELLS + FADE_CELLS + MATRIX_CELLS + LEVELS_CELLS + LFADE_CELLS + MLEVELS_CELLS + MFADE_CELLS
 
 # bfir_engine_create_nup must fail: (realsize, L, tail_ratio, error name) -- the tail's partition is past the range
 NUP_REFUSALS = [(4, 16384, 2, "ERR_UNSUPPORTED"), (8, 8192, 2, "ERR_UNSUPPORTED")]
 
 # bfir_engine_create_levels must fail: (realsize, L, levels, error name) -- the first shape past each limit
 LEVELS_REFUSALS = [(4, 8192, 3, "ERR_UNSUPPORTED"), (4, 4096, 4, "ERR_UNSUPPORTED"), (8, 4096, 3, "ERR_UNSUPPORTED")]
+
+# bfir_engine_create_matrix_levels must fail, 2 -> 3: the same three shapes (check_levels_args serves both kinds)
+MLEVELS_REFUSALS = list(LEVELS_REFUSALS)
 
 
 # ---- test data and the float64 reference ------------------------------------------------------------------------
@@ -528,9 +693,11 @@ def fade_data(orc, cell):
 
 def fade_reference(orc, cell, h_old, h_new, x):
     """float64: y_old before block t0, y_old (1 - f m) + y_new f m with f = 1 / (K L - 1), m = (t - t0) L + n over the K
-    blocks of the fade, y_new after it; y_old / y_new the reference convolutions of the whole stream."""
-    L, t0, K = cell["L"], cell["t0"], FADE_K
-    y_old, y_new = reference(orc, x, h_old), reference(orc, x, h_new)
+    blocks of the fade, y_new after it; y_old / y_new the reference convolutions of the whole stream (of a matrix cell, whose
+    sets are rows of filters: matrix_reference_conv)."""
+    L, t0, K = cell["L"], cell["t0"], cell.get("K", FADE_K)
+    conv = matrix_reference_conv if "n_out" in cell else lambda o, rows, xx: reference(o, xx, rows)
+    y_old, y_new = conv(orc, h_old, x), conv(orc, h_new, x)
     y = y_old.copy()
     y[(t0 + K) * L:] = y_new[(t0 + K) * L:]
     fm = (np.arange(K * L) / (K * L - 1.0))[:, None]
@@ -558,3 +725,30 @@ def matrix_reference_conv(orc, rows, x):
             if h is not None:
                 out[:, o] += reference_conv(orc, x64[:, i], np.asarray(h, np.float64))
     return out
+
+
+def _matrix_rows(orc, rng, cell, lens, gain=1.0):
+    """rows[o][i]: a flat_ir filter of lens[o][i] taps times gain in the working precision, None where lens has None."""
+    dt = orc.real_dtype(cell["s"])
+    return [[None if n is None else (flat_ir(rng, 1, n)[0] * gain).astype(dt) for n in row] for row in lens]
+
+
+def mlevels_data(orc, cell):
+    """(rows, x) of a multi-level matrix cell: every pair its own filter of its own length (cell["lens"]), sum |h| = 1."""
+    rng = _rng(cell)
+    return _matrix_rows(orc, rng, cell, cell["lens"]), _noise(orc, rng, cell)
+
+
+def mfade_data(orc, cell):
+    """(rows_old, rows_new, x) of a fade cell of a multi-level matrix engine: the gains of fade_data, the lengths of the two
+    sets from cell["lens"] and cell["lens_new"]."""
+    rng = _rng(cell)
+    g_old, g_new = (1.0, 0.125) if cell["new_gain"] < 1.0 else (0.125, 1.0)
+    rows_old = _matrix_rows(orc, rng, cell, cell["lens"], g_old)
+    rows_new = _matrix_rows(orc, rng, cell, cell["lens_new"], g_new)
+    return rows_old, rows_new, _noise(orc, rng, cell)
+
+
+def partition_counts(cell, lens):
+    """level_counts of a cell's geometry."""
+    return level_counts(cell["L"], cell["blocks"], cell["ratios"], lens)

@@ -1,16 +1,18 @@
 """The size matrix for the engine kinds on top of the plain diagonal engine (tests/size_matrix.py: NUP_CELLS, FADE_CELLS,
-MATRIX_CELLS, LEVELS_CELLS, LFADE_CELLS): two-level engines, crossfaded coefficient changes, matrix engines, multi-level
-engines and crossfaded coefficient changes on split engines at every transform size their kernels have, with
-flat-envelope filters, odd channels at 1/8 and the per-block, per-channel norm, each against a float64 / long-double
-reference computed here from the frames and taps actually sent -- and against the oracle, as the plain sweep does
-(tests/test_size_matrix_gpu.py)."""
+MATRIX_CELLS, LEVELS_CELLS, LFADE_CELLS, MLEVELS_CELLS, MFADE_CELLS): two-level engines, crossfaded coefficient changes,
+matrix engines, multi-level engines, crossfaded coefficient changes on split engines, multi-level matrix engines and their
+crossfades at every transform size their kernels have, with flat-envelope filters, odd channels at 1/8 and the per-block,
+per-channel norm, each against a float64 / long-double reference computed here from the frames and taps actually sent --
+and against the oracle, as the plain sweep does (tests/test_size_matrix_gpu.py).  The wide cells of MFADE_CELLS run their
+whole fade in one time-tiled k_mac_duo launch and a second time with BFIR_MFADE_DUO=0, byte for byte."""
 import numpy as np
 import pytest
 
 import size_matrix as SM
 from conftest import TOL, env_override
-from test_fade import fade_expected
+from test_fade import fade_expected, fade_weights
 from test_matrix import matrix_reference
+from test_mlevels import uniform_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -260,3 +262,144 @@ def test_lfade_size_matrix(orc, bfir, creation_log, cell):
 
     want, _, _ = fade_expected(orc, L, -(-cell["taps"] // L), s, Cn, h_old, h_new, x, t0, K, cell["in_fmt"], cell["out_fmt"])
     _check(cell, y, SM.fade_reference(orc, cell, h_old, h_new, x), want)
+
+
+# ---- multi-level matrix engines --------------------------------------------------------------------------------------
+def _matrix_levels_engine(bfir, creation_log, cell):
+    """The engine of a MLEVELS / MFADE cell, its creation log line checked: the back end, one plain engine per level."""
+    L, blocks, ratios, n_in, n_out = cell["L"], cell["blocks"], cell["ratios"], cell["n_in"], cell["n_out"]
+    Ls, _ = SM.level_geometry(L, blocks, ratios)
+    del creation_log[:]
+    eng = bfir.BrutefirMatrixLevels(L, blocks, ratios, cell["s"], n_in, n_out, cell["in_fmt"], cell["out_fmt"])
+    names = ", ".join("%d x %d" % (Lk, b) for Lk, b in zip(Ls, blocks))
+    back = "fused" if cell["family"].endswith("_fused") else "general"
+    made = [ln for ln in creation_log if " levels, " in ln]
+    assert made == ["bfir engine: matrix %d -> %d, %d levels, %s; back end %s." % (n_in, n_out, len(blocks), names, back)], creation_log
+    assert len(_engine_lines(creation_log)) == len(blocks), creation_log         # one matrix engine per level, no more
+    return eng
+
+
+def _check_matrix_spectra(eng, cell, rows):
+    """Every partition spectrum of every level and pair against grouped_spectrum, the ragged last one of a filter included; a
+    partition a filter does not reach, and every one of the NULL pair, reads as zeros (absent: the MAC skips it by its count)."""
+    s, L = cell["s"], cell["L"]
+    Ls, D = SM.level_geometry(L, cell["blocks"], cell["ratios"])
+    lens = [[None if h is None else h.size for h in row] for row in rows]
+    counts = SM.partition_counts(cell, lens)
+    for level, (Lp, Bp) in enumerate(zip(Ls, cell["blocks"])):
+        for o, row in enumerate(rows):
+            for i, h in enumerate(row):
+                for b in range(Bp):
+                    got = eng.coeff_block(level, o, i, b).astype(np.float64)
+                    if b >= counts[level][o][i]:
+                        assert not got.any(), (level, o, i, b)
+                        continue
+                    want = SM.grouped_spectrum(h[D[level] + b * Lp:D[level] + (b + 1) * Lp], Lp, 1.0)
+                    assert np.abs(got - want).max() <= TOL[s] * np.abs(want).max(), (level, o, i, b)
+
+
+@pytest.mark.parametrize("cell", SM.MLEVELS_CELLS, ids=[c["id"] for c in SM.MLEVELS_CELLS])
+def test_mlevels_size_matrix(orc, bfir, creation_log, cell):
+    s, L, nb = cell["s"], cell["L"], cell["nb"]
+    Ls, _ = SM.level_geometry(L, cell["blocks"], cell["ratios"])
+    rows, x = SM.mlevels_data(orc, cell)
+
+    with env_override(**cell["env"]):
+        eng = _matrix_levels_engine(bfir, creation_log, cell)
+        eng.set_chunk(3)
+        assert eng.set_coeff(rows) == 0
+        _check_matrix_spectra(eng, cell, rows)
+        # a call that ends inside a block of the last level, one block alone (the latency path), then the rest
+        r_last = Ls[-1] // L
+        y = _run_calls(eng, x, L, (0, r_last + 1, r_last + 2, nb))
+        eng.close()
+    assert y.shape == (nb * L, cell["n_out"])
+
+    _check(cell, y, SM.matrix_reference_conv(orc, rows, x), uniform_reference(orc, L, s, rows, x))
+
+
+@pytest.mark.parametrize("s,L,n,err", SM.MLEVELS_REFUSALS)
+def test_mlevels_refuses_size(bfir, s, L, n, err):
+    with pytest.raises(bfir.BfirError) as ei:
+        bfir.BrutefirMatrixLevels(L, SM.LEVEL_BLOCKS[n], (1,) + (2,) * (n - 1), s, 2, 3)
+    assert ei.value.code == getattr(bfir, err)
+    # nothing left behind: the device still makes and runs a three-level 2 -> 3 engine of a supported size
+    dt = np.float32 if s == 4 else np.float64
+    eng = bfir.BrutefirMatrixLevels(1024, SM.LEVEL_BLOCKS[3], (1, 2, 2), s, 2, 3)
+    taps = 4 * 1024 + 10                                                    # ten taps into the last level
+    h = np.ones(taps, dt) / 16384
+    assert eng.set_coeff([[h, h], [h, None], [None, h]]) == 0
+    rc, y = eng.run(np.ones((16 * 1024, 2), dt))
+    assert rc == 0 and y.shape == (16 * 1024, 3) and np.all(np.isfinite(y))
+    for o, paths in enumerate((2, 1, 1)):                                   # all taps under a constant input: their sum, per path
+        assert abs(float(y[-1, o]) - paths * taps / 16384) <= 1e-5, o
+    eng.close()
+
+
+# ---- crossfaded coefficient changes on multi-level matrix engines --------------------------------------------------------
+def _wide_mac_spans(cell):
+    """MAC launches of the ONE call that holds the whole fade of a wide cell (a profile span is a MAC step, k_mac_duo or
+    k_mac_matrix twice): one for the head's K blocks -- every level contributes to all of them, so run_blocks cuts the chunk
+    nowhere but at the fade's end -- and three per tail level: the block the call began inside, alone from the kept frames,
+    the others up to the last old one (lf_j1: both sets) and the ones after (nup_tail_ahead)."""
+    L, t0, K = cell["L"], cell["t0"], cell["K"]
+    Ls, D = SM.level_geometry(L, cell["blocks"], cell["ratios"])
+    spans = 1
+    for Lk, Dk in zip(Ls[1:], D[1:]):
+        r = Lk // L
+        z_next, j_end, j1 = t0 // r, (t0 + K) // r, (t0 + K - 1 - Dk // L) // r
+        assert t0 % r and z_next < j1 < j_end - 1 and max(j1 - z_next, j_end - 1 - j1) <= -(-cell["chunk"] // r)
+        spans += 3
+    return spans
+
+
+def _mfade_run(bfir, creation_log, cell, rows_old, rows_new, x, duo):
+    """The cell's run with BFIR_MFADE_DUO unset or 0: (output, MAC spans and k_stage_out spans of the first fading call)."""
+    L, t0, K = cell["L"], cell["t0"], cell["K"]
+    first = K if cell["wide"] else 2
+    env = dict(cell["env"], BFIR_MFADE_DUO=duo)
+    with env_override(**env):
+        eng = _matrix_levels_engine(bfir, creation_log, cell)
+        eng.set_chunk(cell["chunk"])         # 2: the fade's K = 3 blocks are cut into 2 + 1; a wide cell: all K in one launch
+        assert eng.set_coeff(rows_old) == 0
+        rc, y0 = eng.run(x[:t0 * L])
+        assert rc == 0
+        del creation_log[:]
+        assert eng.fade_to_rows(rows_new, K) == 0 and eng.fade_remaining() == K
+        said = [ln for ln in creation_log if ln.startswith("bfir matrix engine: crossfade over %d blocks" % K)]
+        assert len(said) == 1 and said[0].endswith("runs %s." % ("k_mac_duo" if duo is None else "k_mac_matrix twice")), creation_log
+        # the first fading call on its own, profiled
+        eng.set_profiling(True)
+        rc, y1 = eng.run(x[t0 * L:(t0 + first) * L])
+        assert rc == 0 and eng.fade_remaining() == K - first
+        prof = eng.profile()
+        eng.set_profiling(False)
+        # the rest of the fade (m0 = 2 L), the swap of the sets and the blocks after it in one call
+        rc, y2 = eng.run(x[(t0 + first) * L:])
+        assert rc == 0 and eng.fade_remaining() == 0
+        eng.close()
+    y = np.concatenate([y0, y1, y2])
+    assert y.shape == (cell["nb"] * L, cell["n_out"])
+    return y, prof["k_mac"][1], prof["k_stage_out"][1]
+
+
+@pytest.mark.parametrize("cell", SM.MFADE_CELLS, ids=[c["id"] for c in SM.MFADE_CELLS])
+def test_mfade_size_matrix(orc, bfir, creation_log, cell):
+    s, L, t0, nb, K = cell["s"], cell["L"], cell["t0"], cell["nb"], cell["K"]
+    fused = cell["family"] == "mfade_fused"
+    rows_old, rows_new, x = SM.mfade_data(orc, cell)
+
+    y, macs, staged = _mfade_run(bfir, creation_log, cell, rows_old, rows_new, x, None)
+    # the fused fade stores the frames itself, the general one ends in k_stage_out
+    assert (staged == 0) if fused else (staged > 0), staged
+    if cell["wide"]:
+        print("%s: MAC spans of the fading call %d" % (cell["id"], macs))
+        assert macs == _wide_mac_spans(cell)
+        # k_mac_duo's specification is the bytes of two k_mac_matrix launches, which MATRIX_CELLS check at these time tiles
+        y2, macs2, _ = _mfade_run(bfir, creation_log, cell, rows_old, rows_new, x, 0)
+        assert macs2 == macs
+        assert y.tobytes() == y2.tobytes()
+
+    w = fade_weights(L, nb, t0, K)[:, None]
+    want = uniform_reference(orc, L, s, rows_old, x) * (1.0 - w) + uniform_reference(orc, L, s, rows_new, x) * w
+    _check(cell, y, SM.fade_reference(orc, cell, rows_old, rows_new, x), want)
