@@ -7,6 +7,10 @@ crossfaded coefficient changes (csrc/fade.hip), matrix engines (csrc/matrix.hip)
 crossfaded coefficient changes on two-level and multi-level engines (csrc/lfade.hip), multi-level matrix engines
 (csrc/mlevels.hip) and their crossfades (csrc/mfade.hip).
 
+DELAY_SUB_CELLS, DELAY_MID_CELLS, DELAY_COPY_CELLS and DELAY_KIND_CELLS are the matrix of the per-channel delays
+(csrc/delay.hip): every instance, tile shape and history edge of k_delay_sub and k_delay_copy, on every kind of engine
+(tests/test_delay_matrix.py on the CPU, tests/test_delay_matrix_gpu.py on the device).
+
 Plain data, importable without a GPU: tests/test_size_matrix.py checks on the CPU that the lists cover exactly the set
 the sources in csrc/ support; tests/test_size_matrix_gpu.py and tests/test_size_matrix_kinds_gpu.py run every row on
 the device."""
@@ -752,3 +756,318 @@ def mfade_data(orc, cell):
 def partition_counts(cell, lens):
     """level_counts of a cell's geometry."""
     return level_counts(cell["L"], cell["blocks"], cell["ratios"], lens)
+
+
+# ---- the delay kernels (csrc/delay.hip; run_blocks_delayed in engine.hip) ---------------------------------------------
+# DELAY_SUB_CELLS, DELAY_COPY_CELLS, DELAY_KIND_CELLS and DELAY_MID_CELLS name every instance, tile shape and history edge
+# of k_delay_sub and k_delay_copy; tests/test_delay_matrix.py checks them against the sources on the CPU and
+# tests/test_delay_matrix_gpu.py runs them.
+DELAY_IN, DELAY_OUT = 0, 1
+FMT_NAMES = {1: "S8", 2: "S16_LE", 3: "S16_BE", 4: "S24_LE", 5: "S24_BE", 6: "S32_LE", 7: "S32_BE", 8: "FLOAT_LE",
+             9: "FLOAT_BE", 10: "FLOAT64_LE", 11: "FLOAT64_BE"}
+FMT_BYTES = {1: 1, 2: 2, 3: 2, 4: 3, 5: 3, 6: 4, 7: 4, 8: 4, 9: 4, 10: 8, 11: 8}
+
+
+def delay_limits():
+    """What delay.hip, kernels.h, engine.hip and the public header fix for the delay kernels."""
+    with open(os.path.join(os.path.dirname(os.path.dirname(CSRC)), "include", "bfir_hip.h")) as f:
+        mc = re.search(r"#define\s+BFIR_MAXCHANNELS\s+(\d+)", f.read())
+    init = re.search(r"bfir_engine_delay_init\(.*?\n\}", _read("engine.hip"), re.S)
+    assert mc and init
+    hl = re.search(r"half_filter_length\s*<\s*(\d+)\s*\|\|\s*half_filter_length\s*>\s*(\d+)", init.group(0))
+    assert hl
+    return {"sub_tile": _const(_read("delay.hip"), "kSubTile"), "delay_ch": _const(_read("kernels.h"), "BFIR_DELAY_CH"),
+            "h_min": int(hl.group(1)), "h_max": int(hl.group(2)), "max_channels": int(mc.group(1))}
+
+
+def delay_source_instances():
+    """({(R, F)} of k_delay_sub, {(unit bytes, VEC)} of k_delay_copy) that delay.hip launches: its hipLaunchKernelGGL lines
+    and the unit types launch_delay_copy hands to delay_copy_t."""
+    src = _read("delay.hip")
+    sub = set(re.findall(r"hipLaunchKernelGGL\(\(k_delay_sub<(\w+),\s*(\w+)>\)", src))
+    vecs = {v == "true" for v in re.findall(r"hipLaunchKernelGGL\(\(k_delay_copy<T,\s*(\w+)>\)", src)}
+    body = re.search(r"void launch_delay_copy\(.*?\n\}", src, re.S)
+    assert body
+    units = {int(b) // 8 for b in re.findall(r"delay_copy_t<uint(\d+)_t>", body.group(0))}
+    return sub, {(u, v) for u in units for v in vecs}
+
+
+def _align(addr):
+    """The largest power of two up to 16 that divides addr."""
+    return 16 if addr % 16 == 0 else addr & -addr
+
+
+def delay_copy_instance(sample_bytes, ptr_align, dst_align):
+    """launch_delay_copy restated: (unit bytes, VEC) from the sample size, the alignment every buffer of the launch has
+    (sources, histories and destinations) and the alignment both destinations have."""
+    unit = sample_bytes if sample_bytes in (8, 4, 2) and ptr_align % sample_bytes == 0 else 1
+    return unit, dst_align % 16 == 0
+
+
+def delay_sub_instance(realsize, sample_bytes):
+    """launch_delay_sub restated: (R, F) of the k_delay_sub instance."""
+    name = {4: "float", 8: "double"}
+    return name[realsize], name[sample_bytes]
+
+
+def delay_sub_lds(C, h, realsize, sample_bytes, lim=None):
+    """Bytes of LDS launch_delay_sub asks for: the tile's output frames at the full channel count, then C source spans."""
+    lim = lim or delay_limits()
+    return lim["sub_tile"] * lim["delay_ch"] * sample_bytes + C * (lim["sub_tile"] + 2 * h) * realsize
+
+
+def delay_sub_grid(n_frames, lim=None):
+    lim = lim or delay_limits()
+    return -(-n_frames // lim["sub_tile"])
+
+
+def uneven_calls(nb):
+    """Blocks per call 2, 1, 3, 2, 1, 3, ... summing to nb (tests/test_delay_gpu.py takes its "uneven" pattern from here)."""
+    out, k = [], 0
+    while sum(out) < nb:
+        out.append(min((2, 1, 3)[k % 3], nb - sum(out)))
+        k += 1
+    return out
+
+
+def delay_n_blocks(reach, L):
+    """Blocks that play a history of `reach` frames in and out (_n_blocks of tests/test_delay_gpu.py is this function)."""
+    return 2 * -(-reach // L) + 3
+
+
+def _sub_geometries(s):
+    """name -> (L, C, h, step_count, kaiser_beta, delays, subdelays, max_delay, calls, chunks), the edge of each in the
+    comment; every one with two channels or more has a channel with subdelay 0, the unfiltered shift by d + h."""
+    top = max(supported_lengths(source_limits(), s))
+    b_total = delay_n_blocks(1000 + 256, 16)
+    return {
+        # every piece (16 frames) is shorter than the span (2 h = 256) and the history; a rectangular window
+        "a": (16, 1, 128, 2, 0.0, (0,), (1,), 0, [1] * 20, (None,)),
+        # 640 frames in one launch: three tiles, the last ragged; the largest LDS request; delays longer than most pieces
+        "b": (16, 8, 128, 1000, 9.0, (0, 1000, 17, 999, 1000, 0, 16, 500), (999, -999, 1, -1, 0, -999, 1, 0), 1000,
+              uneven_calls(60) + [40] + uneven_calls(b_total - 100), (None,)),
+        # three taps that all count; 12-byte frames (fp32), an odd number of blocks
+        "c": (64, 3, 1, 2, 0.0, (5, 0, 70), (1, -1, 0), 70, uneven_calls(delay_n_blocks(70 + 2, 64)), (None,)),
+        # a block is exactly one tile; pieces of 3, 3 and 1 blocks
+        "d": (256, 5, 31, 10, 2.0, (0, 255, 256, 300, 1), (3, -7, 0, 9, -1), 300, [7], (1, 3)),
+        # 20 and 12 workgroups: the XCD remap with a remainder
+        "e": (1024, 2, 8, 10, 9.0, (100, 1500), (3, 0), 1500, [5, 3], (None,)),
+        # the largest transform of the precision
+        "f": (top, 1, 4, 10, 9.0, (7,), (-3,), 7, [2], (None,)),
+    }
+
+
+SUB_TYPE_PAIRS = [(4, FLOAT_LE), (4, FLOAT64_LE), (8, FLOAT_LE), (8, FLOAT64_LE)]
+
+
+def _sub_cell(prefix, side, s, fmt, name, geo, **more):
+    L, C, h, steps, beta, delays, subs, max_delay, calls, chunks = geo
+    cell = {"id": "%s-%s-s%d-%s-%s" % (prefix, "in" if side == DELAY_IN else "out", s, FMT_NAMES[fmt], name),
+            "side": side, "s": s, "fmt": fmt, "geo": name, "L": L, "C": C, "h": h, "steps": steps, "beta": beta,
+            "delays": tuple(delays), "subs": tuple(subs), "max_delay": max_delay, "calls": list(calls), "chunks": tuple(chunks),
+            "instance": delay_sub_instance(s, FMT_BYTES[fmt])}
+    cell.update(more)
+    return cell
+
+
+def _build_delay_sub_cells():
+    return [_sub_cell("dsub", side, s, fmt, name, geo) for side in (DELAY_IN, DELAY_OUT) for s, fmt in SUB_TYPE_PAIRS
+            for name, geo in _sub_geometries(s).items()]
+
+
+def delay_sub_chunk(cell, chunk):
+    """The blocks per launch a stage cell runs with: one of cell["chunks"], None standing for the cell's longest call."""
+    return max(cell["calls"]) if chunk is None else chunk
+
+
+def delay_sub_sees_last_tap(taps_fn, cell):
+    """Whether a stage that drops tap 2 h must leave delay_sub_bound on every filtered channel of the cell.  It adds
+    |f[2h]| |u[n - d - 2h]| to the error.  Against the arithmetic term of the bound alone any tap that the working
+    precision resolves shows (asserted, not assumed: the beta 0 and 2.0 cells in both precisions, the fp64 cells at beta
+    9).  Where the frame type is narrower than R the bound also allows u_F |ref|: of N samples of uniform noise (8192 and
+    more in the cells near this limit, e and f) about N / 64 have |u[n - d - 2h]| > 1/2 and |ref| < 1/32, so a tap of u_F / 16 or more leaves the bound there;
+    a smaller one is hidden by the frame's own rounding and nothing read from such frames can be asked to see it."""
+    if cell["s"] == 4:
+        return cell["beta"] in (0.0, 2.0)
+    u_f = 2.0 ** -24 if cell["fmt"] == FLOAT_LE else 0.0
+    last = [abs(float(np.asarray(taps_fn(cell["h"], sd, cell["steps"], cell["beta"], cell["s"]))[-1]))
+            for sd in delay_sub_steps(cell)[0][1] if sd]
+    return min(last) >= u_f / 16
+
+
+def delay_sub_launches(cell, chunk):
+    """Frames of every k_delay_sub launch of the cell: run_blocks_delayed cuts a call into pieces of at most `chunk` blocks
+    (None: delay_sub_chunk(cell, None), the cell's longest call, which the device test sets with set_chunk: every call is
+    one piece whatever the automatic chunk would be)."""
+    chunk = delay_sub_chunk(cell, chunk)
+    out = []
+    for n in cell["calls"]:
+        while n > 0:
+            tc = min(chunk, n)
+            out.append(tc * cell["L"])
+            n -= tc
+    return out
+
+
+def delay_sub_steps(cell):
+    """[(delays, subdelays, blocks, reset before)] of a cell: one setting for all its calls, or the cell's own steps."""
+    return cell.get("steps_list") or [(cell["delays"], cell["subs"], sum(cell["calls"]), False)]
+
+
+def _build_delay_mid_cells():
+    """Geometry c with the setting changed between calls: sub to another sub, sub to none, none to sub, a longer delay that
+    repeats history, reset() in the middle, one more change.  One call per step."""
+    steps = [((5, 0, 70), (1, -1, 0), 3, False), ((5, 0, 70), (-1, 1, 0), 2, False), ((6, 1, 70), (0, 0, 0), 2, False),
+             ((6, 1, 3), (1, 0, -1), 2, False), ((70, 64, 3), (1, 0, -1), 2, False), ((70, 64, 3), (1, 0, -1), 3, True),
+             ((0, 0, 0), (0, 1, 1), 2, False)]
+    cells = []
+    for side in (DELAY_IN, DELAY_OUT):
+        for s, fmt in SUB_TYPE_PAIRS:
+            geo = list(_sub_geometries(s)["c"])
+            geo[8] = [n for _, _, n, _ in steps]
+            cells.append(_sub_cell("dmid", side, s, fmt, "c", geo, steps_list=steps))
+    return cells
+
+
+INT_FMTS = (1, 2, 3, 4, 5, 6, 7)
+COPY_SHAPE = (16, 3, 2, (0, 7, 37))           # L, C, B, delays
+ALIGN_FMTS = (FLOAT_LE, FLOAT64_LE, 2, 4, 1)  # FLOAT_LE, FLOAT64_LE, S16_LE, S24_LE, S8
+DITHER_FMTS = (2, 4, 6)                       # S16_LE, S24_LE, S32_LE
+
+
+def _build_delay_copy_cells():
+    """Whole samples.  kind "format": run() through the engine's own aligned buffers; "dither": a dithered integer output,
+    delayed behind the dither; "align": run_device with the caller's pointer on the delayed side `offset` bytes past a
+    16-byte boundary -- the engine proper works between that side's aligned scratch and the other side's aligned pointer, which
+    chunk_aligned accepts for every format here, so the other side stays undelayed.  `instance` is what launch_delay_copy
+    then picks: an input-side launch stores to the scratch and the history (VEC) and reads the caller's pointer, an
+    output-side launch stores to the caller's pointer."""
+    L, C, B, delays = COPY_SHAPE
+    cells = []
+
+    def add(kind, side, fmt, offset, s=4, **more):
+        sb = FMT_BYTES[fmt]
+        inst = delay_copy_instance(sb, _align(offset), 16 if side == DELAY_IN else _align(offset))
+        cell = {"id": "dcopy-%s-%s-%s%s" % (kind, "in" if side == DELAY_IN else "out", FMT_NAMES[fmt], "+%d" % offset if offset else ""),
+                "kind": kind, "side": side, "s": s, "fmt": fmt, "offset": offset, "L": L, "C": C, "B": B, "delays": delays,
+                "max_delay": max(delays), "calls": uneven_calls(delay_n_blocks(max(delays), L)), "instance": inst}
+        cell.update(more)
+        cells.append(cell)
+    for side in (DELAY_IN, DELAY_OUT):
+        for fmt in sorted(FMT_NAMES):
+            add("format", side, fmt, 0, s=8 if fmt in (10, 11) else 4)
+    for fmt in DITHER_FMTS:
+        add("dither", DELAY_OUT, fmt, 0)
+    for side in (DELAY_IN, DELAY_OUT):
+        for fmt in ALIGN_FMTS:
+            for offset in sorted({FMT_BYTES[fmt], 1}, reverse=True):      # one sample, one byte
+                add("align", side, fmt, offset, s=8 if fmt == FLOAT64_LE else 4)
+    return cells
+
+
+KIND_L = 64
+DELAY_KINDS = {   # kind -> (inputs, outputs); BrutefirMatrix 3 -> 2, BrutefirNup, BrutefirLevels of three levels, BrutefirMatrixLevels 2 -> 3
+    "matrix": (3, 2), "nup": (3, 3), "levels": (3, 3), "mlevels": (2, 3)}
+KIND_SUB = (4, 10, 9.0, (5, 70, 0), (3, 0, -7), 70)      # h, step_count, beta, delays, subdelays (one 0), max_delay
+KIND_FADE = (5, 3, (3, 0, 40), (100, 31, 0), 100)        # t0, fade blocks, delays before / from the second fade block, max_delay
+
+
+def _build_delay_kind_cells():
+    """L = 64, fp32, FLOAT_LE.  Per kind a sub-sample stage on each side, and per kind and for the plain engine a fade that
+    runs while the input side is delayed by whole samples: t0 blocks, the kind's fade call over 3 head blocks, one block, the
+    delays changed by set_delay, the rest."""
+    h, steps, beta, delays, subs, max_delay = KIND_SUB
+    cells = []
+    for kind, (n_in, n_out) in DELAY_KINDS.items():
+        for side in (DELAY_IN, DELAY_OUT):
+            C = n_in if side == DELAY_IN else n_out
+            nb = delay_n_blocks(max_delay + 2 * h, KIND_L) + 8          # long enough for every level to sound
+            geo = (KIND_L, C, h, steps, beta, delays[:C], subs[:C], max_delay, uneven_calls(nb), (None,))
+            cells.append(_sub_cell("dkind-" + kind, side, 4, FLOAT_LE, "sub", geo, kind=kind, n_in=n_in, n_out=n_out))
+    t0, K, d0, d1, max_delay = KIND_FADE
+    for kind, (n_in, n_out) in list(DELAY_KINDS.items()) + [("plain", (2, 2))]:
+        nb = t0 + K + 9
+        cells.append({"id": "dkind-%s-fade" % kind, "kind": kind, "fade": True, "side": DELAY_IN, "s": 4, "fmt": FLOAT_LE,
+                      "L": KIND_L, "C": n_in, "n_in": n_in, "n_out": n_out, "t0": t0, "K": K, "nb": nb,
+                      "delays": d0[:n_in], "delays_after": d1[:n_in], "max_delay": max_delay,
+                      "instance": delay_copy_instance(4, 16, 16)})
+    return cells
+
+
+DELAY_SUB_CELLS = _build_delay_sub_cells()
+DELAY_MID_CELLS = _build_delay_mid_cells()
+DELAY_COPY_CELLS = _build_delay_copy_cells()
+DELAY_KIND_CELLS = _build_delay_kind_cells()
+DELAY_STAGE_CELLS = DELAY_SUB_CELLS + DELAY_MID_CELLS + [c for c in DELAY_KIND_CELLS if not c.get("fade")]
+DELAY_CELLS = DELAY_SUB_CELLS + DELAY_MID_CELLS + DELAY_COPY_CELLS + DELAY_KIND_CELLS
+
+
+# ---- the float64 model of the sub-sample stage and its error bound ----------------------------------------------------
+def frame_dtype(fmt):
+    return np.dtype("<f4") if fmt == FLOAT_LE else np.dtype("<f8")
+
+
+def _shifted(v, d):
+    w = np.zeros_like(v)
+    if d < v.shape[0]:
+        w[d:] = v[:v.shape[0] - d]
+    return w
+
+
+def delay_sub_reference(taps_fn, u, L, s, h, steps, beta, per_block):
+    """The stage on the stream u [frames, C] that starts from silence, with per_block[t] = (delays, subdelays) in force in
+    block t.  (ref, amp, filtered), each [frames, C]: ref_c[n] = sum_k f[k] u_c[n - d_c - k] over the taps
+    f = taps_fn(h, subdelay, steps, beta, s) in their float64 value, summed in long double and rounded once to float64;
+    amp_c[n] = sum_k |f[k]| |u_c[n - d_c - k]|; on a channel without a filter ref is u_c[n - d_c - h] itself, amp 0 and
+    filtered False."""
+    u = np.asarray(u)
+    n, C = u.shape
+    ref, amp, filt = np.zeros((n, C)), np.zeros((n, C)), np.zeros((n, C), bool)
+    for c in range(C):
+        uc = u[:, c].astype(np.longdouble)
+        cache = {}
+        for t in range(n // L):
+            d, sd = per_block[t][0][c], per_block[t][1][c]
+            if (d, sd) not in cache:
+                if sd == 0:
+                    cache[(d, sd)] = (_shifted(uc, d + h).astype(np.float64), np.zeros(n))
+                else:
+                    f = np.asarray(taps_fn(h, sd, steps, beta, s)).astype(np.longdouble)
+                    cache[(d, sd)] = (_shifted(np.convolve(uc, f)[:n], d).astype(np.float64),
+                                      _shifted(np.convolve(np.abs(uc), np.abs(f))[:n], d).astype(np.float64))
+            r, a = cache[(d, sd)]
+            ref[t * L:(t + 1) * L, c], amp[t * L:(t + 1) * L, c], filt[t * L:(t + 1) * L, c] = \
+                r[t * L:(t + 1) * L], a[t * L:(t + 1) * L], sd != 0
+    return ref, amp, filt
+
+
+def delay_sub_bound(s, fmt, h, ref, amp):
+    """|y - ref| <= (n_taps + 2) u_R amp + u_F |ref|: an n_taps-term fma chain in working precision (unit roundoff u_R)
+    whose first term passes n_taps roundings, the rounding of the source to R on load and of the sum on store (+ 2), and the
+    store to a frame type narrower than R (unit roundoff u_F, else 0).  Derived, not measured."""
+    u_r = 2.0 ** -24 if s == 4 else 2.0 ** -53
+    u_f = 2.0 ** -24 if (s == 8 and fmt == FLOAT_LE) else 0.0
+    return (2 * h + 1 + 2) * u_r * amp + u_f * np.abs(ref)
+
+
+def delay_sub_model(taps_fn, cell, u):
+    """(ref, amp, filtered) of a stage cell on the stream u: delay_sub_reference with the cell's setting per block; after a
+    reset() the stream starts from silence again."""
+    L = cell["L"]
+    parts, pos, seg, per_block = [], 0, 0, []
+    for delays, subs, nb, reset in delay_sub_steps(cell):
+        if reset:
+            parts.append((seg, pos, per_block))
+            seg, per_block = pos, []
+        per_block += [(delays, subs)] * nb
+        pos += nb
+    parts.append((seg, pos, per_block))
+    outs = [delay_sub_reference(taps_fn, u[a * L:b * L], L, cell["s"], cell["h"], cell["steps"], cell["beta"], pb)
+            for a, b, pb in parts]
+    return tuple(np.concatenate([o[k] for o in outs]) for k in range(3))
+
+
+def delay_sub_audio(orc, cell):
+    """The frames a stage cell sends: orc.synth_audio in the frame type."""
+    side_c = cell["C"]
+    return orc.synth_audio(_rng(cell), sum(cell["calls"]) * cell["L"], side_c, frame_dtype(cell["fmt"]))

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from conftest import TOL, rel_err
+from size_matrix import delay_n_blocks, uneven_calls   # shared with the delay cells of the size matrix
 
 pytestmark = pytest.mark.gpu
 
@@ -22,8 +23,7 @@ SHAPES = [(4, 16, 3, 3, (0, 1, 37)), (4, 512, 2, 2, (511, 513)), (8, 1024, 2, 1,
 PATTERNS = ("one", "blocks", "uneven")
 
 
-def _n_blocks(max_delay, L):
-    return 2 * -(-max_delay // L) + 3
+_n_blocks = delay_n_blocks   # 2 ceil(max_delay / L) + 3
 
 
 def _calls(pattern, nb):
@@ -31,11 +31,7 @@ def _calls(pattern, nb):
         return [nb]
     if pattern == "blocks":
         return [1] * nb
-    out, k = [], 0
-    while sum(out) < nb:   # 2, 1, 3, 2, 1, 3, ...
-        out.append(min((2, 1, 3)[k % 3], nb - sum(out)))
-        k += 1
-    return out
+    return uneven_calls(nb)   # 2, 1, 3, 2, 1, 3, ...
 
 
 def shift_model(u, L, delays):
