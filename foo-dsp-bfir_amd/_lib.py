@@ -91,6 +91,12 @@ SIGNATURES = {
     "bfir_engine_set_delay": (_ci, [_vp, _ci, _pi, _pi, _ci]),
     "bfir_engine_get_delay": (_ci, [_vp, _ci, _pi, _pi, _ci]),
     "bfir_engine_delay_latency": (_ci, [_vp, _ci]),
+    "bfir_resample_filter": (_ci, [_ci, _ci, _ci, _cd, _cd, _cd, _ci, _ci, _vp, _pi]),
+    "bfir_resampler_create": (_vp, [_ci, _ci, _ci, _cd, _cd, _cd, _ci, _ci, _ci, _pi]),
+    "bfir_resampler_out_frames": (_cl, [_vp, _cl]),
+    "bfir_resampler_run": (_cl, [_vp, _vp, _cl, _vp, _cl]),
+    "bfir_resampler_run_device": (_cl, [_vp, _vp, _cl, _vp, _cl]),
+    "bfir_resampler_destroy": (None, [_vp]),
     "bfir_convolver_create": (_vp, [_ci, _ci, _ci, _pi]),
     "bfir_convolver_destroy": (None, [_vp]),
     "bfir_convolver_cbufsize": (_ci, [_vp]),

@@ -5,6 +5,7 @@ brutefir/brutefir.hpp:15-128 so the parity tests read like the reference's
 callers (foo_dsp_bfir/foo_dsp_bfir.cpp:279-345, brutefir/preprocessor.cpp:287-333).
 Everything is computed by libbfir_hip.so on the GPU."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -74,6 +75,7 @@ class Brutefir:
         self.in_format = dflt if in_format is None else in_format
         self.out_format = dflt if out_format is None else out_format
         self.n_engines, self.device = n_engines, device
+        self.sampling_rate = sampling_rate
         self._lib = _lib.load()
         err = C.c_int(0)
         self._h = self._lib.bfir_engine_create_batch(
@@ -105,7 +107,13 @@ class Brutefir:
     def set_coeff(self, coeffs, n_coeffs=None, length=None, coeff_blocks=None, scale=1.0,
                   engine_index=0):
         """set_coeff(void **coeffs, n_coeffs, length, coeff_blocks, scale)
-        (brutefir/brutefir.cpp:179-228).  Returns 0 or -2."""
+        (brutefir/brutefir.cpp:179-228).  Returns 0 or -2.
+
+        A file name in place of the arrays is the reference's other overload, set_coeff(filename, coeff_blocks, scale)
+        (set_coeff_file below): its second and third positional arguments are coeff_blocks and scale."""
+        if isinstance(coeffs, (str, bytes, os.PathLike)):
+            blocks = coeff_blocks if coeff_blocks is not None else n_coeffs
+            return self.set_coeff_file(coeffs, blocks, scale if length is None else length)
         rd = _real_dtype(self.s)
         arrs = [np.ascontiguousarray(c, dtype=rd) for c in coeffs]
         n_coeffs = len(arrs) if n_coeffs is None else n_coeffs
@@ -114,6 +122,24 @@ class Brutefir:
         ptrs = (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
         return self._lib.bfir_engine_set_coeff_at(self._h, engine_index, ptrs, n_coeffs, length,
                                                   coeff_blocks, float(scale))
+
+    def set_coeff_file(self, filename, coeff_blocks=None, scale=1.0):
+        """set_coeff(const wchar_t *filename, coeff_blocks, scale) (brutefir/brutefir.cpp:89-165): one filter per channel
+        from a sound file with the engine's channel count and sampling rate, at most coeff_blocks * filter_length frames of
+        it.  Returns the number of filters, -1 for an incompatible (or unreadable) file, -2 when loading failed.  A file at
+        another rate goes through buffer.resample_snd_file first."""
+        from . import buffer
+        coeff_blocks = self.B if coeff_blocks is None else int(coeff_blocks)
+        if not buffer.check_snd_file(filename, self.C, self.sampling_rate):
+            return -1
+        got = buffer.load_snd_coeff(filename, self.s, coeff_blocks * self.L)
+        if got is None:
+            return -2
+        coeffs, length = got
+        n = min(len(coeffs), self.C)
+        if Brutefir.set_coeff(self, coeffs[:n], n, length, coeff_blocks, scale) != 0:
+            return -2
+        return n
 
     def set_coeff_fade(self, coeffs, fade_blocks, n_coeffs=None, length=None, coeff_blocks=None, scale=1.0):
         """bfir_engine_set_coeff_fade: load a second filter set and fade to it over the next `fade_blocks` blocks

@@ -5,9 +5,13 @@
 #pragma once
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
+#include <cwchar>
+#include <string>
 
 #include "bfir_types.hpp"
+#include "coeff_hip.hpp"
 
 class brutefir {
 public:
@@ -15,7 +19,7 @@ public:
     // false, run() returns an error), as the reference's does.
     brutefir(int filter_length, int filter_blocks, int realsize, int channels, int in_format,
              int out_format, int sampling_rate, bool apply_dither, int device = 0)
-        : m_channels(channels)
+        : m_channels(channels), m_filter_length(filter_length), m_realsize(realsize), m_rate(sampling_rate)
     {
         int err = 0;
         m_e = bfir_engine_create(filter_length, filter_blocks, realsize, channels, in_format, out_format,
@@ -67,9 +71,34 @@ public:
 
     bool is_initialized() { return m_e && bfir_engine_is_initialized(m_e); }
 
-    // brutefir.cpp:88-165 loads a sound file through libsndfile; file I/O is outside the
-    // convolution path, so coefficients arrive as arrays (the overload below).
-    int set_coeff(const wchar_t *, int, double) { return -1; }
+    // brutefir.cpp:88-165: one filter per channel from a sound file with the engine's channel count and sampling rate, at
+    // most coeff_blocks * filter_length frames of it and at most n_channels filters.  The number of filters; -1 for an
+    // incompatible (or unreadable) file, or an engine built by another constructor than the first; -2 when loading failed.
+    // A file at another rate goes through buffer::resample_snd_file first (foo_dsp_bfir.cpp:181-233).
+    int set_coeff(const char *filename, int coeff_blocks, double scale)
+    {
+        if (!m_e || !filename) return -1;
+        if (!buffer::check_snd_file(filename, m_channels, m_rate)) return -1;
+        int length = 0, n_coeffs = 0;
+        void **coeffs = coeff::load_snd_coeff(filename, &length, m_realsize, coeff_blocks * m_filter_length, &n_coeffs);
+        if (!coeffs) return -2;
+        const int n_files = n_coeffs;
+        if (n_coeffs > m_channels) n_coeffs = m_channels;
+        const int rc = bfir_engine_set_coeff(m_e, (const void *const *)coeffs, n_coeffs, length, coeff_blocks, scale);
+        for (int n = 0; n < n_files; n++) bfir_aligned_free(coeffs[n]);
+        bfir_aligned_free(coeffs);
+        return rc == 0 ? n_coeffs : -2;
+    }
+    // the reference's wide-character signature: the name narrowed as util::wstr2str does (buffer.cpp:244)
+    int set_coeff(const wchar_t *filename, int coeff_blocks, double scale)
+    {
+        if (!filename) return -1;
+        std::string narrow(wcslen(filename) * MB_CUR_MAX + 1, '\0');
+        const size_t n = wcstombs(&narrow[0], filename, narrow.size());
+        if (n == (size_t)-1) return -1;
+        narrow.resize(n);
+        return set_coeff(narrow.c_str(), coeff_blocks, scale);
+    }
 
     // brutefir.cpp:179-228: 0, or -2 when a tap is NaN/Inf.
     int set_coeff(void **coeffs, int n_coeffs, int length, int coeff_blocks, double scale)
@@ -222,6 +251,7 @@ public:
 private:
     bfir_engine *m_e = nullptr;
     int m_channels = 0, m_err = 0;
+    int m_filter_length = 0, m_realsize = 0, m_rate = -1;   // of the first constructor: what the file form of set_coeff needs
     bfir_overflow m_last[BFIR_MAXCHANNELS];
     bfir_log_fn m_log = nullptr;
 };

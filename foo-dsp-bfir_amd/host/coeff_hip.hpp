@@ -1,10 +1,12 @@
 // coeff_hip.hpp -- coeff::preprocess_coeff (brutefir/coeff.cpp:292-354) over the
 // convolver stand-in: cut an impulse response into coeff_blocks partitions of
-// filter_length taps and pre-transform each on the GPU.
+// filter_length taps and pre-transform each on the GPU; and coeff::load_snd_coeff
+// (coeff.cpp:245-277): one buffer of taps per channel of a sound file.
 #pragma once
 #include <cstdint>
 #include <cstring>
 
+#include "buffer_hip.hpp"
 #include "fftw_convolver_hip.hpp"
 
 namespace coeff {
@@ -32,6 +34,22 @@ inline void **preprocess_coeff(fftw_convolver *convolver, void *coeffs, int filt
     }
     bfir_aligned_free(zeros);
     return cbuf;
+}
+
+// coeff.cpp:245-277: the file's channels as separate buffers in realsize precision, at most max_length frames of each
+// (-1: all); *length frames per buffer, *n_coeffs buffers.  The caller frees every buffer and the table with
+// bfir_aligned_free.  NULL where the file cannot be read.
+inline void **load_snd_coeff(const char *filename, int *length, int realsize, int max_length, int *n_coeffs)
+{
+    int n_channels = 0, n_frames = 0;
+    void **coeffs = nullptr;
+    void *buf = buffer::load_from_snd_file(filename, &n_channels, &n_frames, realsize, max_length, false);
+    if (buf) {
+        coeffs = buffer::deinterlace(buf, n_channels, n_frames, realsize);
+        bfir_aligned_free(buf);
+        if (coeffs) { *length = n_frames; *n_coeffs = n_channels; }
+    }
+    return coeffs;
 }
 
 }  // namespace coeff

@@ -561,6 +561,52 @@ const void *bfir_td_coeffs(const bfir_td_conv *tdc);
  * caller's 2 * blocklen reals */
 int bfir_td_convolve(bfir_td_conv *tdc, void *overlap_block);
 
+/* ------------------------------------------------------------------ */
+/* sampling-rate conversion of an impulse response: the arithmetic     */
+/* buffer::resample_snd_file (buffer.cpp:225-330) hands to             */
+/* libsamplerate (src_simple, SRC_SINC_BEST_QUALITY)                   */
+/* ------------------------------------------------------------------ */
+/* libsamplerate's filter tables are not part of the reference tree, so this stage is defined from first principles:
+ * band-limited interpolation on an exact rational grid.  Rates are integers; g = gcd(in_rate, out_rate), p = out_rate / g,
+ * q = in_rate / g.  Output frame m sits at input time m q / p = n0 + phase / p with n0 = (m q) div p and phase = (m q) mod p
+ * in 64-bit integers: exactly p phases, no table interpolation, no accumulated time error.
+ *   rho = min(1, p / q) cutoff,  W = zero_crossings / rho,  Wc = ceil(W),  K = 2 Wc taps per phase
+ *   tap j of a phase meets input frame n0 - Wc + 1 + j; with u = phase / p + Wc - 1 - j it is
+ *   gain rho sinc(pi rho u) I0(kaiser_beta sqrt(1 - (u / W)^2)) / I0(kaiser_beta) for |u| < W, else 0
+ *   y_c[m] = sum over j = 0 .. K - 1 of T[phase(m)][j] x_c[n0(m) - Wc + 1 + j], x_c = 0 outside [0, n_in)
+ *   n_out = ceil(n_in p / q)
+ * The window is applied once (firwindow_kaiser's twice-applied weight belongs to the delay filters only).  Taps are
+ * evaluated on the host in long double and rounded once to realsize precision; the sum runs in that precision with j
+ * ascending and one fused multiply-add per tap, samples rounded once on store (the convention of the sub-sample delay
+ * stage).  Equal rates copy the bytes, NaNs included, whatever the other parameters.
+ * zero_crossings 1 .. 128, kaiser_beta >= 0, cutoff in [0.5, 1], gain finite, rates >= 1, realsize 4 or 8: anything else is
+ * BFIR_ERR_ARG.  K > 4096 or p K > 2^22 table entries: BFIR_ERR_UNSUPPORTED (44100 -> 96000 has p = 320; the standard audio
+ * rates stay far below both). */
+
+/* buffer.cpp:225-330 (the filter src_simple would apply): the K taps of phase 0 .. p - 1 in realsize precision (float or
+ * double at `taps`), and K in *n_taps.  Pure host arithmetic, no device.  taps == NULL returns only K (then n_taps must
+ * not be NULL).  A phase outside 0 .. p - 1: BFIR_ERR_ARG. */
+int bfir_resample_filter(int in_rate, int out_rate, int zero_crossings, double kaiser_beta, double cutoff, double gain,
+                         int realsize, int phase, void *taps, int *n_taps);
+
+typedef struct bfir_resampler bfir_resampler;
+/* buffer.cpp:225-330 (src_simple's converter state): the phase table, [K][p] in realsize precision, resident on `device`,
+ * for interleaved frames of `channels` (1 .. BFIR_MAXCHANNELS) float (realsize 4) or double (realsize 8) samples.
+ * Arguments are checked before the device: BFIR_ERR_NO_DEVICE only for valid ones, and never a CPU stand-in. */
+bfir_resampler *bfir_resampler_create(int in_rate, int out_rate, int zero_crossings, double kaiser_beta, double cutoff, double gain,
+                                      int realsize, int channels, int device, int *err);
+/* buffer.cpp:292-298: the frames n_in input frames give, ceil(n_in p / q) -- all of them, where the reference caps the
+ * output at the source's frame count.  Negative: BFIR_ERR_ARG. */
+int64_t bfir_resampler_out_frames(const bfir_resampler *r, int64_t n_in);
+/* buffer.cpp:295-302 (src_simple): n_in interleaved frames at `in` to min(max_out, n_out) frames at `out`, both host
+ * buffers; returns the count written or a BFIR_ERR_* code.  Waits for the result. */
+int64_t bfir_resampler_run(bfir_resampler *r, const void *in, int64_t n_in, void *out, int64_t max_out);
+/* buffer.cpp:295-302: the same on device pointers (aligned to the sample; 16-byte alignment lets whole 16-byte stores
+ * through).  Queued on the device's null stream, not waited for. */
+int64_t bfir_resampler_run_device(bfir_resampler *r, const void *d_in, int64_t n_in, void *d_out, int64_t max_out);
+/* buffer.cpp:316-318: waits for queued work and releases the table and the staging buffers */
+void bfir_resampler_destroy(bfir_resampler *r);
+
 /* Page-locked host memory for frame buffers handed to bfir_engine_run: the copy engines read and write it directly, so the
  * staging memcpy through the engine's own pinned buffers is skipped (the reference's callers allocate their frame buffers
  * with _aligned_realloc, foo_dsp_bfir.cpp:291-293; any hipHostMalloc / hipHostRegister'ed buffer is recognised the same way).
