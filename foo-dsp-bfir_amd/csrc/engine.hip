@@ -237,6 +237,9 @@ struct bfir_engine {
     // Every level of a multi-level matrix engine: a launch that needs both sets of a fade runs k_mac_duo (mfade.hip) instead
     // of k_mac_matrix twice.  BFIR_MFADE_DUO=0|1, read at creation (choose_path)
     bool mfade_duo = true;
+    // The channel-pair inverse with 16-byte frame stores (k_inv_quad_ps, quad.hip; InvPairArgs.quad): by default for launches
+    // that fill the GPU.  BFIR_INV_QUAD=0|1 forbids it / takes it wherever it applies, read at creation (choose_path)
+    int inv_quad = -1;
     // profiling
     bool profiling = false;
     struct Span { int k; hipEvent_t a, b; };
@@ -417,6 +420,7 @@ static void choose_path(bfir_engine *e)
     // both sets of a fading multi-level matrix engine in one MAC launch (k_mac_duo), the default: lower than two launches of
     // k_mac_matrix in every paired run ("Crossfades on multi-level matrix engines"); BFIR_MFADE_DUO=0 keeps the two
     if (const char *mv = getenv("BFIR_MFADE_DUO")) e->mfade_duo = atoi(mv) != 0;
+    if (const char *qv = getenv("BFIR_INV_QUAD")) e->inv_quad = atoi(qv) != 0;
     if (const char *pm = getenv("BFIR_PIPE")) { e->pipe3 = atoi(pm) >= 3; e->serial = atoi(pm) == 1; }
     // fp64 engines: one stream.  Their kernels are bound by issue and latency, not by memory, each fills the GPU by itself, and
     // three of them side by side only get into each other's way: the plug-in's shape 42.8 -> 45.9 Gsamples/s, 8 channels 42.5 ->
@@ -1489,7 +1493,7 @@ static void queue_inv(bfir_engine *e, Path p, const Chunk &c, hipStream_t st)
         a.C = e->Co; a.n_eng = e->n_eng; a.n_t = c.tc;
         a.scale = (float)e->out_scale; a.max = (float)e->of_max;
         a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
-        a.tp = e->pair_tp;
+        a.tp = e->pair_tp; a.quad = e->inv_quad;
         if (e->matrix && (e->Co & 1)) {
             // the head of a multi-level matrix engine with an odd output count, in a chunk to which no level contributes: the
             // pairs below it through the pair kernel, frames Co floats apart, then the last output alone (k_inv_lone, no ring)

@@ -245,8 +245,12 @@ struct InvPairArgs {
     long of_shard_stride = 0;
     int tp = 0;                                          // pairs in time, as in FwdPairArgs
     int frame_stride = 0;                                // channel pairs only: floats between output frames; 0 = C (wider: an odd matrix output beside the pairs)
+    int quad = -1;                                       // k_inv_quad_ps where it applies: 0 never, 1 always, -1 for launches that fill the GPU
 };
 void launch_inv_pair(const FftPlan &plan, const InvPairArgs &a, hipStream_t s);
+// quad.hip: channel pairs, C % 4 == 0, frames C floats apart and 16-byte aligned -- two pairs in turn per workgroup and
+// 16-byte frame stores, the same bits as the pair kernel.  false: not taken (launch_inv_pair goes on with the pair kernel).
+bool launch_inv_quad(const FftPlan &plan, const InvPairArgs &a, hipStream_t s);
 
 // fade.hip: the back end of a crossfaded coefficient change (bfir_engine_set_coeff_fade; the reference's blend is
 // fftw_convolver::convolver_crossfade_inplace, brutefir/fftw_convolver.cpp:275-321).  The MAC has run twice over the same

@@ -15,7 +15,10 @@ stores issued after the prefetch.  That is only right while, in the code hipcc a
 hipcc cross-compiles without a GPU, so this runs in the CPU test suite (tests/test_isa_audit.py) and fails the build
 when a compiler or flag change breaks an assumption.  BFIR_PAIR=0 (the planar staging kernels) is the fallback at run time.
 
-    python scripts/audit_ps_isa.py [pair.s]      (without an argument: compiles csrc/pair.hip to assembly first)
+k_inv_quad_ps (quad.hip) has two prefetch statements and two counted waits per block: audit_quad() checks 1 - 3 for each
+window (tests/test_quad_isa.py); audit() and parse() see the pair and time-pair kernels only.
+
+    python scripts/audit_ps_isa.py [pair.s]      (without an argument: compiles csrc/pair.hip and csrc/quad.hip to assembly first)
 """
 import os
 import re
@@ -28,11 +31,11 @@ VMEM = re.compile(r"^(buffer|global|flat|scratch)_(load|store|atomic)")
 REG = re.compile(r"\bv(\d+)\b|\bv\[(\d+):(\d+)\]")
 
 
-def compile_to_asm(out_path):
+def compile_to_asm(out_path, source="pair.hip"):
     sys.path.insert(0, ROOT)
     from importlib import import_module
     b = import_module("foo_dsp_bfir_amd._build")
-    src = os.path.join(b.CSRC, "pair.hip")
+    src = os.path.join(b.CSRC, source)
     cmd = ["hipcc"] + b.FLAGS + ["-S", "--cuda-device-only", "-o", out_path, src]
     subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL)
     return out_path
@@ -144,11 +147,11 @@ def audit_kernel(k, meta):
     return errs
 
 
-def parse(asm_path):
+def parse(asm_path, family="pair|tp"):
     text = open(asm_path).read().splitlines()
     kernels, cur, name = {}, None, None
     for ln in text:
-        m = re.match(r"^(_ZN4bfir\S*k_(?:fwd|inv)_(?:pair|tp)_psILi\d+E\S*):", ln)
+        m = re.match(r"^(_ZN4bfir\S*k_(?:fwd|inv)_(?:%s)_psILi\d+E\S*):" % family, ln)
         if m:
             name, cur = m.group(1), []
             continue
@@ -179,12 +182,109 @@ def audit(asm_path):
     return report
 
 
+def audit_quad_kernel(k, meta):
+    """The quad kernels (quad.hip) alternate two prefetch statements and two in-loop waits, one per channel pair, before the
+    closing vmcnt(0).  Same properties as audit_kernel, per window: on every path from a prefetch statement to the first
+    asm wait behind it the vector-memory operations are all stores and as many as that wait's count (the closing wait
+    takes any number: it waits for all), and nothing on the way touches that statement's destination registers."""
+    errs = []
+    for key in (".vgpr_spill_count", ".sgpr_spill_count", ".private_segment_fixed_size"):
+        if meta.get(key, None) != 0:
+            errs.append("%s = %r (must be 0)" % (key, meta.get(key)))
+    pre = [i for i, (t, a) in enumerate(k.ins) if a and t.startswith("buffer_load")]
+    wait_at = {i: int(re.search(r"vmcnt\((\d+)\)", t).group(1)) for i, (t, a) in enumerate(k.ins)
+               if a and t.startswith("s_waitcnt vmcnt")}
+    stmts = []                                               # one statement = consecutive asm loads
+    for i in pre:
+        if stmts and i == stmts[-1][-1] + 1:
+            stmts[-1].append(i)
+        else:
+            stmts.append([i])
+    if len(stmts) != 2 or any(len(s) != 8 for s in stmts):
+        return errs + ["expected TWO prefetch statements of 8 loads, found asm loads at %s" % pre]
+
+    def reaches_prefetch(w):                                 # a wait inside the loop: the prefetch comes round again
+        seen, stack = set(), list(k.succ(w))
+        while stack:
+            i = stack.pop()
+            if i in seen:
+                continue
+            seen.add(i)
+            if i in pre:
+                return True
+            stack.extend(k.succ(i))
+        return False
+
+    closing = [w for w in wait_at if not reaches_prefetch(w)]
+    inloop = [w for w in wait_at if w not in closing]
+    if len(inloop) != 2 or len(closing) != 1 or wait_at[closing[0]] != 0:
+        return errs + ["expected two in-loop asm waits and one closing vmcnt(0), found %s" % sorted(wait_at.items())]
+    reached = {}                                             # wait -> statements whose window ends there
+    for n, stmt in enumerate(stmts):
+        dests = set()
+        for i in stmt:
+            dests |= vregs(k.ins[i][0].split(",")[0])
+        seen, stack, ends = set(), [(stmt[-1] + 1, 0, 0)], {}
+        while stack:
+            i, n_vmem, n_store = stack.pop()
+            if (i, n_vmem) in seen or n_vmem > 64:
+                continue
+            seen.add((i, n_vmem))
+            t, in_asm = k.ins[i]
+            if i in wait_at:
+                ends.setdefault(i, set()).add((n_vmem, n_store))
+                continue
+            if in_asm and t.startswith("buffer_load"):
+                errs.append("a path from prefetch %d reaches a prefetch without passing a wait (instruction %d)" % (n, i))
+                continue
+            if not in_asm and not t.startswith("s_"):
+                hit = vregs(t) & dests
+                if hit:
+                    errs.append("prefetch %d: destination v%s touched before its wait: `%s`" % (n, sorted(hit), t))
+            if VMEM.match(t):
+                n_vmem += 1
+                n_store += 1 if "_store" in t else 0
+            nxt = k.succ(i)
+            if not nxt:
+                errs.append("a path from prefetch %d ends the program without a wait (`%s`)" % (n, t))
+            for j in nxt:
+                stack.append((j, n_vmem, n_store))
+        if not any(w in inloop for w in ends):
+            errs.append("no path from prefetch %d reaches an in-loop wait" % n)
+        for w, counts in ends.items():
+            reached.setdefault(w, set()).add(n)
+            for n_vmem, n_store in counts:
+                if n_store != n_vmem or (w in inloop and n_vmem != wait_at[w]):
+                    errs.append("path from prefetch %d to `s_waitcnt vmcnt(%d)` carries %d vector-memory ops, %d of them stores"
+                                % (n, wait_at[w], n_vmem, n_store))
+    for w in inloop:
+        if len(reached.get(w, ())) != 1:
+            errs.append("the in-loop wait vmcnt(%d) ends the windows of prefetches %s (must be exactly one)"
+                        % (wait_at[w], sorted(reached.get(w, ()))))
+    if closing[0] not in reached:
+        errs.append("no path from a prefetch reaches the closing vmcnt(0) wait")
+    return errs
+
+
+def audit_quad(asm_path=None):
+    """{"k_inv_quad_ps<13>": [errors], ...} for the quad kernels; without a listing, compiles csrc/quad.hip first."""
+    if asm_path is None:
+        asm_path = compile_to_asm(os.path.join(tempfile.mkdtemp(prefix="bfir_isa_"), "quad.s"), "quad.hip")
+    kernels, meta = parse(asm_path, "quad")
+    report = {}
+    for name, k in sorted(kernels.items()):
+        short = re.search(r"k_(fwd|inv)_quad_psILi(\d+)E", name)
+        report["k_%s_quad_ps<%s>" % short.groups()] = audit_quad_kernel(k, meta.get(name, {}))
+    return report
+
+
 def main():
     if len(sys.argv) > 1:
         path = sys.argv[1]
     else:
         path = compile_to_asm(os.path.join(tempfile.mkdtemp(prefix="bfir_isa_"), "pair.s"))
     rep = audit(path)
+    rep.update(audit_quad(path if len(sys.argv) > 1 else None))
     bad = 0
     for k, errs in rep.items():
         print("%-24s %s" % (k, "ok" if not errs else "FAIL"))
