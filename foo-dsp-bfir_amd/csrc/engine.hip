@@ -1481,6 +1481,47 @@ static void queue_fwd(bfir_engine *e, Path p, const Chunk &c, hipStream_t sf)
     if (p != Path::Staging) { e->hist_raw[0] = e->tails[c.par][0]; e->hist_raw[1] = e->tails[c.par][1]; }
 }
 
+// What the one-transform fused back ends of chunk c take for their overflow statistics and NaN guard.
+static InvStats inv_stats(const bfir_engine *e, const Chunk &c)
+{
+    return InvStats{(float)e->of_max, e->d_of, e->GCo, e->d_bad, c.block_base, e->bad_host_cur};
+}
+
+// The rings of the tails in nup_mask for the head chunk that starts at blockcounter, in level order; z_new: beside each its
+// second ring during a fade.  Returns their number; the entries past it repeat the first (kernel arguments nothing reads).
+static int chunk_rings(const bfir_engine *e, LevelRing (&ring)[BFIR_LEVEL_RINGS], const void **z_new = nullptr)
+{
+    int nr = 0;
+    for (int i = 0; i < e->n_tail; i++) {
+        if (!(e->nup_mask >> i & 1)) continue;
+        const bfir_engine *t = e->tail[i];
+        // a level outside the fade (neither set reaches it, but output queued before it stopped still plays) adds the same to both sums
+        if (z_new) z_new[nr] = t->lf_mode ? t->zring2 : t->zring;
+        LevelRing &g = ring[nr++];
+        g.z = t->zring; g.zlen = g.z_ch_stride = (long)t->zblocks * t->L;
+        g.m0 = ((long long)e->blockcounter - e->lv_D[i]) * e->L; g.m_min = t->z_from * (long long)t->L;
+        g.m0r = (long)(((g.m0 % g.zlen) + g.zlen) % g.zlen);
+    }
+    if (!nr) ring[0] = LevelRing{nullptr, 0, 0, 0, 0, 0};
+    for (int k = std::max(nr, 1); k < BFIR_LEVEL_RINGS; k++) { ring[k] = ring[0]; if (z_new) z_new[k] = z_new[0]; }
+    return nr;
+}
+
+// The last output of a matrix engine with an odd output count, beside the pairs below it whose frames are Co floats apart:
+// alone through k_inv_lone, with the nr rings (none: a chunk to which no level contributes).
+static void queue_inv_lone(bfir_engine *e, const Chunk &c, const LevelRing (&ring)[BFIR_LEVEL_RINGS], int nr, hipStream_t st)
+{
+    LoneInvArgs a;
+    a.ch = e->Co & ~1;
+    a.y = (const float *)c.Y + (long)a.ch * e->chunk * e->N;
+    for (int k = 0; k < BFIR_LEVEL_RINGS; k++) a.ring[k] = ring[k];
+    a.n_rings = nr;
+    a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
+    a.frame_stride = e->Co; a.n_t = c.tc;
+    a.scale = (float)e->out_scale; a.st = inv_stats(e, c);
+    launch_inv_lone(e->plan2, a, st);
+}
+
 // Product spectra -> the chunk's output blocks: raw frames + overflow statistics (pair, direct) or planar tout (staging).
 // The output side counts by Co / GCo where a matrix engine can get (never the staging path).
 static void queue_inv(bfir_engine *e, Path p, const Chunk &c, hipStream_t st)
@@ -1498,15 +1539,8 @@ static void queue_inv(bfir_engine *e, Path p, const Chunk &c, hipStream_t st)
             // the head of a multi-level matrix engine with an odd output count, in a chunk to which no level contributes: the
             // pairs below it through the pair kernel, frames Co floats apart, then the last output alone (k_inv_lone, no ring)
             a.C = e->Co & ~1; a.frame_stride = e->Co;
-            LoneInvArgs b;
-            b.y = (const float *)c.Y + (long)a.C * e->chunk * e->N;
-            b.ring[0] = b.ring[1] = b.ring[2] = LevelRing{nullptr, 0, 0, 0, 0, 0};
-            b.n_rings = 0;
-            b.raw = (float *)c.d_out; b.frame_off = c.frame_off;
-            b.frame_stride = e->Co; b.ch = a.C; b.n_t = c.tc;
-            b.scale = a.scale; b.max = a.max;
-            b.overflow = e->d_of; b.of_shard_stride = e->GCo; b.bad_block = e->d_bad; b.block_base = c.block_base; b.bad_host = e->bad_host_cur;
-            launch_inv_lone(e->plan2, b, st);
+            LevelRing none[BFIR_LEVEL_RINGS] = {};
+            queue_inv_lone(e, c, none, 0, st);
         }
         launch_inv_pair(e->plan2, a, st);
         return;
@@ -1551,9 +1585,8 @@ static void queue_inv_fade(bfir_engine *e, const Chunk &c, hipStream_t st)
         a.y_new = (const float *)c.Y2; a.y_new_ch_stride = c.y2_ch_stride;
         a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
         a.n_ch = e->Co; a.n_t = c.tc;
-        a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+        a.scale = (float)e->out_scale; a.st = inv_stats(e, c);
         a.f = e->fade_f; a.m0 = c.m0;
-        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
         launch_inv_fade(e->plan2, a, st);
         return;
     }
@@ -1611,51 +1644,20 @@ static void queue_inv_tail(bfir_engine *e, const Chunk &c, hipStream_t st)
 static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
 {
     LevelRing ring[BFIR_LEVEL_RINGS];
-    int nr = 0;
-    for (int i = 0; i < e->n_tail; i++) {
-        if (!(e->nup_mask >> i & 1)) continue;
-        const bfir_engine *t = e->tail[i];
-        LevelRing &g = ring[nr++];
-        g.z = t->zring; g.zlen = g.z_ch_stride = (long)t->zblocks * t->L;
-        g.m0 = ((long long)e->blockcounter - e->lv_D[i]) * e->L; g.m_min = t->z_from * (long long)t->L;
-        g.m0r = (long)(((g.m0 % g.zlen) + g.zlen) % g.zlen);
-    }
+    const int nr = chunk_rings(e, ring);
     if (e->back_fused) {   // one inverse per channel pair and block, the sum, statistics and frame store in one kernel
         ProfScope ps(e, BFIR_K_INV, st);
         // a matrix engine with an odd output count: the pairs below it, frames Co floats apart, then the last output alone
-        const int n_pair = e->Co & ~1, fstride = n_pair == e->Co ? 0 : e->Co;
-        if (n_pair < e->Co) {
-            LoneInvArgs a;
-            a.y = (const float *)c.Y + (long)n_pair * e->chunk * e->N;
-            for (int k = 0; k < BFIR_LEVEL_RINGS; k++) a.ring[k] = ring[k < nr ? k : 0];
-            a.n_rings = nr;
-            a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
-            a.frame_stride = e->Co; a.ch = n_pair; a.n_t = c.tc;
-            a.scale = (float)e->out_scale; a.max = (float)e->of_max;
-            a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
-            launch_inv_lone(e->plan2, a, st);
-        }
-        if (nr == 1) {
-            NupInvArgs a;
-            a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
-            a.z = (const float *)ring[0].z; a.z_ch_stride = ring[0].z_ch_stride; a.zlen = ring[0].zlen;
-            a.m0 = ring[0].m0; a.m_min = ring[0].m_min; a.m0r = ring[0].m0r;
-            a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
-            a.n_ch = n_pair; a.n_t = c.tc; a.frame_stride = fstride;
-            a.scale = (float)e->out_scale; a.max = (float)e->of_max;
-            a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
-            launch_inv_nup(e->plan2, a, st);
-        } else {
-            LevelsInvArgs a;
-            a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
-            for (int k = 0; k < BFIR_LEVEL_RINGS; k++) a.ring[k] = ring[k < nr ? k : 0];
-            a.n_rings = nr;
-            a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
-            a.n_ch = n_pair; a.n_t = c.tc; a.frame_stride = fstride;
-            a.scale = (float)e->out_scale; a.max = (float)e->of_max;
-            a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
-            launch_inv_levels(e->plan2, a, st);
-        }
+        const int n_pair = e->Co & ~1;
+        if (n_pair < e->Co) queue_inv_lone(e, c, ring, nr, st);
+        LevelsInvArgs a;
+        a.y = (const float *)c.Y; a.y_ch_stride = (long)e->chunk * e->N;
+        for (int k = 0; k < BFIR_LEVEL_RINGS; k++) a.ring[k] = ring[k];
+        a.n_rings = nr;
+        a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
+        a.n_ch = n_pair; a.n_t = c.tc; a.frame_stride = n_pair == e->Co ? 0 : e->Co;
+        a.scale = (float)e->out_scale; a.st = inv_stats(e, c);
+        launch_inv_levels(e->plan2, a, st);
         return;
     }
     // the general form: a planar inverse into tout, the sum, then the staging path's output kernel
@@ -1667,21 +1669,12 @@ static void queue_inv_nup(bfir_engine *e, const Chunk &c, hipStream_t st)
         a.n_t = c.tc; a.n_ch = e->GCo;
         a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
         launch_inv(e->plan, a, st);
-        if (nr == 1) {
-            NupCombineArgs b;
-            b.y = e->tout; b.y_ch_stride = t_stride;
-            b.z = ring[0].z; b.z_ch_stride = ring[0].z_ch_stride; b.zlen = ring[0].zlen;
-            b.m0 = ring[0].m0; b.m_min = ring[0].m_min; b.m0r = ring[0].m0r;
-            b.n_ch = e->GCo; b.n = (long)c.tc * e->L; b.realsize = e->s;
-            launch_nup_combine(b, st);
-        } else {
-            LevelsCombineArgs b;
-            b.y = e->tout; b.y_ch_stride = t_stride;
-            for (int k = 0; k < BFIR_LEVEL_RINGS; k++) b.ring[k] = ring[k < nr ? k : 0];
-            b.n_rings = nr;
-            b.n_ch = e->GCo; b.n = (long)c.tc * e->L; b.realsize = e->s;
-            launch_levels_combine(b, st);
-        }
+        LevelsCombineArgs b;
+        b.y = e->tout; b.y_ch_stride = t_stride;
+        for (int k = 0; k < BFIR_LEVEL_RINGS; k++) b.ring[k] = ring[k];
+        b.n_rings = nr;
+        b.n_ch = e->GCo; b.n = (long)c.tc * e->L; b.realsize = e->s;
+        launch_levels_combine(b, st);
     }
     queue_stage_out(e, c, e->tout, t_stride, st);
 }
@@ -1692,18 +1685,7 @@ static void queue_inv_lfade(bfir_engine *e, const Chunk &c, hipStream_t st)
 {
     LevelRing ring[BFIR_LEVEL_RINGS];
     const void *z_new[BFIR_LEVEL_RINGS];
-    int nr = 0;
-    for (int i = 0; i < e->n_tail; i++) {
-        if (!(e->nup_mask >> i & 1)) continue;
-        const bfir_engine *t = e->tail[i];
-        // a level outside the fade (neither set reaches it, but output queued before it stopped still plays) adds the same to both sums
-        z_new[nr] = t->lf_mode ? t->zring2 : t->zring;
-        LevelRing &g = ring[nr++];
-        g.z = t->zring; g.zlen = g.z_ch_stride = (long)t->zblocks * t->L;
-        g.m0 = ((long long)e->blockcounter - e->lv_D[i]) * e->L; g.m_min = t->z_from * (long long)t->L;
-        g.m0r = (long)(((g.m0 % g.zlen) + g.zlen) % g.zlen);
-    }
-    for (int k = nr; k < BFIR_LEVEL_RINGS; k++) { ring[k] = ring[0]; z_new[k] = z_new[0]; }
+    const int nr = chunk_rings(e, ring, z_new);
     if (e->fade_fused) {   // one inverse per channel and block, both sums, blend, statistics and frame store in one kernel
         ProfScope ps(e, BFIR_K_INV, st);
         LfadeInvArgs a;
@@ -1713,9 +1695,8 @@ static void queue_inv_lfade(bfir_engine *e, const Chunk &c, hipStream_t st)
         a.n_rings = nr;
         a.raw = (float *)c.d_out; a.frame_off = c.frame_off;
         a.n_ch = e->Co; a.n_t = c.tc;                      // a matrix engine: its outputs, an odd count included
-        a.scale = (float)e->out_scale; a.max = (float)e->of_max;
+        a.scale = (float)e->out_scale; a.st = inv_stats(e, c);
         a.f = e->fade_f; a.m0 = c.m0;
-        a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
         launch_inv_lfade(e->plan2, a, st);
         return;
     }

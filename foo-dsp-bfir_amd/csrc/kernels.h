@@ -252,6 +252,24 @@ void launch_inv_pair(const FftPlan &plan, const InvPairArgs &a, hipStream_t s);
 // 16-byte frame stores, the same bits as the pair kernel.  false: not taken (launch_inv_pair goes on with the pair kernel).
 bool launch_inv_quad(const FftPlan &plan, const InvPairArgs &a, hipStream_t s);
 
+// What every one-transform fused back end below (inv_back.h) needs for its overflow statistics and NaN guard.
+struct InvStats {
+    float max;                                           // bfoverflow_t.max
+    DevOverflow *overflow; long of_shard_stride;
+    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+};
+// The launch of a planar middle step k<real, VEC>(args) -- blocks of 256 lanes over args.n samples of args.n_ch channels --
+// given its four instances (BFIR_PLANAR_KERNELS) and the verdict on alignment: lane-consecutive, 16 bytes per lane where
+// every channel's samples are 16-byte aligned, else one sample per lane.
+#define BFIR_PLANAR_KERNELS(k) k<float, 4>, k<float, 1>, k<double, 2>, k<double, 1>
+template <typename A>
+inline void launch_planar(void (*f4)(A), void (*f1)(A), void (*d2)(A), void (*d1)(A), const A &a, bool aligned, hipStream_t s)
+{
+    const long lanes = aligned ? a.n / (16 / a.realsize) : a.n;
+    const dim3 grid((unsigned)((lanes + 255) / 256), (unsigned)a.n_ch), block(256);
+    hipLaunchKernelGGL(a.realsize == 4 ? (aligned ? f4 : f1) : (aligned ? d2 : d1), grid, block, 0, s, a);
+}
+
 // fade.hip: the back end of a crossfaded coefficient change (bfir_engine_set_coeff_fade; the reference's blend is
 // fftw_convolver::convolver_crossfade_inplace, brutefir/fftw_convolver.cpp:275-321).  The MAC has run twice over the same
 // delay line: y_old holds the products with the old filters, y_new those with the new ones.  Sample n of block t blends as
@@ -265,10 +283,9 @@ struct FadeInvArgs {
     const float *y_new; long y_new_ch_stride;
     float *raw; long frame_off;                          // output frames of ONE engine, n_ch channels wide
     int n_ch, n_t;
-    float scale, max;
+    float scale;
     float f; int m0;                                     // the ramp: 1 / (K L - 1), and m of sample 0 of block 0
-    DevOverflow *overflow; long of_shard_stride;
-    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+    InvStats st;
 };
 void launch_inv_fade(const FftPlan &plan, const FadeInvArgs &a, hipStream_t s);
 // k_fade_blend, the general form's middle step: y_old[c][i] <- blend(y_old[c][i], y_new[c][i]) on planar time buffers
@@ -281,68 +298,51 @@ struct FadeBlendArgs {
 };
 void launch_fade_blend(const FadeBlendArgs &a, hipStream_t s);
 
-// nup.hip: the back end of a two-level engine (bfir_engine_create_nup).  The head level's products are in y; the tail level
-// has left its time output z in a planar ring [n_ch][zlen] of working precision, sample m of z at m mod zlen.  Sample n of
-// block t of the chunk is  y_head[n] + z[m],  m = m0 + t L + n  (one addition, head first); nothing is added where
-// m < m_min.  m0, m_min and zlen are multiples of L; m0r = m0 mod zlen.
-// k_inv_nup, the fused form: fp32, (re, im) pairs, FLOAT_LE frames, even n_ch, 512 <= L <= 8192 (pair_supported).  One
-// workgroup per (channel pair, block): Z = Y_a + i Y_b, ONE inverse of 2L points (`plan` is the plan of 2L points), the sum,
-// overflow statistics, NaN guard, frame store.
-struct NupInvArgs {
-    const float *y; long y_ch_stride;                    // [n_ch][..][N] product spectra, (re, im) pairs
-    const float *z; long z_ch_stride; long zlen;         // the tail's time ring
-    long long m0, m_min; long m0r;
-    float *raw; long frame_off;                          // output frames of ONE engine, n_ch channels wide
-    int n_ch, n_t;
-    float scale, max;
-    DevOverflow *overflow; long of_shard_stride;
-    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
-    int frame_stride = 0;                                // floats between output frames; 0 = n_ch (wider: an odd matrix output beside the pairs)
-};
-void launch_inv_nup(const FftPlan &plan, const NupInvArgs &a, hipStream_t s);
-// k_nup_combine, the general form's middle step: y[c][i] <- y[c][i] + z[c][(m0 + i) mod zlen] on a planar time buffer
-// [n_ch][..] (i < n: the chunk's n_t L samples of a channel); launch_inv fills it, launch_stage_out follows.
-struct NupCombineArgs {
-    void *y; long y_ch_stride;                           // in reals
-    const void *z; long z_ch_stride; long zlen;
-    long long m0, m_min; long m0r;
-    int n_ch; long n;
-    int realsize;
-};
-void launch_nup_combine(const NupCombineArgs &a, hipStream_t s);
-
-// levels.hip: the back end of a multi-level engine (bfir_engine_create_levels) for a chunk to which two or three tail
-// levels contribute (one: the two-level back end above).  Every contributing level has left its time output in a ring of
-// its own, described as in NupInvArgs; sample n of block t is  ((y_head[n] + z_0[m_0]) + z_1[m_1]) + z_2[m_2],
-// m_r = ring[r].m0 + t L + n, the rings in level order, nothing added from a ring where m_r < ring[r].m_min.  Each m0,
-// m_min and zlen is a multiple of L, so a block's L samples of a ring are contiguous: the rings wrap between blocks only.
+// nup.hip, levels.hip: the back ends of a two-level engine (bfir_engine_create_nup) and of a multi-level engine
+// (bfir_engine_create_levels).  The head level's products are in y; every contributing tail level has left its time output
+// in a planar ring [n_ch][zlen] of working precision of its own, sample m at m mod zlen.  Sample n of block t of the chunk is
+//   ((y_head[n] + z_0[m_0]) + z_1[m_1]) + z_2[m_2],   m_r = ring[r].m0 + t L + n
+// the additions head first, rings in level order, nothing added from a ring where m_r < ring[r].m_min.  Each m0, m_min and
+// zlen is a multiple of L, so a block's L samples of a ring are contiguous: the rings wrap between blocks only.
 constexpr int BFIR_LEVEL_RINGS = 3;
 struct LevelRing {
     const void *z; long z_ch_stride; long zlen;          // planar [n_ch][zlen] reals of working precision
     long long m0, m_min; long m0r;                       // m0r = m0 mod zlen
 };
-// k_inv_levels, the fused form: as k_inv_nup (fp32, (re, im) pairs, FLOAT_LE frames, even n_ch, 512 <= L <= 8192; `plan` is
-// the plan of 2L points) with n_rings = 2 or 3 additions per sample.
+// k_inv_nup (one ring, nup.hip) and k_inv_levels (two or three, levels.hip), the fused form: fp32, (re, im) pairs, FLOAT_LE
+// frames, even n_ch, 512 <= L <= 8192 (pair_supported).  One workgroup per (channel pair, block): Z = Y_a + i Y_b, ONE
+// inverse of 2L points (`plan` is the plan of 2L points), the sums, overflow statistics, NaN guard, frame store.
 struct LevelsInvArgs {
     const float *y; long y_ch_stride;                    // [n_ch][..][N] product spectra, (re, im) pairs
-    LevelRing ring[BFIR_LEVEL_RINGS]; int n_rings;
+    LevelRing ring[BFIR_LEVEL_RINGS]; int n_rings;       // 1 .. 3
     float *raw; long frame_off;                          // output frames of ONE engine, n_ch channels wide
     int n_ch, n_t;
-    float scale, max;
-    DevOverflow *overflow; long of_shard_stride;
-    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
-    int frame_stride = 0;                                // as in NupInvArgs
+    float scale;
+    InvStats st;
+    int frame_stride = 0;                                // floats between output frames; 0 = n_ch (wider: an odd matrix output beside the pairs)
 };
-void launch_inv_levels(const FftPlan &plan, const LevelsInvArgs &a, hipStream_t s);
-// k_levels_combine, the general form's middle step: y[c][i] <- y[c][i] + z_0 + z_1 (+ z_2) on a planar time buffer
-// [n_ch][..] (i < n: the chunk's n_t L samples of a channel) in one pass; launch_inv fills it, launch_stage_out follows.
+void launch_inv_nup(const FftPlan &plan, const LevelsInvArgs &a, hipStream_t s);      // n_rings == 1
+void launch_inv_levels(const FftPlan &plan, const LevelsInvArgs &a, hipStream_t s);   // any n_rings: one goes to launch_inv_nup
+// k_nup_combine (one ring) and k_levels_combine, the general form's middle step: y[c][i] <- y[c][i] + z_0 (+ z_1 (+ z_2)),
+// z_r at (ring[r].m0 + i) mod zlen, on a planar time buffer [n_ch][..] (i < n: the chunk's n_t L samples of a channel) in one
+// pass; launch_inv fills it, launch_stage_out follows.
 struct LevelsCombineArgs {
     void *y; long y_ch_stride;                           // in reals
     LevelRing ring[BFIR_LEVEL_RINGS]; int n_rings;
     int n_ch; long n;
     int realsize;
 };
-void launch_levels_combine(const LevelsCombineArgs &a, hipStream_t s);
+void launch_nup_combine(const LevelsCombineArgs &a, hipStream_t s);      // n_rings == 1
+void launch_levels_combine(const LevelsCombineArgs &a, hipStream_t s);   // any n_rings: one goes to launch_nup_combine
+// the alignment verdict (launch_planar) on n_rings rings, and on their second set where a fade keeps one
+inline bool rings_aligned16(const LevelRing *ring, const void *const *z_new, int n_rings, int vec)
+{
+    bool ok = true;
+    for (int r = 0; r < n_rings; r++)
+        ok = ok && ring[r].z_ch_stride % vec == 0 && ring[r].zlen % vec == 0 && ring[r].m0r % vec == 0 &&
+             ((uintptr_t)ring[r].z | (uintptr_t)(z_new ? z_new[r] : nullptr)) % 16 == 0;
+    return ok;
+}
 
 // mlevels.hip: the fused back end of a multi-level matrix engine (bfir_engine_create_matrix_levels) with an odd output
 // count.  Outputs (0, 1), (2, 3), ... go through k_inv_nup / k_inv_levels with n_ch = 2 floor(n_out / 2) and frame_stride =
@@ -354,9 +354,8 @@ struct LoneInvArgs {
     LevelRing ring[BFIR_LEVEL_RINGS]; int n_rings;       // planar rings of ALL channels: channel ch is read
     float *raw; long frame_off;                          // output frames of ONE engine, frame_stride floats apart
     int frame_stride, ch, n_t;
-    float scale, max;
-    DevOverflow *overflow; long of_shard_stride;         // [n_out] per shard: channel ch is updated
-    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+    float scale;
+    InvStats st;                                         // overflow: [n_out] per shard, channel ch is updated
 };
 void launch_inv_lone(const FftPlan &plan, const LoneInvArgs &a, hipStream_t s);
 
@@ -374,10 +373,9 @@ struct LfadeInvArgs {
     LevelRing ring[BFIR_LEVEL_RINGS]; const void *z_new[BFIR_LEVEL_RINGS]; int n_rings;
     float *raw; long frame_off;                          // output frames of ONE engine, n_ch channels wide
     int n_ch, n_t;
-    float scale, max;
+    float scale;
     float f; int m0;                                     // the ramp: 1 / (K L - 1), and m of sample 0 of block 0
-    DevOverflow *overflow; long of_shard_stride;
-    int *bad_block; int block_base; int *bad_host;       // as in StageOutArgs
+    InvStats st;
 };
 void launch_inv_lfade(const FftPlan &plan, const LfadeInvArgs &a, hipStream_t s);
 // k_lfade_sum, the general form's middle step: y_old[c][i] <- blend(y_old[c][i] + old rings, y_new[c][i] + new rings) on
