@@ -240,6 +240,9 @@ struct bfir_engine {
     // The channel-pair inverse with 16-byte frame stores (k_inv_quad_ps, quad.hip; InvPairArgs.quad): by default for launches
     // that fill the GPU.  BFIR_INV_QUAD=0|1 forbids it / takes it wherever it applies, read at creation (choose_path)
     int inv_quad = -1;
+    // The channel-pair forward transform with 16-byte frame loads (k_fwd_wide_ps, wide.hip; FwdPairArgs.wide): the same rule.
+    // BFIR_FWD_WIDE=0|1, read at creation (choose_path)
+    int fwd_wide = -1;
     // profiling
     bool profiling = false;
     struct Span { int k; hipEvent_t a, b; };
@@ -421,6 +424,7 @@ static void choose_path(bfir_engine *e)
     // k_mac_matrix in every paired run ("Crossfades on multi-level matrix engines"); BFIR_MFADE_DUO=0 keeps the two
     if (const char *mv = getenv("BFIR_MFADE_DUO")) e->mfade_duo = atoi(mv) != 0;
     if (const char *qv = getenv("BFIR_INV_QUAD")) e->inv_quad = atoi(qv) != 0;
+    if (const char *wv = getenv("BFIR_FWD_WIDE")) e->fwd_wide = atoi(wv) != 0;
     if (const char *pm = getenv("BFIR_PIPE")) { e->pipe3 = atoi(pm) >= 3; e->serial = atoi(pm) == 1; }
     // fp64 engines: one stream.  Their kernels are bound by issue and latency, not by memory, each fills the GPU by itself, and
     // three of them side by side only get into each other's way: the plug-in's shape 42.8 -> 45.9 Gsamples/s, 8 channels 42.5 ->
@@ -1456,7 +1460,7 @@ static void queue_fwd(bfir_engine *e, Path p, const Chunk &c, hipStream_t sf)
         a.hist_eng_stride = (long)e->L * e->C;
         a.dst = (float *)e->X; a.dst_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = c.base_slot;
         a.scale = (float)e->in_scale;
-        a.tp = e->pair_tp;
+        a.tp = e->pair_tp; a.wide = e->fwd_wide;
         launch_fwd_pair(e->plan2, a, sf);
     } else {
         FwdArgs a;

@@ -233,8 +233,12 @@ struct FwdPairArgs {
     float *dst; long dst_ch_stride; int ring, base_slot; // delay line, (re, im) pairs
     float scale;
     int tp = 0;                                          // pairs in TIME: blocks t, t+1 of one channel per transform (any C)
+    int wide = -1;                                       // k_fwd_wide_ps where it applies: 0 never, 1 always, -1 for launches that fill the GPU
 };
 void launch_fwd_pair(const FftPlan &plan, const FwdPairArgs &a, hipStream_t s);
+// wide.hip: channel pairs, C % 4 == 0, frames and history blocks 16-byte aligned -- two pairs in turn per workgroup and
+// 16-byte frame loads, the same bits as the pair kernel.  false: not taken (launch_fwd_pair goes on with the pair kernel).
+bool launch_fwd_wide(const FftPlan &plan, const FwdPairArgs &a, hipStream_t s);
 struct InvPairArgs {
     const float *y; long y_ch_stride;                    // [gc][n_t][N] product spectra, (re, im) pairs
     float *raw; long eng_stride; long frame_off;         // output frames

@@ -675,6 +675,7 @@ void launch_fwd_pair(const FftPlan &plan, const FwdPairArgs &a, hipStream_t s)
         }
         return;
     }
+    if (launch_fwd_wide(plan, a, s)) return;               // two channel pairs per workgroup, 16-byte frame loads (wide.hip)
     const int pairs = a.n_eng * (a.C / 2);
     if (a.n_t <= 0 || pairs <= 0 || !plan.twb) return;
     const int len = pair_run_len(a.n_t, pairs, false), runs = (a.n_t + len - 1) / len;

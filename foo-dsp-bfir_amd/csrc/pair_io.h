@@ -1,4 +1,4 @@
-// pair_io.h -- buffer addressing and hand-counted prefetch of the persistent float-frame kernels (pair.hip, quad.hip).
+// pair_io.h -- buffer addressing and hand-counted prefetch of the persistent float-frame kernels (pair.hip, quad.hip, wide.hip).
 #pragma once
 #include "kernels.h"
 
@@ -87,6 +87,30 @@ __device__ __forceinline__ void asm_prefetch2x4x4(u32x4 (&a)[4], u32x4 (&b)[4], 
                  "buffer_load_dwordx4 %7, %8, %10, %13 offen nt"
                  : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3])
                  : "v"(voff), "s"(ra), "s"(rb), "s"(s1), "s"(s2), "s"(s3)
+                 : "memory");
+}
+// 8 x 16 bytes per lane: buffer[voff + k * step] <- d[k].  One asm statement that ENDS in a wait state: left to the
+// compiler (raw_buffer_store_b128 with a register offset) the instruction after a store was a VALU write of the store's
+// first data register -- in k_inv_quad_ps the next piece's overflow count -- and on the GPU that value (0) went out in
+// place of channel 4q's sample in some lanes of some launches.  Data registers of a 16-byte store must not be written in
+// the slot behind it (cdna_hip_programming.md 5.7 item 1, stores); the opening s_nop covers the descriptor fresh from
+// readfirstlane.  (quad.hip: the output frames; wide.hip: the history frames.)
+__device__ __forceinline__ void asm_store8x4(const u32x4 (&d)[8], unsigned voff, i32x4 r, unsigned step)
+{
+    const unsigned s1 = __builtin_amdgcn_readfirstlane(step), s2 = 2 * s1, s3 = 3 * s1, s4 = 4 * s1, s5 = 5 * s1, s6 = 6 * s1, s7 = 7 * s1;
+    asm volatile("s_nop 4\n\t"
+                 "buffer_store_dwordx4 %0, %8, %9, 0 offen\n\t"
+                 "buffer_store_dwordx4 %1, %8, %9, %10 offen\n\t"
+                 "buffer_store_dwordx4 %2, %8, %9, %11 offen\n\t"
+                 "buffer_store_dwordx4 %3, %8, %9, %12 offen\n\t"
+                 "buffer_store_dwordx4 %4, %8, %9, %13 offen\n\t"
+                 "buffer_store_dwordx4 %5, %8, %9, %14 offen\n\t"
+                 "buffer_store_dwordx4 %6, %8, %9, %15 offen\n\t"
+                 "buffer_store_dwordx4 %7, %8, %9, %16 offen\n\t"
+                 "s_nop 1"
+                 :
+                 : "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(d[4]), "v"(d[5]), "v"(d[6]), "v"(d[7]),
+                   "v"(voff), "s"(r), "s"(s1), "s"(s2), "s"(s3), "s"(s4), "s"(s5), "s"(s6), "s"(s7)
                  : "memory");
 }
 // 2 x 8 x 4 bytes per lane (time pairs: one channel's samples of two blocks): b[e] <- buffer B[voff + e * step], c[e] <- buffer C[...]

@@ -52,30 +52,6 @@ __device__ __forceinline__ void asm_prefetch2x4x4_out(u32x4 (&a)[4], u32x4 (&b)[
                  : "memory");
 }
 
-// 8 x 16 bytes per lane: buffer[voff + k * step] <- d[k].  One asm statement that ENDS in a wait state: left to the
-// compiler (raw_buffer_store_b128 with a register offset) the instruction after a store was a VALU write of the store's
-// first data register -- the next piece's overflow count -- and on the GPU that value (0) went out in place of channel
-// 4q's sample in some lanes of some launches.  Data registers of a 16-byte store must not be written in the slot behind
-// it (cdna_hip_programming.md 5.7 item 1, stores); the opening s_nop covers the descriptor fresh from readfirstlane.
-__device__ __forceinline__ void asm_store8x4(const u32x4 (&d)[8], unsigned voff, i32x4 r, unsigned step)
-{
-    const unsigned s1 = __builtin_amdgcn_readfirstlane(step), s2 = 2 * s1, s3 = 3 * s1, s4 = 4 * s1, s5 = 5 * s1, s6 = 6 * s1, s7 = 7 * s1;
-    asm volatile("s_nop 4\n\t"
-                 "buffer_store_dwordx4 %0, %8, %9, 0 offen\n\t"
-                 "buffer_store_dwordx4 %1, %8, %9, %10 offen\n\t"
-                 "buffer_store_dwordx4 %2, %8, %9, %11 offen\n\t"
-                 "buffer_store_dwordx4 %3, %8, %9, %12 offen\n\t"
-                 "buffer_store_dwordx4 %4, %8, %9, %13 offen\n\t"
-                 "buffer_store_dwordx4 %5, %8, %9, %14 offen\n\t"
-                 "buffer_store_dwordx4 %6, %8, %9, %15 offen\n\t"
-                 "buffer_store_dwordx4 %7, %8, %9, %16 offen\n\t"
-                 "s_nop 1"
-                 :
-                 : "v"(d[0]), "v"(d[1]), "v"(d[2]), "v"(d[3]), "v"(d[4]), "v"(d[5]), "v"(d[6]), "v"(d[7]),
-                   "v"(voff), "s"(r), "s"(s1), "s"(s2), "s"(s3), "s"(s4), "s"(s5), "s"(s6), "s"(s7)
-                 : "memory");
-}
-
 template <int LOG2N>
 __global__ __launch_bounds__(FftCfg<LOG2N>::NT, inv_ps_min_waves<LOG2N>()) void k_inv_quad_ps(InvPairArgs a, const float2 *__restrict__ twb, int run_len)
 {

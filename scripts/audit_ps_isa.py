@@ -18,7 +18,12 @@ when a compiler or flag change breaks an assumption.  BFIR_PAIR=0 (the planar st
 k_inv_quad_ps (quad.hip) has two prefetch statements and two counted waits per block: audit_quad() checks 1 - 3 for each
 window (tests/test_quad_isa.py); audit() and parse() see the pair and time-pair kernels only.
 
-    python scripts/audit_ps_isa.py [pair.s]      (without an argument: compiles csrc/pair.hip and csrc/quad.hip to assembly first)
+k_fwd_wide_ps (wide.hip) has ONE prefetch statement of eight loads (both channel pairs of the next block, issued under the
+second pair's passes), one counted wait and one closing wait: audit_wide() holds it to 1 - 4 as they stand
+(tests/test_wide_isa.py).
+
+    python scripts/audit_ps_isa.py [pair.s]      (without an argument: compiles csrc/pair.hip, csrc/quad.hip and csrc/wide.hip
+                                                  to assembly first)
 """
 import os
 import re
@@ -278,6 +283,18 @@ def audit_quad(asm_path=None):
     return report
 
 
+def audit_wide(asm_path=None):
+    """{"k_fwd_wide_ps<13>": [errors], ...} for the wide kernels; without a listing, compiles csrc/wide.hip first."""
+    if asm_path is None:
+        asm_path = compile_to_asm(os.path.join(tempfile.mkdtemp(prefix="bfir_isa_"), "wide.s"), "wide.hip")
+    kernels, meta = parse(asm_path, "wide")
+    report = {}
+    for name, k in sorted(kernels.items()):
+        short = re.search(r"k_(fwd|inv)_wide_psILi(\d+)E", name)
+        report["k_%s_wide_ps<%s>" % short.groups()] = audit_kernel(k, meta.get(name, {}))
+    return report
+
+
 def main():
     if len(sys.argv) > 1:
         path = sys.argv[1]
@@ -285,6 +302,7 @@ def main():
         path = compile_to_asm(os.path.join(tempfile.mkdtemp(prefix="bfir_isa_"), "pair.s"))
     rep = audit(path)
     rep.update(audit_quad(path if len(sys.argv) > 1 else None))
+    rep.update(audit_wide(path if len(sys.argv) > 1 else None))
     bad = 0
     for k, errs in rep.items():
         print("%-24s %s" % (k, "ok" if not errs else "FAIL"))
