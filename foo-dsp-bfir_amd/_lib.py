@@ -54,6 +54,7 @@ SIGNATURES = {
     "bfir_version": (C.c_char_p, []),
     "bfir_engine_create": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_create_batch": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
+    "bfir_engine_create_big": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_create_matrix": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_destroy": (None, [_vp]),
     "bfir_engine_is_initialized": (_ci, [_vp]),

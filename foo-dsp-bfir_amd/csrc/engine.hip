@@ -105,6 +105,11 @@ struct bfir_engine {
     int in_bytes = 0, out_bytes = 0, in_fmt = 0, out_fmt = 0;
     double in_scale = 1.0, out_scale = 1.0, of_max = 1.0;
     FftPlan plan;
+    // a big engine (bfir_engine_create_big, bigconv.hip): partitions past one workgroup's transform.  `plan` stays empty and
+    // every transform goes through bplan's two passes (queue_transform_*); the spectra X, H, Y are in its transposed bin
+    // order, which the MAC never notices and read_spectrum undoes.  Always the staging path.
+    bool big = false;
+    BigPlan bplan;
     int chunk = 0, ring = 0;        // allocated geometry
     int want_chunk = 0;                    // blocks per launch (bfir_engine_set_chunk); 0 = automatic; buffers are sized lazily
     void *H = nullptr, *X = nullptr, *Y = nullptr, *tout = nullptr;
@@ -398,6 +403,7 @@ static void choose_path(bfir_engine *e)
     e->direct = !e->pair && fmt_is_native(e->in_fmt) && fmt_is_native(e->out_fmt) && !(pv && atoi(pv) == 0) &&
                 (dv ? atoi(dv) != 0 : wide);
     if (e->matrix) e->direct = !e->pair;   // a matrix engine has no staging path: float frames only, direct where not paired
+    if (e->big) e->pair = e->pair_tp = e->direct = false;   // the two-pass transforms take the planar form only
     if (e->nup || e->nup_tail) {           // both levels of a two-level engine likewise, and no pairs in time: an odd count is direct
         e->pair = e->pair && !e->pair_tp;
         e->pair_tp = false;
@@ -436,6 +442,11 @@ static void choose_path(bfir_engine *e)
 static void log_creation(const bfir_engine *e)
 {
     char shape[64];
+    if (e->big) {
+        bfir_logf("bfir engine: big, %d x %d channels, partition %d = %d x %d, %d blocks, realsize %d on device %d. layout=%s",
+                  e->n_eng, e->C, e->L, 1 << e->bplan.log2m1, 1 << e->bplan.log2m2, e->B, e->s, e->device, e->ilv ? "pairs" : "grouped");
+        return;
+    }
     // a matrix engine's path=pair can give way to direct mode while an input feeds no output (bfir_engine_set_coeff_matrix logs it)
     if (e->matrix) snprintf(shape, sizeof(shape), "matrix %d -> %d", e->C, e->Co);
     else snprintf(shape, sizeof(shape), "%d x %d channels", e->n_eng, e->C);
@@ -449,7 +460,7 @@ static void log_creation(const bfir_engine *e)
 // nup_level: 0, or 1 / 2 for the head / tail level of a two-level engine (bfir_engine_create_nup)
 static bfir_engine *engine_create(int n_engines, int filter_length, int filter_blocks, int realsize, int channels,
                                   int channels_out, bool matrix, int in_format, int out_format, int sampling_rate,
-                                  int apply_dither, int device, int *err, int nup_level = 0, int ring_extra = 0)
+                                  int apply_dither, int device, int *err, int nup_level = 0, int ring_extra = 0, bool big = false)
 {
     int dummy;
     if (!err) err = &dummy;
@@ -484,10 +495,11 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
     e->of_max = fmt_info(out_format).isfloat ? 1.0 : fmt_full_scale(out_format) - 1.0;
     e->nup = nup_level == 1; e->nup_tail = nup_level == 2;
     e->ring_extra = ring_extra;
+    e->big = big;
     choose_path(e);
     e->nblk.assign(matrix ? (size_t)e->Co * e->C : (size_t)e->GC, 0);   // matrix: [o C + i]
     e->eng_init.assign(n_engines, 0);
-    int rc = fft_plan_create(&e->plan, filter_length, realsize);
+    int rc = big ? big_plan_create(&e->bplan, filter_length, realsize) : fft_plan_create(&e->plan, filter_length, realsize);
     if (rc != 0) { *err = (rc == -1) ? BFIR_ERR_UNSUPPORTED : BFIR_ERR_HIP; delete e; return nullptr; }
     auto fail = [&](int code) { *err = code; bfir_engine_destroy(e); return (bfir_engine *)nullptr; };
     if (e->pair || e->direct) {
@@ -586,6 +598,34 @@ static bool length_supported(int filter_length, int realsize)
 {
     return filter_length >= 16 && filter_length <= 16384 &&
            ((size_t)filter_length + (size_t)filter_length / 32) * 2 * (size_t)realsize <= 160 * 1024;
+}
+
+// Partitions past one workgroup's transform: 2^15 (fp64: 2^14) .. 2^20 samples, the lengths big_split takes.
+extern "C" bfir_engine *bfir_engine_create_big(int filter_length, int filter_blocks, int realsize, int channels,
+                                               int in_format, int out_format, int sampling_rate, int apply_dither,
+                                               int device, int *err)
+{
+    int dummy, l1, l2;
+    if (!err) err = &dummy;
+    const bool pow2 = filter_length >= 1 && !(filter_length & (filter_length - 1));
+    // everything else about the arguments is engine_create's to judge, in its order
+    if (pow2 && (realsize == 4 || realsize == 8) && channels >= 1 && channels <= BFIR_MAXCHANNELS && filter_blocks >= 1) {
+        if (!big_split(filter_length, realsize, &l1, &l2)) {
+            if (length_supported(filter_length, realsize))
+                bfir_logf("bfir engine: partition %d with realsize %d is one workgroup's transform: use bfir_engine_create.",
+                          filter_length, realsize);
+            else
+                bfir_logf("bfir engine: partition %d is past the big engine's range (up to 1048576).", filter_length);
+            *err = BFIR_ERR_UNSUPPORTED; return nullptr;
+        }
+        // one channel's filters and its smallest delay line (a chunk of one block) within the kernels' 32-bit element counts
+        if ((2ull + (unsigned long long)filter_blocks) * 2ull * (unsigned long long)filter_length >= (1ull << 31)) {
+            bfir_logf("bfir engine: %d partitions of %d are past the kernels' 32-bit indexing.", filter_blocks, filter_length);
+            *err = BFIR_ERR_UNSUPPORTED; return nullptr;
+        }
+    }
+    return engine_create(1, filter_length, filter_blocks, realsize, channels, channels, false, in_format, out_format,
+                         sampling_rate, apply_dither, device, err, 0, 0, true);
 }
 
 // The time ring of tail[i] for head chunks of up to `chunk` blocks; the blocks still to be read are carried over.
@@ -758,6 +798,7 @@ extern "C" void bfir_engine_destroy(bfir_engine *e)
     free_work(e);
     fft_plan_destroy(&e->plan);
     fft_plan_destroy(&e->plan2);
+    big_plan_destroy(&e->bplan);
     for (int st = 0; st < 2; st++) for (int i = 0; i < 2; i++) if (e->tails[st][i]) (void)hipFree(e->tails[st][i]);
     void *bufs[] = {e->H, e->saved[0], e->saved[1], e->d_nblk, e->d_of, e->d_bad, e->d_dither_tab, e->d_dither_state,
                     e->H2, e->d_nblk2, e->Yf[0], e->Yf[1], e->ft[0], e->ft[1]};
@@ -784,6 +825,16 @@ extern "C" int bfir_engine_set_chunk(bfir_engine *e, int blocks_per_launch)
     if (!e || blocks_per_launch < 0) return BFIR_ERR_ARG;   // 0: automatic (the default)
     e->want_chunk = blocks_per_launch;
     return BFIR_OK;
+}
+
+// The planar transforms of an engine: one workgroup per transform, or a big engine's two passes.
+static void queue_transform_fwd(const bfir_engine *e, const FwdArgs &a, hipStream_t s)
+{
+    if (e->big) launch_fwd_big(e->bplan, a, s); else launch_fwd(e->plan, a, s);
+}
+static void queue_transform_inv(const bfir_engine *e, const InvArgs &a, hipStream_t s)
+{
+    if (e->big) launch_inv_big(e->bplan, a, s); else launch_inv(e->plan, a, s);
 }
 
 // coeff::preprocess_coeff + convolver_coeffs2cbuf for n_rows filters, rows row0 .. of H: coeffs[n] (n < n_coeffs <= n_rows)
@@ -836,7 +887,7 @@ static int load_filters(bfir_engine *e, void *Hdst, int row0, int n_rows, const 
     fa.out_scale = 1.0 / (double)e->N;                          // fftw_convolver.cpp:520
     fa.zero_first_half = 1;
     fa.interleaved = e->ilv;
-    launch_fwd(e->plan, fa, e->stream);
+    queue_transform_fwd(e, fa, e->stream);
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipFree(d_taps));
     HIP_TRY(hipGetLastError());
@@ -1190,7 +1241,20 @@ static int read_spectrum(bfir_engine *e, int f, int block, void *dst)
     HIP_TRY(hipDeviceSynchronize());
     const size_t cb = cbuf_bytes(e);
     HIP_TRY(hipMemcpy(dst, (char *)e->H + ((size_t)f * e->B + block) * cb, cb, hipMemcpyDeviceToHost));
-    if (e->ilv) {   // hand out the reference's grouped layout (fftw_convolver.cpp:883-907)
+    if (e->big) {   // ... and natural bin order: bin k1 + M1 k2 is kept at position k1 M2 + k2 (bigconv.hip), in either layout
+        const int l1 = e->bplan.log2m1, M2 = 1 << e->bplan.log2m2;
+        const bool ilv = e->ilv;
+        auto natural = [&](auto *o) {
+            using R = typename std::remove_pointer<decltype(o)>::type;
+            std::vector<R> tmp(o, o + e->N);
+            for (int k = 0; k < e->N / 2; k++) {
+                const int p = (k & ((1 << l1) - 1)) * M2 + (k >> l1);
+                o[8 * (k >> 2) + (k & 3)] = ilv ? tmp[2 * p] : tmp[8 * (p >> 2) + (p & 3)];
+                o[8 * (k >> 2) + 4 + (k & 3)] = ilv ? tmp[2 * p + 1] : tmp[8 * (p >> 2) + 4 + (p & 3)];
+            }
+        };
+        if (e->s == 4) natural((float *)dst); else natural((double *)dst);
+    } else if (e->ilv) {   // hand out the reference's grouped layout (fftw_convolver.cpp:883-907)
         auto regroup = [&](auto *o) {
             using R = typename std::remove_pointer<decltype(o)>::type;
             std::vector<R> tmp(o, o + e->N);
@@ -1480,7 +1544,7 @@ static void queue_fwd(bfir_engine *e, Path p, const Chunk &c, hipStream_t sf)
             // input_timecbuf[n][curbuf] (fftw_convolver.cpp:184 left it there one call earlier)
             a.prev = e->hist[e->curbuf].ptr; a.prev_ch_stride = e->hist[e->curbuf].ch_stride;
         }
-        launch_fwd(e->plan, a, sf);
+        queue_transform_fwd(e, a, sf);
     }
     if (p != Path::Staging) { e->hist_raw[0] = e->tails[c.par][0]; e->hist_raw[1] = e->tails[c.par][1]; }
 }
@@ -1560,7 +1624,7 @@ static void queue_inv(bfir_engine *e, Path p, const Chunk &c, hipStream_t st)
     } else {
         a.dst = e->tout; a.dst_ch_stride = (long)e->chunk * e->L; a.n_ch = e->GC;
     }
-    launch_inv(e->plan, a, st);
+    queue_transform_inv(e, a, st);
 }
 
 // staging path, after the inverse transform: planar tout -> raw frames + overflow statistics (+ dither)
@@ -1603,9 +1667,9 @@ static void queue_inv_fade(bfir_engine *e, const Chunk &c, hipStream_t st)
         a.in_scale = e->out_scale; a.full_output = 0; a.interleaved = e->ilv;
         a.dst_ch_stride = t_stride;
         a.src = c.Y; a.src_ch_stride = (long)e->chunk * e->N; a.dst = e->ft[0];
-        launch_inv(e->plan, a, st);
+        queue_transform_inv(e, a, st);
         a.src = c.Y2; a.src_ch_stride = c.y2_ch_stride; a.dst = e->ft[1];
-        launch_inv(e->plan, a, st);
+        queue_transform_inv(e, a, st);
         FadeBlendArgs b;
         b.y_old = e->ft[0]; b.y_new = e->ft[1]; b.ch_stride = t_stride;
         b.n_ch = e->GCo; b.n = (long)c.tc * e->L;
@@ -2434,6 +2498,10 @@ static int run_call(bfir_engine *e, const void *d_in, long in_stride, void *d_ou
     return run_blocks(e, d_in, in_stride, d_out, out_stride, 0, n, block_base, st, input_ready);
 }
 
+// What the work buffers of a big engine's default chunk may take: the delay line, both Yb and the three time buffers.
+// Its blocks are long, so launches of a few hundred of them already fill the GPU; bfir_engine_set_chunk can ask for more.
+static constexpr size_t kBigWorkBytes = 8ull << 30;
+
 static int ensure_chunk(bfir_engine *e, int n_blocks)
 {
     // automatic: as many blocks per launch as give a launch the work of 4096 blocks of the 8-channel, 4096-sample
@@ -2460,7 +2528,23 @@ static int ensure_chunk(bfir_engine *e, int n_blocks)
     // launch's length is its run time: bound it (64 blocks: the serial walk stays in the milliseconds and the
     // other kernels of the pipeline get the GPU in between; integer outputs are off the measured path)
     if (e->d_dither_tab) limit = std::min(limit, 64);
+    if (e->big && e->want_chunk <= 0) {
+        // a chunk of c blocks holds 2 c + B delay-line slots, two Yb of c spectra (4 c + B spectra of N reals) and three time
+        // buffers of c blocks of L reals (1.5 c spectra): the most blocks that keep all of them within kBigWorkBytes
+        const long spectra = (long)(kBigWorkBytes / ((size_t)e->GC * cbuf_bytes(e)));
+        limit = (int)std::max(1L, std::min((long)limit, (2 * (spectra - e->B)) / 11));
+    }
     const int want = std::max(1, std::min(limit, n_blocks));
+    if (e->big && want > e->chunk) {
+        // the MAC kernels and the transforms index one channel's delay line and products with 32-bit element counts here
+        // and there, and launch_mac / launch_*_big would skip a launch whose grid does not fit: refused before anything
+        // is allocated or queued
+        const unsigned long long ring = 2ull * want + e->B;
+        if (ring * (unsigned long long)e->N >= (1ull << 31) || !big_launch_fits(e->bplan, want, e->GC)) {
+            bfir_logf("bfir engine: %d blocks of %d per launch are past the kernels' 32-bit indexing.", want, e->L);
+            return BFIR_ERR_UNSUPPORTED;
+        }
+    }
     if (want > e->chunk) {
         const int rc = alloc_work(e, want);
         if (rc != BFIR_OK || !e->nup) return rc;

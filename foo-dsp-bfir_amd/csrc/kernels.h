@@ -213,6 +213,25 @@ struct InvArgs {
 };
 void launch_inv(const FftPlan &plan, const InvArgs &a, hipStream_t s);
 
+// Long partitions (bigconv.hip): the real FFT of N = 2L reals, L = M1 M2 = 2^15 .. 2^20 (fp64: from 2^14), in two passes
+// per direction over the workgroup FFTs of M1 and M2 points.  Spectra are in TRANSPOSED bin order -- bin k1 + M1 k2 at
+// position k1 M2 + k2, bin 0 (DC | Nyquist) at position 0 -- in either layout of FwdArgs.interleaved.
+struct BigPlan {
+    int log2m = 0, log2m1 = 0, log2m2 = 0;   // M = M1 M2 complex points: columns of M1, rows of M2
+    int realsize = 0;
+    FftPlan p1, p2;                          // the column and the row transform
+    void *t_hi = nullptr, *t_lo = nullptr;   // exp(-2 pi i j / M) = t_hi[j >> 10] t_lo[j & 1023]
+    void *s_hi = nullptr, *s_lo = nullptr;   // exp(-2 pi i k / N) likewise: the split twiddles
+};
+bool big_split(int filter_length, int realsize, int *log2m1, int *log2m2);   // false: not a length the big kernels take
+int  big_plan_create(BigPlan *plan, int filter_length, int realsize);         // 0, -1 (unsupported) or -2 (HIP)
+void big_plan_destroy(BigPlan *plan);
+bool big_launch_fits(const BigPlan &plan, int n_t, int n_ch);                 // the grids of such a launch fit
+// The planar forms only (raw_bytes == 0, full_output == 0).  launch_fwd_big works in place on the delay-line slots;
+// launch_inv_big CONSUMES a.src (its row pass leaves the half-transformed data there for the column pass).
+void launch_fwd_big(const BigPlan &plan, const FwdArgs &a, hipStream_t s);
+void launch_inv_big(const BigPlan &plan, const InvArgs &a, hipStream_t s);
+
 // Pair path (pair.hip): two adjacent channels per complex transform, straight from / to interleaved
 // FLOAT_LE frames; fp32, even channel count, 512 <= L <= 8192.  `plan` is the plan of 2L points.
 bool pair_supported(int filter_length);

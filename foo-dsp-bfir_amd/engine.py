@@ -266,6 +266,28 @@ class Brutefir:
         return dst
 
 
+class BrutefirBig(Brutefir):
+    """Brutefir on long partitions (bfir_engine_create_big): filter_length 32768 ... 1048576 (realsize 8: from 16384), the
+    lengths past one workgroup's transform.  One engine; everything else is Brutefir's -- every sample format, dither,
+    set_coeff, set_coeff_fade, the delays, coeff_block in the reference's layout and natural bin order."""
+
+    def __init__(self, filter_length, filter_blocks, realsize, channels,
+                 in_format=None, out_format=None, sampling_rate=44100, apply_dither=False, device=0):
+        dflt = SAMPLE_FORMAT_FLOAT_LE if realsize == 4 else SAMPLE_FORMAT_FLOAT64_LE
+        self.L, self.B, self.s, self.C = filter_length, filter_blocks, realsize, channels
+        self.in_format = dflt if in_format is None else in_format
+        self.out_format = dflt if out_format is None else out_format
+        self.n_engines, self.device = 1, device
+        self.sampling_rate = sampling_rate
+        self._lib = _lib.load()
+        err = C.c_int(0)
+        self._h = self._lib.bfir_engine_create_big(
+            filter_length, filter_blocks, realsize, channels, self.in_format,
+            self.out_format, sampling_rate, int(bool(apply_dither)), device, C.byref(err))
+        if not self._h:
+            raise BfirError(err.value, "bfir_engine_create_big")
+
+
 class BrutefirMatrix(Brutefir):
     """n_in inputs -> n_out outputs with one filter per (output, input) pair (bfir_engine_create_matrix):
     y_o = sum_i h_{o,i} * x_i.  Frames are FLOAT_LE or FLOAT64_LE; the default is the working precision's.

@@ -27,6 +27,20 @@ public:
         m_err = err;
         memset(m_last, 0, sizeof(m_last));
     }
+    // Long partitions (bfir_engine_create_big): filter_blocks partitions of 32768 ... 1048576 samples (realsize 8: from
+    // 16384), the lengths past bfir_engine_create's.  Everything else is the first constructor's: every sample format, dither,
+    // both set_coeff overloads.
+    struct long_partitions { int filter_blocks; };
+    brutefir(int filter_length, long_partitions big, int realsize, int channels, int in_format, int out_format,
+             int sampling_rate, bool apply_dither, int device = 0)
+        : m_channels(channels), m_filter_length(filter_length), m_realsize(realsize), m_rate(sampling_rate)
+    {
+        int err = 0;
+        m_e = bfir_engine_create_big(filter_length, big.filter_blocks, realsize, channels, in_format, out_format,
+                                     sampling_rate, apply_dither ? 1 : 0, device, &err);
+        m_err = err;
+        memset(m_last, 0, sizeof(m_last));
+    }
     // Two partition lengths (bfir_engine_create_nup): taps [0, head_blocks * filter_length) on partitions of filter_length,
     // the rest on tail_blocks partitions of tail_ratio * filter_length; run() keeps its filter_length-frame blocks.
     // Float frames only, no dither.  Coefficients: the set_coeff(coeffs, n_coeffs, length, scale) overload.

@@ -118,6 +118,22 @@ bfir_engine *bfir_engine_create_batch(int n_engines, int filter_length, int filt
                                       int realsize, int channels, int in_format, int out_format,
                                       int sampling_rate, int apply_dither, int device, int *err);
 
+/* Long partitions ("big" engines): a diagonal engine whose partition does not fit one workgroup's transform -- the
+ * playback configurations written as a few partitions of 65536 or more.  filter_length is a power of two, 32768 ...
+ * 1048576 with realsize 4 and 16384 ... 1048576 with realsize 8; a power of two outside that range is
+ * BFIR_ERR_UNSUPPORTED (16 ... 16384 / 8192 are bfir_engine_create's), anything else BFIR_ERR_ARG as there.  One engine
+ * (no batch), 1 <= channels <= BFIR_MAXCHANNELS, all eleven sample formats, HP-TPDF dither with integer outputs.
+ * Every transform runs as two passes over the workgroup FFT (bigconv.hip) and the spectra are kept in a transposed bin
+ * order, which only bfir_engine_read_coeff undoes: it hands out the reference's grouped layout in natural bin order, like
+ * every other kind.  bfir_engine_set_coeff, _set_coeff_at, _read_coeff, run, run_device, sync, reset, get_overflow,
+ * set_chunk, set_profiling, get_profile, is_initialized, destroy, set_coeff_fade, fade_remaining and the delay calls work
+ * on it as on an engine from bfir_engine_create; the matrix, nup and levels calls return BFIR_ERR_UNSUPPORTED.  A launch
+ * (bfir_engine_set_chunk) whose delay line would pass 2^31 samples per channel is refused with BFIR_ERR_UNSUPPORTED
+ * before anything is queued; the default never gets there. */
+bfir_engine *bfir_engine_create_big(int filter_length, int filter_blocks, int realsize, int channels,
+                                    int in_format, int out_format, int sampling_rate, int apply_dither,
+                                    int device, int *err);
+
 /* n_inputs -> n_outputs, one filter per (output, input) pair: output o is the sum over the inputs i of input i
  * convolved with h_{o,i} (a BruteFIR filter graph folded into one matrix).  1 <= n_inputs, n_outputs <=
  * BFIR_MAXCHANNELS.  Frames: n_inputs-channel frames in, n_outputs-channel frames out, FLOAT_LE or FLOAT64_LE each
