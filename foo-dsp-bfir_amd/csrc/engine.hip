@@ -14,8 +14,9 @@
 // side -- Y, the overflow statistics, the output frames -- for its Co outputs; H is [Co][C][B][N], the MAC k_mac_matrix.
 // A run of n blocks is cut into chunks of at most `chunk` blocks.  A chunk is front (fwd; stage_in before it on the
 // staging path), MAC and back (inv; stage_out after it on the staging path), software-pipelined over three streams.
-// What is written once here, because every path shares it: the path an engine takes (choose_path), the filter
-// loader (load_filters) and the chunk schedule (run_chunk: streams, events, the MAC; queue_fwd / queue_inv and the
+// What is written once here, because every path shares it: the path an engine takes (choose_path), the coefficient
+// side (FilterRows: check_rows, load_filters; split engines, diagonal or matrix: set_coeff_split, set_coeff_split_fade)
+// and the chunk schedule (run_chunk: streams, events, the MAC; queue_fwd / queue_inv and the
 // two staging launches are what differs per path).
 #include <hip/hip_runtime.h>
 
@@ -275,6 +276,9 @@ struct bfir_engine {
 };
 
 static size_t cbuf_bytes(const bfir_engine *e) { return (size_t)e->N * (size_t)e->s; }
+
+// level k = 0 .. n_tail of a split engine: the head, then its tails (any other engine is its own level 0)
+static bfir_engine *level(const bfir_engine *e, int k) { return k == 0 ? const_cast<bfir_engine *>(e) : e->tail[k - 1]; }
 
 // everything a delayed side owns (the device is idle)
 static void delay_free(bfir_engine *e, int side)
@@ -837,31 +841,55 @@ static void queue_transform_inv(const bfir_engine *e, const InvArgs &a, hipStrea
     if (e->big) launch_inv_big(e->bplan, a, s); else launch_inv(e->plan, a, s);
 }
 
-// coeff::preprocess_coeff + convolver_coeffs2cbuf for n_rows filters, rows row0 .. of H: coeffs[n] (n < n_coeffs <= n_rows)
-// goes to row row0 + n, nb partitions each.  A NULL entry is an error (null_ok = false) or an all-zero filter, as are the
-// rows past n_coeffs.  Nothing is uploaded before every filter has passed the finite check.  Hdst: the filter buffer that
-// takes them, H or (a fade's second set) H2.  lengths: the tap count of every filter where they differ (a filter without
-// taps is one without a path); else all have `length`.
-static int load_filters(bfir_engine *e, void *Hdst, int row0, int n_rows, const void *const *coeffs, int n_coeffs, int length, int nb,
-                        double scale, bool null_ok, const int *lengths = nullptr)
+// The filters of one set call as the rows of H they go to: the C channels of a diagonal engine, or the Co x C pairs of a
+// matrix engine ([o C + i]).  A row without taps is an all-zero filter (a matrix engine: no path from input i to output o).
+namespace {
+struct FilterRows {
+    std::vector<const void *> taps;
+    std::vector<int> len;        // the tap count of every row
+    int n_required = 0;          // a NULL among the first so many rows is BFIR_ERR_ARG: the n_coeffs of a diagonal engine
+    explicit FilterRows(size_t n_rows = 0) : taps(n_rows), len(n_rows) {}
+};
+}
+
+// coeffs[n] (n < n_coeffs) for channel n, all of `length` taps; the channels past n_coeffs get zeros
+static FilterRows diagonal_rows(const bfir_engine *e, const void *const *coeffs, int n_coeffs, int length)
 {
-    const size_t taps_pad = (size_t)nb * e->L;
-    const size_t cb = cbuf_bytes(e);
-    const size_t cnt = std::min((size_t)length, taps_pad);
-    // zero padded impulse per filter; a block past the end is all zero
-    // (coeff.cpp:315-339), taps are scaled in working precision (fftw_convolver.cpp:491,507)
-    std::vector<char> host((size_t)n_rows * taps_pad * e->s, 0);
-    for (int n = 0; n < n_coeffs; n++) {
-        if (!coeffs[n] || (lengths && lengths[n] <= 0)) { if (null_ok) continue; return BFIR_ERR_ARG; }
-        const size_t cnt_n = lengths ? std::min((size_t)lengths[n], taps_pad) : cnt;
+    FilterRows r((size_t)e->C);
+    r.n_required = std::min(n_coeffs, e->C);                    // brutefir.cpp:190-193
+    for (int n = 0; n < r.n_required; n++) r.taps[n] = coeffs[n];
+    for (int &len : r.len) len = length;
+    return r;
+}
+
+// coeffs[o n_in + i], NULL = no path; every filter of its own length (a NULL has none), or all of `length` taps
+static FilterRows matrix_rows(const bfir_engine *e, const void *const *coeffs, const int *lengths, int length)
+{
+    const int P = e->Co * e->C;                                 // filters, [o][i]
+    FilterRows r((size_t)P);
+    for (int n = 0; n < P; n++) {
+        r.taps[n] = coeffs[n];
+        r.len[n] = !lengths ? length : coeffs[n] ? lengths[n] : 0;
+    }
+    return r;
+}
+
+// coeff::preprocess_coeff's finite check over the first max_taps taps of every row (what the call loads), scaled in
+// working precision (fftw_convolver.cpp:491,507).  Every entry point calls it once, before its first upload: a NaN / Inf
+// tap anywhere is refused before anything is uploaded at any level.
+static int check_rows(const bfir_engine *e, const FilterRows &r, size_t max_taps, double scale)
+{
+    for (int n = 0; n < (int)r.taps.size(); n++) {
+        if (!r.taps[n]) { if (n < r.n_required) return BFIR_ERR_ARG; continue; }
+        const size_t cnt = std::min((size_t)r.len[n], max_taps);
         bool finite = true;
         if (e->s == 4) {
-            const float *src = (const float *)coeffs[n];
+            const float *src = (const float *)r.taps[n];
             const float sc = (float)scale;
-            for (size_t i = 0; i < cnt_n; i++) finite &= std::isfinite((double)(src[i] * sc));
+            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite((double)(src[i] * sc));
         } else {
-            const double *src = (const double *)coeffs[n];
-            for (size_t i = 0; i < cnt_n; i++) finite &= std::isfinite(src[i] * scale);
+            const double *src = (const double *)r.taps[n];
+            for (size_t i = 0; i < cnt; i++) finite &= std::isfinite(src[i] * scale);
         }
         if (!finite) {
             bfir_logf("NaN or Inf value among coefficients.");
@@ -869,8 +897,22 @@ static int load_filters(bfir_engine *e, void *Hdst, int row0, int n_rows, const 
             else bfir_logf("Error preprocessing coefficient %d", n);
             return BFIR_ERR_COEFF;
         }
-        memcpy(host.data() + (size_t)n * taps_pad * e->s, coeffs[n], cnt_n * e->s);
     }
+    return BFIR_OK;
+}
+
+// convolver_coeffs2cbuf for the rows of a call that has passed check_rows: row n goes to row row0 + n of Hdst, nb
+// partitions each.  Hdst: the filter buffer that takes them, H or (a fade's second set) H2.
+static int load_filters(bfir_engine *e, void *Hdst, int row0, const FilterRows &r, int nb, double scale)
+{
+    const int n_rows = (int)r.taps.size();
+    const size_t taps_pad = (size_t)nb * e->L;
+    const size_t cb = cbuf_bytes(e);
+    // zero padded impulse per filter; a block past the end is all zero (coeff.cpp:315-339)
+    std::vector<char> host((size_t)n_rows * taps_pad * e->s, 0);
+    for (int n = 0; n < n_rows; n++)
+        if (r.taps[n] && r.len[n] > 0)
+            memcpy(host.data() + (size_t)n * taps_pad * e->s, r.taps[n], std::min((size_t)r.len[n], taps_pad) * e->s);
     void *d_taps = nullptr;
     void *rows = (char *)Hdst + (size_t)row0 * e->B * cb;
     HIP_TRY(hipMalloc(&d_taps, host.size()));
@@ -906,10 +948,11 @@ extern "C" int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const 
     HIP_TRY(hipDeviceSynchronize());
     e->fade_len = e->fade_pos = 0;                              // a plain change during a fade cancels it: a hard cut, as ever
     e->eng_init[engine_index] = 0;                              // free_coeff(), brutefir.cpp:188
-    if (n_coeffs > e->C) n_coeffs = e->C;                       // brutefir.cpp:190-193
     const int nb = std::min(coeff_blocks, e->B);                // run() never looks past B blocks
     const int gc0 = engine_index * e->C;
-    const int rc = load_filters(e, e->H, gc0, e->C, coeffs, n_coeffs, length, nb, scale, false);
+    const FilterRows rows = diagonal_rows(e, coeffs, n_coeffs, length);
+    int rc = check_rows(e, rows, (size_t)nb * e->L, scale);
+    if (rc == BFIR_OK) rc = load_filters(e, e->H, gc0, rows, nb, scale);
     if (rc != BFIR_OK) return rc;
     for (int n = 0; n < e->C; n++) e->nblk[gc0 + n] = nb;
     HIP_TRY(hipMemcpy(e->d_nblk + gc0, e->nblk.data() + gc0, sizeof(int) * e->C, hipMemcpyHostToDevice));
@@ -945,70 +988,14 @@ static int level_start(bfir_engine *e, int i)
     return BFIR_OK;
 }
 
-// The filters of a two-level or multi-level engine, split at every D_k: taps [0, D_1) to the head, [D_k, D_(k+1)) to level
-// k.  Mid-stream every delay line is kept: the head takes the new filters from the next block, level k from its next
-// block that completes; what a level has already put into its time ring still plays.
-static int set_coeff_split(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
-{
-    long long cap = (long long)e->B * e->L;
-    for (int i = 0; i < e->n_tail; i++) cap += (long long)e->tail[i]->B * e->tail[i]->L;
-    if (!coeffs || n_coeffs < 0 || length < 0 || (long long)length > cap) return BFIR_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (e->fade_len > 0) { e->fade_len = e->fade_pos = 0; lfade_finish(e, false); }   // a plain change during a fade cancels it: a hard cut
-    e->eng_init[0] = 0;
-    if (n_coeffs > e->C) n_coeffs = e->C;
-    const int len_h = (int)std::min<long long>(length, (long long)e->B * e->L);
-    const int nb_h = std::min(e->B, std::max(1, (len_h + e->L - 1) / e->L));
-    int rc = load_filters(e, e->H, 0, e->C, coeffs, n_coeffs, len_h, nb_h, scale, false);
-    if (rc != BFIR_OK) return rc;
-    int len_lv[BFIR_MAX_LEVELS - 1], nb_lv[BFIR_MAX_LEVELS - 1];
-    for (int i = 0; i < e->n_tail; i++) {
-        bfir_engine *t = e->tail[i];
-        const long long D = (long long)e->lv_D[i] * e->L;
-        const int len_t = len_lv[i] = (int)std::max(0ll, std::min((long long)length - D, (long long)t->B * t->L));
-        nb_lv[i] = len_t > 0 ? std::min(t->B, (len_t + t->L - 1) / t->L) : 0;
-        if (len_t > 0) {
-            std::vector<const void *> rest((size_t)n_coeffs);
-            for (int n = 0; n < n_coeffs; n++) rest[n] = (const char *)coeffs[n] + (size_t)D * e->s;
-            rc = load_filters(t, t->H, 0, t->C, rest.data(), n_coeffs, len_t, nb_lv[i], scale, false);
-            if (rc != BFIR_OK) return rc;
-        }
-    }
-    for (int n = 0; n < e->C; n++) e->nblk[n] = nb_h;
-    HIP_TRY(hipMemcpy(e->d_nblk, e->nblk.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
-    for (int i = 0; i < e->n_tail; i++) {
-        bfir_engine *t = e->tail[i];
-        for (int n = 0; n < e->C; n++) t->nblk[n] = nb_lv[i];
-        HIP_TRY(hipMemcpy(t->d_nblk, t->nblk.data(), sizeof(int) * t->C, hipMemcpyHostToDevice));
-        if (len_lv[i] > 0 && !e->lv_active[i]) { rc = level_start(e, i); if (rc != BFIR_OK) return rc; }
-        e->lv_active[i] = len_lv[i] > 0;
-        t->eng_init[0] = 1;
-    }
-    e->eng_init[0] = 1;
-    return BFIR_OK;
-}
-
-extern "C" int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
-{
-    if (!e) return BFIR_ERR_ARG;
-    if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
-    return set_coeff_split(e, coeffs, n_coeffs, length, scale);
-}
-
-extern "C" int bfir_engine_set_coeff_levels(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
-{
-    if (!e) return BFIR_ERR_ARG;
-    if (!e->levels) return BFIR_ERR_UNSUPPORTED;
-    return set_coeff_split(e, coeffs, n_coeffs, length, scale);
-}
-
-// does every input of a matrix engine feed some output under these partition counts ([o C + i])?
-static bool every_input_read(const bfir_engine *e, const std::vector<int> &nblk)
+// Does every input of a matrix engine feed some output?  It does if any filter of its column has taps on any level:
+// count(k, n) is the partition count of filter n = o C + i on level k (a uniform engine has the one level).
+template <class Count> static bool every_input_read(const bfir_engine *e, Count count)
 {
     for (int i = 0; i < e->C; i++) {
         bool read = false;
-        for (int o = 0; o < e->Co; o++) read = read || nblk[o * e->C + i] > 0;
+        for (int o = 0; o < e->Co; o++)
+            for (int k = 0; k <= e->n_tail; k++) read = read || count(k, o * e->C + i) > 0;
         if (!read) return false;
     }
     return true;
@@ -1035,98 +1022,137 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
     HIP_TRY(hipDeviceSynchronize());
     e->fade_len = e->fade_pos = 0;                              // a plain change during a fade cancels it
     e->eng_init[0] = 0;
-    const int P = e->Co * e->C;                                 // filters, [o][i]
     const int nb = std::min(coeff_blocks, e->B);
-    const int rc = load_filters(e, e->H, 0, P, coeffs, P, length, nb, scale, true);
+    const FilterRows rows = matrix_rows(e, coeffs, nullptr, length);
+    int rc = check_rows(e, rows, (size_t)nb * e->L, scale);
+    if (rc == BFIR_OK) rc = load_filters(e, e->H, 0, rows, nb, scale);
     if (rc != BFIR_OK) return rc;
-    for (int n = 0; n < P; n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
-    if (e->pair_cap) matrix_take_path(e, every_input_read(e, e->nblk));
+    for (size_t n = 0; n < rows.taps.size(); n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
+    if (e->pair_cap) matrix_take_path(e, every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
     e->eng_init[0] = 1;
     return BFIR_OK;
 }
 
-// The n_out x n_in filters of a multi-level matrix engine, each of its own length, split at every D_k as set_coeff_split
-// splits them: level k gets taps [D_k, D_(k+1)) of every filter that reaches past D_k, with that filter's own partition
-// count (0: skipped on that level, never multiplied by zero).  Mid-stream the rules of set_coeff_split hold per level.
+// The rows of a set call on a split engine, cut at every D_k: level k (0: the head) gets taps [D_k, D_(k+1)) of every row
+// that reaches past D_k.  Host arithmetic alone: neither the device nor the engine's state is touched.
+namespace {
+struct LevelSplit {
+    struct Level {
+        FilterRows rows;         // the part of every row that falls into the level (a row without taps there: none)
+        std::vector<int> nb;     // the row's partitions there
+        int nb_max = 0;          // 0: the set does not reach the level
+    } lv[BFIR_MAX_LEVELS];
+};
+}
+
+// A filter of a matrix engine has ceil(len / L_k) partitions on level k, its own count (0: skipped on that level, never
+// multiplied by zero).  The channels of a diagonal engine all get the level's count, the zero rows past n_coeffs too, and
+// on the head at least one partition.
+static LevelSplit split_rows(const bfir_engine *e, const FilterRows &r)
+{
+    LevelSplit sp;
+    const size_t n_rows = r.taps.size();
+    for (int k = 0; k <= e->n_tail; k++) {
+        const bfir_engine *l = level(e, k);
+        LevelSplit::Level &s = sp.lv[k];
+        const long long D = k == 0 ? 0 : (long long)e->lv_D[k - 1] * e->L;
+        s.rows = FilterRows(n_rows); s.nb.assign(n_rows, 0);
+        for (size_t n = 0; n < n_rows; n++) {
+            const int len = (int)std::max(0ll, std::min((long long)r.len[n] - D, (long long)l->B * l->L));
+            s.rows.len[n] = len;
+            if (len > 0 && r.taps[n]) s.rows.taps[n] = (const char *)r.taps[n] + (size_t)D * e->s;
+            s.nb[n] = (len + l->L - 1) / l->L;
+            s.nb_max = std::max(s.nb_max, s.nb[n]);
+        }
+        if (!e->matrix) { s.nb_max = std::max(s.nb_max, k == 0 ? 1 : 0); s.nb.assign(n_rows, s.nb_max); }
+    }
+    return sp;
+}
+
+// what the set calls of a split engine ask of the lengths: none negative, none past the taps its levels hold
+static int check_split_lengths(const bfir_engine *e, const FilterRows &r)
+{
+    long long cap = 0;
+    for (int k = 0; k <= e->n_tail; k++) cap += (long long)level(e, k)->B * level(e, k)->L;
+    for (int len : r.len) if (len < 0 || (long long)len > cap) return BFIR_ERR_ARG;
+    return BFIR_OK;
+}
+
+// The filters of a two-level, multi-level or multi-level matrix engine, split at every D_k: taps [0, D_1) to the head,
+// [D_k, D_(k+1)) to level k.  Mid-stream every delay line is kept: the head takes the new filters from the next block,
+// level k from its next block that completes; what a level has already put into its time ring still plays.
+static int set_coeff_split(bfir_engine *e, const FilterRows &rows, double scale)
+{
+    int rc = check_split_lengths(e, rows);
+    if (rc != BFIR_OK) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (e->fade_len > 0) { e->fade_len = e->fade_pos = 0; lfade_finish(e, false); }   // a plain change during a fade cancels it: a hard cut
+    e->eng_init[0] = 0;
+    rc = check_rows(e, rows, SIZE_MAX, scale);
+    if (rc != BFIR_OK) return rc;
+    const LevelSplit sp = split_rows(e, rows);
+    // the head, then level after level: the part of every filter that falls into the level and its partitions there
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = level(e, k);
+        const LevelSplit::Level &s = sp.lv[k];
+        if (s.nb_max > 0) {   // a level on which no filter has taps does no work at all (a matrix head: its MAC stores zeros)
+            rc = load_filters(l, l->H, 0, s.rows, s.nb_max, scale);
+            if (rc != BFIR_OK) return rc;
+        }
+        l->nblk = s.nb;
+        // the matrix MAC takes the counts by value (MatArgs.nblk)
+        if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
+    }
+    for (int i = 0; i < e->n_tail; i++) {
+        const bool active = sp.lv[i + 1].nb_max > 0;
+        if (active && !e->lv_active[i]) { rc = level_start(e, i); if (rc != BFIR_OK) return rc; }
+        e->lv_active[i] = active;
+        e->tail[i]->eng_init[0] = 1;
+    }
+    if (e->matrix) {
+        // An input is read if any filter of its column has taps on any level; while one is not, no level pairs channels (a
+        // pair is ONE transform: a NaN on the unread input would reach the spectra of its partner)
+        const bool all_read = every_input_read(e, [&](int k, int n) { return sp.lv[k].nb[n]; });
+        for (int i = 0; i < e->n_tail; i++) if (e->tail[i]->pair_cap) matrix_take_path(e->tail[i], all_read);
+        // While no level beyond the head has taps the engine IS bfir_engine_create_matrix(L, blocks[0], ...) and takes its path,
+        // which pairs channels only with an even count on both sides: so it gives that engine's bytes
+        bool any_tail = false;
+        for (int i = 0; i < e->n_tail; i++) any_tail = any_tail || e->lv_active[i];
+        if (e->pair_cap) {
+            if (all_read && !any_tail && (e->Co & 1)) {
+                if (e->pair) bfir_logf("bfir matrix engine: no level beyond the head has taps: path=direct from the next block on.");
+                e->pair = false; e->direct = true;
+            } else matrix_take_path(e, all_read);
+        }
+    }
+    e->eng_init[0] = 1;
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || n_coeffs < 0) return BFIR_ERR_ARG;
+    return set_coeff_split(e, diagonal_rows(e, coeffs, n_coeffs, length), scale);
+}
+
+extern "C" int bfir_engine_set_coeff_levels(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->levels) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || n_coeffs < 0) return BFIR_ERR_ARG;
+    return set_coeff_split(e, diagonal_rows(e, coeffs, n_coeffs, length), scale);
+}
+
+// The n_out x n_in filters of a multi-level matrix engine, each of its own length: coeffs[o n_in + i], NULL = no path
 extern "C" int bfir_engine_set_coeff_matrix_levels(bfir_engine *e, const void *const *coeffs, const int *lengths, double scale)
 {
     if (!e) return BFIR_ERR_ARG;
     if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
     if (!coeffs || !lengths) return BFIR_ERR_ARG;
-    const int P = e->Co * e->C;                                 // filters, [o][i]
-    long long cap = (long long)e->B * e->L;
-    for (int i = 0; i < e->n_tail; i++) cap += (long long)e->tail[i]->B * e->tail[i]->L;
-    for (int n = 0; n < P; n++)
-        if (coeffs[n] && (lengths[n] < 0 || (long long)lengths[n] > cap)) return BFIR_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (e->fade_len > 0) { e->fade_len = e->fade_pos = 0; lfade_finish(e, false); }   // a plain change during a fade cancels it: a hard cut
-    e->eng_init[0] = 0;
-    // a NaN / Inf tap anywhere is refused before anything is uploaded at any level
-    for (int n = 0; n < P; n++) {
-        if (!coeffs[n]) continue;
-        bool finite = true;
-        if (e->s == 4) {
-            const float *src = (const float *)coeffs[n];
-            const float sc = (float)scale;
-            for (int i = 0; i < lengths[n]; i++) finite &= std::isfinite((double)(src[i] * sc));
-        } else {
-            const double *src = (const double *)coeffs[n];
-            for (int i = 0; i < lengths[n]; i++) finite &= std::isfinite(src[i] * scale);
-        }
-        if (!finite) {
-            bfir_logf("NaN or Inf value among coefficients.");
-            bfir_logf("Error preprocessing coefficient %d (output %d, input %d)", n, n / e->C, n % e->C);
-            return BFIR_ERR_COEFF;
-        }
-    }
-    // the head, then level after level: the part of every filter that falls into the level and its partitions there
-    bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
-    std::vector<const void *> part((size_t)P);
-    std::vector<int> len((size_t)P);
-    bool active[BFIR_MAX_LEVELS] = {false, false, false, false};
-    for (int k = 0; k <= e->n_tail; k++) {
-        bfir_engine *l = lv[k];
-        const long long D = k == 0 ? 0 : (long long)e->lv_D[k - 1] * e->L;
-        int nb_max = 0;
-        for (int n = 0; n < P; n++) {
-            const long long rest = coeffs[n] ? std::min((long long)lengths[n] - D, (long long)l->B * l->L) : 0;
-            len[n] = (int)std::max(0ll, rest);
-            part[n] = len[n] > 0 ? (const char *)coeffs[n] + (size_t)D * e->s : nullptr;
-            l->nblk[n] = (len[n] + l->L - 1) / l->L;
-            nb_max = std::max(nb_max, l->nblk[n]);
-        }
-        active[k] = nb_max > 0;
-        if (nb_max > 0) {   // a level on which no filter has taps does no work at all (the head: its MAC stores zeros)
-            const int rc = load_filters(l, l->H, 0, P, part.data(), P, 0, nb_max, scale, true, len.data());
-            if (rc != BFIR_OK) return rc;
-        }
-    }
-    for (int i = 0; i < e->n_tail; i++) {
-        if (active[i + 1] && !e->lv_active[i]) { const int rc = level_start(e, i); if (rc != BFIR_OK) return rc; }
-        e->lv_active[i] = active[i + 1];
-        e->tail[i]->eng_init[0] = 1;
-    }
-    // An input is read if any filter of its column has taps on any level; while one is not, no level pairs channels (a
-    // pair is ONE transform: a NaN on the unread input would reach the spectra of its partner)
-    bool all_read = true;
-    for (int i = 0; i < e->C; i++) {
-        bool read = false;
-        for (int o = 0; o < e->Co; o++) read = read || (coeffs[o * e->C + i] && lengths[o * e->C + i] > 0);
-        all_read = all_read && read;
-    }
-    for (int i = 0; i < e->n_tail; i++) if (e->tail[i]->pair_cap) matrix_take_path(e->tail[i], all_read);
-    // While no level beyond the head has taps the engine IS bfir_engine_create_matrix(L, blocks[0], ...) and takes its path,
-    // which pairs channels only with an even count on both sides: so it gives that engine's bytes
-    const bool any_tail = active[1] || active[2] || active[3];
-    if (e->pair_cap) {
-        if (all_read && !any_tail && (e->Co & 1)) {
-            if (e->pair) bfir_logf("bfir matrix engine: no level beyond the head has taps: path=direct from the next block on.");
-            e->pair = false; e->direct = true;
-        } else matrix_take_path(e, all_read);
-    }
-    e->eng_init[0] = 1;
-    return BFIR_OK;
+    return set_coeff_split(e, matrix_rows(e, coeffs, lengths, 0), scale);
 }
 
 // ---------------------------------------------------------------------------
@@ -1169,44 +1195,73 @@ static void fade_swap_sets(bfir_engine *e)
     if (e->nup) lfade_finish(e, true);
 }
 
-// rows: the filters of the call (C of a diagonal engine, Co x C of a matrix engine)
+// what every fade call asks of fade_blocks and of the engine's state
+static int check_fade_args(const bfir_engine *e, int fade_blocks)
+{
+    // m = 0 .. K L - 1 must be exact as a float (fftw_convolver.cpp:302 multiplies by (float)n)
+    if (fade_blocks < 1 || (long long)fade_blocks * e->L > (1ll << 24)) return BFIR_ERR_ARG;
+    if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
+    return BFIR_OK;
+}
+
+// What a fade needs beside the active set, allocated at the first fade: on every level (a uniform engine: itself) H2 for
+// n_rows filters with its counts, on a tail the second ring; and which back end the fade takes.  The device is idle.
+static int fade_prepare(bfir_engine *e, int n_rows)
+{
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = level(e, k);
+        if (l->H2) continue;
+        HIP_TRY(hipMalloc(&l->H2, (size_t)n_rows * l->B * cbuf_bytes(l)));
+        HIP_TRY(hipMalloc((void **)&l->d_nblk2, sizeof(int) * l->GC));   // not read by the matrix MAC; swapped with d_nblk
+    }
+    for (int i = 0; i < e->n_tail; i++) {
+        bfir_engine *t = e->tail[i];
+        if (!t->zring2) HIP_TRY(hipMalloc(&t->zring2, (size_t)t->GCo * t->zblocks * t->L * t->s));
+    }
+    e->fade_fused = e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L);
+    // direct / staging engines (a split engine: an odd channel count) have none yet
+    if (e->fade_fused && !e->plan2.tw && fft_plan_create(&e->plan2, 2 * e->L, 4) != 0) return BFIR_ERR_HIP;
+    return BFIR_OK;
+}
+
+// the fade is the next fade_blocks blocks the engine processes
+static void fade_begin(bfir_engine *e, int fade_blocks)
+{
+    e->fade_f = (float)(1.0 / (double)(float)(fade_blocks * e->L - 1));
+    e->fade_d = 1.0 / (double)(fade_blocks * e->L - 1);
+    e->fade_len = fade_blocks; e->fade_pos = 0;
+}
+
+// a uniform engine, diagonal (coeffs[n] for channel n < n_coeffs) or matrix (coeffs[o n_in + i], NULL = no path)
 static int set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, int coeff_blocks, double scale,
                           int fade_blocks)
 {
     if (e->n_eng > 1 || e->d_dither_tab) return BFIR_ERR_UNSUPPORTED;   // batches; HP-TPDF dither (a recursion over the output samples)
     if (e->nup) return BFIR_ERR_UNSUPPORTED;                            // two-level engines do not fade
     if (!coeffs || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
-    // m = 0 .. K L - 1 must be exact as a float (:302 multiplies by (float)n)
-    if (fade_blocks < 1 || (long long)fade_blocks * e->L > (1ll << 24)) return BFIR_ERR_ARG;
-    if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
+    int rc = check_fade_args(e, fade_blocks);
+    if (rc != BFIR_OK) return rc;
+    const int nb = std::min(coeff_blocks, e->B);
+    const FilterRows rows = e->matrix ? matrix_rows(e, coeffs, nullptr, length) : diagonal_rows(e, coeffs, n_coeffs, length);
+    // a NaN / Inf tap is refused before anything is uploaded: the engine keeps running the old set
+    rc = check_rows(e, rows, (size_t)nb * e->L, scale);
+    if (rc != BFIR_OK) return rc;
     HIP_TRY(hipSetDevice(e->device));
     // queued work may still read what was H before the last fade's swap: H2 is written only when the device is idle
     HIP_TRY(hipDeviceSynchronize());
-    const size_t cb = cbuf_bytes(e);
-    const int n_rows = e->matrix ? e->Co * e->C : e->C;
-    if (!e->H2) {
-        HIP_TRY(hipMalloc(&e->H2, (size_t)n_rows * e->B * cb));
-        HIP_TRY(hipMalloc((void **)&e->d_nblk2, sizeof(int) * e->GC));
-    }
-    e->fade_fused = e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L);
-    if (e->fade_fused && !e->plan2.tw && fft_plan_create(&e->plan2, 2 * e->L, 4) != 0) return BFIR_ERR_HIP;   // direct / staging engines have none yet
-    const int nb = std::min(coeff_blocks, e->B);
-    if (!e->matrix && n_coeffs > e->C) n_coeffs = e->C;
-    // a NaN / Inf tap is refused before anything is uploaded: the engine keeps running the old set
-    const int rc = load_filters(e, e->H2, 0, n_rows, coeffs, e->matrix ? n_rows : n_coeffs, length, nb, scale, e->matrix);
+    rc = fade_prepare(e, (int)rows.taps.size());
+    if (rc == BFIR_OK) rc = load_filters(e, e->H2, 0, rows, nb, scale);
     if (rc != BFIR_OK) return rc;
     e->nblk2.assign(e->nblk.size(), 0);
-    for (int n = 0; n < n_rows; n++) e->nblk2[n] = (e->matrix && !coeffs[n]) ? 0 : nb;
+    for (size_t n = 0; n < rows.taps.size(); n++) e->nblk2[n] = (e->matrix && !coeffs[n]) ? 0 : nb;
     if (!e->matrix) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
     if (e->matrix && e->pair_cap) {
         // no channel pairs around an unread input, per set: the fade's forward transforms take the pair path only if every
         // input is read under BOTH sets; after the fade the new set decides
-        e->pair_new = every_input_read(e, e->nblk2);
-        matrix_take_path(e, e->pair_new && every_input_read(e, e->nblk));
+        e->pair_new = every_input_read(e, [&](int, int n) { return e->nblk2[n]; });
+        matrix_take_path(e, e->pair_new && every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
     }
-    e->fade_f = (float)(1.0 / (double)(float)(fade_blocks * e->L - 1));
-    e->fade_d = 1.0 / (double)(fade_blocks * e->L - 1);
-    e->fade_len = fade_blocks; e->fade_pos = 0;
+    fade_begin(e, fade_blocks);
     return BFIR_OK;
 }
 
@@ -1442,6 +1497,21 @@ static MatArgs matrix_mac_args(const bfir_engine *e, int base_slot, void *Y, int
     a.n_t = tc; a.n_in = e->C; a.n_out = e->Co; a.N = e->N; a.realsize = e->s;
     a.interleaved = e->ilv;
     return a;
+}
+
+// The MAC of tc blocks of an engine, a level included, from delay-line slot base_slot on into Y (y_ch_stride reals per
+// channel) with the active or the second set: k_mac on a diagonal engine, k_mac_matrix on a matrix engine.
+static int queue_mac(const bfir_engine *e, int base_slot, void *Y, long y_ch_stride, int tc, bool second, hipStream_t s)
+{
+    if (!e->matrix) {
+        MacArgs a = mac_args(e, base_slot, Y, tc, second);
+        a.y_ch_stride = y_ch_stride;
+        launch_mac(a, s);
+        return BFIR_OK;
+    }
+    MatArgs a = matrix_mac_args(e, base_slot, Y, tc, second);
+    a.y_ch_stride = y_ch_stride;
+    return launch_mac_matrix(a, s) != 0 ? BFIR_ERR_UNSUPPORTED : BFIR_OK;
 }
 
 // a chunk the matrix MAC cannot take is refused before anything is queued (never skipped)
@@ -1850,15 +1920,9 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
         if (duo) {   // a multi-level matrix engine: both sets in one pass over the delay line
             if (launch_mac_duo(matrix_duo_args(e, c.base_slot, c.Y, c.Y2, c.y2_ch_stride, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
         }
-        else if (!e->matrix) launch_mac(mac_args(e, c.base_slot, c.Y, tc), sm);
-        else if (launch_mac_matrix(matrix_mac_args(e, c.base_slot, c.Y, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
-        if (both && !duo) {   // the same delay line through the same kernels with the new set, behind the first
-            if (!e->matrix) { MacArgs a = mac_args(e, c.base_slot, c.Y2, tc, true); a.y_ch_stride = c.y2_ch_stride; launch_mac(a, sm); }
-            else {
-                MatArgs a = matrix_mac_args(e, c.base_slot, c.Y2, tc, true); a.y_ch_stride = c.y2_ch_stride;
-                if (launch_mac_matrix(a, sm) != 0) return BFIR_ERR_UNSUPPORTED;
-            }
-        }
+        else if ((rc = queue_mac(e, c.base_slot, c.Y, (long)e->chunk * e->N, tc, false, sm)) != BFIR_OK) return rc;
+        // the same delay line through the same kernels with the new set, behind the first
+        if (both && !duo && (rc = queue_mac(e, c.base_slot, c.Y2, c.y2_ch_stride, tc, true, sm)) != BFIR_OK) return rc;
     }
     if (!il) {
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
@@ -1913,248 +1977,12 @@ static int ensure_fade_buffers(bfir_engine *e)
 // floor(a / b), b > 0
 static long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); }
 
-static int set_coeff_split_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale, int fade_blocks)
+// Catch-up: the blocks a level has run with the old set that the fade's first head block, or a later one, reads under
+// the new set -- their MAC again, with the new set alone, on the delay line the level still holds, into the second ring.
+// A level that restarted mid-stream less than that many blocks ago (bfir_engine_set_coeff_levels) has only those since,
+// the ones before read as zero under the new set.  Then the level's place in the lf_mode schedule.
+static int lfade_catch_up(bfir_engine *e, int fade_blocks, const LevelSplit &sp)
 {
-    long long cap = (long long)e->B * e->L;
-    for (int i = 0; i < e->n_tail; i++) cap += (long long)e->tail[i]->B * e->tail[i]->L;
-    if (!coeffs || n_coeffs < 0 || length < 0 || (long long)length > cap) return BFIR_ERR_ARG;
-    // m = 0 .. K L - 1 must be exact as a float (fftw_convolver.cpp:302 multiplies by (float)n)
-    if (fade_blocks < 1 || (long long)fade_blocks * e->L > (1ll << 24)) return BFIR_ERR_ARG;
-    if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
-    if (n_coeffs > e->C) n_coeffs = e->C;
-    for (int n = 0; n < n_coeffs; n++) if (!coeffs[n]) return BFIR_ERR_ARG;
-    // the split of set_coeff_split
-    const int len_h = (int)std::min<long long>(length, (long long)e->B * e->L);
-    const int nb_h = std::min(e->B, std::max(1, (len_h + e->L - 1) / e->L));
-    int len_lv[BFIR_MAX_LEVELS - 1], nb_lv[BFIR_MAX_LEVELS - 1];
-    for (int i = 0; i < e->n_tail; i++) {
-        const bfir_engine *t = e->tail[i];
-        const long long D = (long long)e->lv_D[i] * e->L;
-        len_lv[i] = (int)std::max(0ll, std::min((long long)length - D, (long long)t->B * t->L));
-        nb_lv[i] = len_lv[i] > 0 ? std::min(t->B, (len_lv[i] + t->L - 1) / t->L) : 0;
-        // a level the old set does not reach runs no forward transforms: it has no delay line to fade on
-        if (len_lv[i] > 0 && !e->lv_active[i]) {
-            bfir_logf("bfir engine: the new filters reach level %d, the active ones do not: load the first set zero-padded to the "
-                      "longest length that will be faded to.", i + 1);
-            return BFIR_ERR_UNSUPPORTED;
-        }
-    }
-    // a NaN / Inf tap at any level is refused before anything is uploaded at any level: the engine keeps running the old set
-    for (int n = 0; n < n_coeffs; n++) {
-        bool finite = true;
-        if (e->s == 4) {
-            const float *src = (const float *)coeffs[n];
-            const float sc = (float)scale;
-            for (int i = 0; i < length; i++) finite &= std::isfinite((double)(src[i] * sc));
-        } else {
-            const double *src = (const double *)coeffs[n];
-            for (int i = 0; i < length; i++) finite &= std::isfinite(src[i] * scale);
-        }
-        if (!finite) {
-            bfir_logf("NaN or Inf value among coefficients.");
-            bfir_logf("Error preprocessing coefficient %d", n);
-            return BFIR_ERR_COEFF;
-        }
-    }
-    HIP_TRY(hipSetDevice(e->device));
-    // queued work may still read what was H before the last fade's swap, and the catch-up below reads the delay lines: the
-    // device is idle from here to the end of the call
-    HIP_TRY(hipDeviceSynchronize());
-    // H2, the second ring and Yf of every level: allocated at the first fade
-    bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
-    for (bfir_engine *l : lv) {
-        if (!l || l->H2) continue;
-        HIP_TRY(hipMalloc(&l->H2, (size_t)l->C * l->B * cbuf_bytes(l)));
-        HIP_TRY(hipMalloc((void **)&l->d_nblk2, sizeof(int) * l->GC));
-    }
-    for (int i = 0; i < e->n_tail; i++) {
-        bfir_engine *t = e->tail[i];
-        if (!t->zring2) HIP_TRY(hipMalloc(&t->zring2, (size_t)t->GC * t->zblocks * t->L * t->s));
-    }
-    e->fade_fused = e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L);
-    if (e->fade_fused && !e->plan2.tw && fft_plan_create(&e->plan2, 2 * e->L, 4) != 0) return BFIR_ERR_HIP;   // an odd channel count: direct mode has none yet
-    int rc = load_filters(e, e->H2, 0, e->C, coeffs, n_coeffs, len_h, nb_h, scale, false);
-    if (rc != BFIR_OK) return rc;
-    e->nblk2.assign(e->nblk.size(), nb_h);
-    HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
-    for (int i = 0; i < e->n_tail; i++) {
-        bfir_engine *t = e->tail[i];
-        if (!e->lv_active[i]) continue;
-        if (len_lv[i] > 0) {
-            std::vector<const void *> rest((size_t)n_coeffs);
-            for (int n = 0; n < n_coeffs; n++) rest[n] = (const char *)coeffs[n] + (size_t)e->lv_D[i] * e->L * e->s;
-            rc = load_filters(t, t->H2, 0, t->C, rest.data(), n_coeffs, len_lv[i], nb_lv[i], scale, false);
-            if (rc != BFIR_OK) return rc;
-        } else {   // the new set does not reach the level: one all-zero partition, so its products with the new set are zero
-            HIP_TRY(hipMemset(t->H2, 0, (size_t)t->C * t->B * cbuf_bytes(t)));
-            nb_lv[i] = 1;
-        }
-        t->nblk2.assign(t->nblk.size(), nb_lv[i]);
-        HIP_TRY(hipMemcpy(t->d_nblk2, t->nblk2.data(), sizeof(int) * t->C, hipMemcpyHostToDevice));
-    }
-    // Catch-up: the blocks a level has run with the old set that the fade's first head block, or a later one, reads under
-    // the new set.  Their spectra are still in the delay line; a level that restarted mid-stream less than that many blocks
-    // ago (bfir_engine_set_coeff_levels) has only those since, the ones before read as zero under the new set.
-    const long long a_f = (long long)e->blockcounter;
-    for (int i = 0; i < e->n_tail; i++) {
-        bfir_engine *t = e->tail[i];
-        if (!e->lv_active[i]) continue;
-        const int r = e->lv_r[i];
-        rc = ensure_fade_buffers(t);
-        if (rc != BFIR_OK) return rc;
-        HIP_TRY(hipMemsetAsync(t->zring2, 0, (size_t)t->GC * t->zblocks * t->L * t->s, e->stream));
-        long long j0 = std::max(t->z_from, floor_div(a_f - e->lv_D[i], r));
-        j0 = std::max(j0, t->z_next - std::min<long long>((long long)t->blockcounter, t->ring_extra));
-        for (long long j = j0; j < t->z_next;) {
-            const int n = (int)std::min<long long>(t->z_next - j, t->yf_blocks);
-            const long long bc = (long long)t->blockcounter - (t->z_next - j);   // the level's own count of block j
-            MacArgs a = mac_args(t, (int)(bc % t->ring), t->Yf[0], n, true);
-            a.y_ch_stride = (long)t->yf_blocks * t->N;
-            launch_mac(a, e->stream);
-            inv_to_ring(t, t->Yf[0], a.y_ch_stride, t->zring2, j, n, e->stream);
-            j += n;
-        }
-        t->lf_j1 = floor_div(a_f + fade_blocks - 1 - e->lv_D[i], r);
-        t->lf_stop = len_lv[i] == 0;
-        t->lf_mode = 1;
-        if (t->z_next > t->lf_j1) { tail_swap_sets(t); t->lf_mode = 2; }   // every old block the fade reads has run
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    HIP_TRY(hipGetLastError());
-    e->fade_f = (float)(1.0 / (double)(float)(fade_blocks * e->L - 1));
-    e->fade_d = 1.0 / (double)(fade_blocks * e->L - 1);
-    e->fade_len = fade_blocks; e->fade_pos = 0;
-    return BFIR_OK;
-}
-
-extern "C" int bfir_engine_set_coeff_nup_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
-                                              int fade_blocks)
-{
-    if (!e) return BFIR_ERR_ARG;
-    if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
-    return set_coeff_split_fade(e, coeffs, n_coeffs, length, scale, fade_blocks);
-}
-
-extern "C" int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
-                                                 int fade_blocks)
-{
-    if (!e) return BFIR_ERR_ARG;
-    if (!e->levels) return BFIR_ERR_UNSUPPORTED;
-    return set_coeff_split_fade(e, coeffs, n_coeffs, length, scale, fade_blocks);
-}
-
-// The crossfade of a multi-level matrix engine: the schedule of set_coeff_split_fade (catch-up, lf_mode, second rings,
-// lfade_finish) with the split of bfir_engine_set_coeff_matrix_levels -- every filter of its own length, cut at every D_k,
-// partition counts per filter and level (0: skipped there) -- and the front-end rule of bfir_engine_set_coeff_matrix_fade.
-extern "C" int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const void *const *coeffs, const int *lengths, double scale,
-                                                        int fade_blocks)
-{
-    if (!e) return BFIR_ERR_ARG;
-    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
-    if (!coeffs || !lengths) return BFIR_ERR_ARG;
-    const int P = e->Co * e->C;                                 // filters, [o][i]
-    long long cap = (long long)e->B * e->L;
-    for (int i = 0; i < e->n_tail; i++) cap += (long long)e->tail[i]->B * e->tail[i]->L;
-    for (int n = 0; n < P; n++)
-        if (coeffs[n] && (lengths[n] < 0 || (long long)lengths[n] > cap)) return BFIR_ERR_ARG;
-    // m = 0 .. K L - 1 must be exact as a float (fftw_convolver.cpp:302 multiplies by (float)n)
-    if (fade_blocks < 1 || (long long)fade_blocks * e->L > (1ll << 24)) return BFIR_ERR_ARG;
-    if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
-    // the split of bfir_engine_set_coeff_matrix_levels: per level, the part of every filter that falls into it
-    bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
-    std::vector<const void *> part[BFIR_MAX_LEVELS];
-    std::vector<int> len[BFIR_MAX_LEVELS], nb2[BFIR_MAX_LEVELS];
-    int nb_max[BFIR_MAX_LEVELS] = {0, 0, 0, 0};
-    for (int k = 0; k <= e->n_tail; k++) {
-        const bfir_engine *l = lv[k];
-        const long long D = k == 0 ? 0 : (long long)e->lv_D[k - 1] * e->L;
-        part[k].assign((size_t)P, nullptr); len[k].assign((size_t)P, 0); nb2[k].assign(l->nblk.size(), 0);
-        for (int n = 0; n < P; n++) {
-            const long long rest = coeffs[n] ? std::min((long long)lengths[n] - D, (long long)l->B * l->L) : 0;
-            len[k][n] = (int)std::max(0ll, rest);
-            part[k][n] = len[k][n] > 0 ? (const char *)coeffs[n] + (size_t)D * e->s : nullptr;
-            nb2[k][n] = (len[k][n] + l->L - 1) / l->L;
-            nb_max[k] = std::max(nb_max[k], nb2[k][n]);
-        }
-        // a level no filter of the old set reaches runs no forward transforms: it has no delay line to fade on (per level,
-        // not per filter: a filter that is new on a running level fades in)
-        if (k > 0 && nb_max[k] > 0 && !e->lv_active[k - 1]) {
-            bfir_logf("bfir engine: the new filters reach level %d, the active ones do not: load the first set zero-padded to the "
-                      "longest length that will be faded to.", k);
-            return BFIR_ERR_UNSUPPORTED;
-        }
-    }
-    // a NaN / Inf tap at any level is refused before anything is uploaded at any level: the engine keeps running the old set
-    for (int n = 0; n < P; n++) {
-        if (!coeffs[n]) continue;
-        bool finite = true;
-        if (e->s == 4) {
-            const float *src = (const float *)coeffs[n];
-            const float sc = (float)scale;
-            for (int i = 0; i < lengths[n]; i++) finite &= std::isfinite((double)(src[i] * sc));
-        } else {
-            const double *src = (const double *)coeffs[n];
-            for (int i = 0; i < lengths[n]; i++) finite &= std::isfinite(src[i] * scale);
-        }
-        if (!finite) {
-            bfir_logf("NaN or Inf value among coefficients.");
-            bfir_logf("Error preprocessing coefficient %d (output %d, input %d)", n, n / e->C, n % e->C);
-            return BFIR_ERR_COEFF;
-        }
-    }
-    // the catch-up's launches (up to a tail's chunk) must fit the matrix MAC's grid: refused before anything changes
-    for (int i = 0; i < e->n_tail; i++)
-        if (e->lv_active[i]) { const int rc = matrix_chunk_ok(e->tail[i], e->tail[i]->chunk); if (rc != BFIR_OK) return rc; }
-    HIP_TRY(hipSetDevice(e->device));
-    // queued work may still read what was H before the last fade's swap, and the catch-up below reads the delay lines: the
-    // device is idle from here to the end of the call
-    HIP_TRY(hipDeviceSynchronize());
-    // H2 with its per-filter counts, the second ring and Yf of every level: allocated at the first fade
-    for (bfir_engine *l : lv) {
-        if (!l || l->H2) continue;
-        HIP_TRY(hipMalloc(&l->H2, (size_t)P * l->B * cbuf_bytes(l)));
-        HIP_TRY(hipMalloc((void **)&l->d_nblk2, sizeof(int) * l->GC));   // not read by the matrix MAC; swapped with d_nblk
-    }
-    for (int i = 0; i < e->n_tail; i++) {
-        bfir_engine *t = e->tail[i];
-        if (!t->zring2) HIP_TRY(hipMalloc(&t->zring2, (size_t)t->GCo * t->zblocks * t->L * t->s));
-    }
-    e->fade_fused = e->s == 4 && e->ilv && e->out_fmt == BFIR_SAMPLE_FORMAT_FLOAT_LE && pair_supported(e->L);
-    if (e->fade_fused && !e->plan2.tw && fft_plan_create(&e->plan2, 2 * e->L, 4) != 0) return BFIR_ERR_HIP;
-    for (int k = 0; k <= e->n_tail; k++) {
-        bfir_engine *l = lv[k];
-        if (k > 0 && !e->lv_active[k - 1]) continue;
-        if (nb_max[k] > 0) {   // a level the new set does not reach: every count 0, its products with the new set are stored as zeros
-            const int rc = load_filters(l, l->H2, 0, P, part[k].data(), P, 0, nb_max[k], scale, true, len[k].data());
-            if (rc != BFIR_OK) return rc;
-        } else HIP_TRY(hipMemset(l->H2, 0, (size_t)P * l->B * cbuf_bytes(l)));
-        l->nblk2 = nb2[k];
-    }
-    // Front end: a level pairs channels only while every input is read under BOTH sets (an input is read if any filter of
-    // its column has taps on any level); after the fade the new set decides (fade_swap_sets, lfade_finish).  The head of an
-    // engine without taps beyond D_1 and an odd output count is direct, as bfir_engine_set_coeff_matrix_levels has it.
-    bool read_old = true, read_new = true, tail_old = false, tail_new = false;
-    for (int i = 0; i < e->C; i++) {
-        bool ro = false, rn = false;
-        for (int o = 0; o < e->Co; o++) {
-            for (int k = 0; k <= e->n_tail; k++) ro = ro || lv[k]->nblk[o * e->C + i] > 0;
-            rn = rn || (coeffs[o * e->C + i] && lengths[o * e->C + i] > 0);
-        }
-        read_old = read_old && ro; read_new = read_new && rn;
-    }
-    for (int i = 0; i < e->n_tail; i++) { tail_old = tail_old || e->lv_active[i]; tail_new = tail_new || nb_max[i + 1] > 0; }
-    for (int i = 0; i < e->n_tail; i++) {
-        bfir_engine *t = e->tail[i];
-        t->pair_new = read_new;
-        if (t->pair_cap) matrix_take_path(t, read_old && read_new);
-    }
-    if (e->pair_cap) {
-        const bool odd = (e->Co & 1) != 0;
-        e->pair_new = read_new && !(odd && !tail_new);
-        matrix_take_path(e, e->pair_new && read_old && !(odd && !tail_old));
-    }
-    // Catch-up, as set_coeff_split_fade: the blocks a level has run with the old set that the fade's first head block, or a
-    // later one, reads under the new set -- their MAC again, with the new set alone, on the delay line the level still holds
     const long long a_f = (long long)e->blockcounter;
     for (int i = 0; i < e->n_tail; i++) {
         bfir_engine *t = e->tail[i];
@@ -2165,28 +1993,128 @@ extern "C" int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const vo
         HIP_TRY(hipMemsetAsync(t->zring2, 0, (size_t)t->GCo * t->zblocks * t->L * t->s, e->stream));
         long long j0 = std::max(t->z_from, floor_div(a_f - e->lv_D[i], r));
         j0 = std::max(j0, t->z_next - std::min<long long>((long long)t->blockcounter, t->ring_extra));
+        const long yf_stride = (long)t->yf_blocks * t->N;
         for (long long j = j0; j < t->z_next;) {
             const int n = (int)std::min<long long>(t->z_next - j, t->yf_blocks);
             const long long bc = (long long)t->blockcounter - (t->z_next - j);   // the level's own count of block j
-            MatArgs a = matrix_mac_args(t, (int)(bc % t->ring), t->Yf[0], n, true);
-            a.y_ch_stride = (long)t->yf_blocks * t->N;
-            if (launch_mac_matrix(a, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;   // checked above: not reached
-            inv_to_ring(t, t->Yf[0], a.y_ch_stride, t->zring2, j, n, e->stream);
+            rc = queue_mac(t, (int)(bc % t->ring), t->Yf[0], yf_stride, n, true, e->stream);
+            if (rc != BFIR_OK) return rc;   // a matrix level: checked before anything changed, not reached
+            inv_to_ring(t, t->Yf[0], yf_stride, t->zring2, j, n, e->stream);
             j += n;
         }
         t->lf_j1 = floor_div(a_f + fade_blocks - 1 - e->lv_D[i], r);
-        t->lf_stop = nb_max[i + 1] == 0;
+        t->lf_stop = sp.lv[i + 1].nb_max == 0;
         t->lf_mode = 1;
         if (t->z_next > t->lf_j1) { tail_swap_sets(t); t->lf_mode = 2; }   // every old block the fade reads has run
     }
+    return BFIR_OK;
+}
+
+// The crossfade of a two-level, multi-level or multi-level matrix engine: the split of set_coeff_split into H2 of every
+// level, the catch-up, and the head's fade as a uniform engine's.
+static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double scale, int fade_blocks)
+{
+    int rc = check_split_lengths(e, rows);
+    if (rc == BFIR_OK) rc = check_fade_args(e, fade_blocks);
+    if (rc != BFIR_OK) return rc;
+    for (int n = 0; n < rows.n_required; n++) if (!rows.taps[n]) return BFIR_ERR_ARG;
+    const LevelSplit sp = split_rows(e, rows);
+    for (int i = 0; i < e->n_tail; i++) {
+        // a level the old set does not reach runs no forward transforms: it has no delay line to fade on (per level, not
+        // per filter: a filter of a matrix engine that is new on a running level fades in)
+        if (sp.lv[i + 1].nb_max > 0 && !e->lv_active[i]) {
+            bfir_logf("bfir engine: the new filters reach level %d, the active ones do not: load the first set zero-padded to the "
+                      "longest length that will be faded to.", i + 1);
+            return BFIR_ERR_UNSUPPORTED;
+        }
+    }
+    // a NaN / Inf tap at any level is refused before anything is uploaded at any level: the engine keeps running the old set
+    rc = check_rows(e, rows, SIZE_MAX, scale);
+    if (rc != BFIR_OK) return rc;
+    // the catch-up's launches (up to a tail's chunk) must fit the matrix MAC's grid: refused before anything changes
+    for (int i = 0; i < e->n_tail; i++)
+        if (e->lv_active[i]) { rc = matrix_chunk_ok(e->tail[i], e->tail[i]->chunk); if (rc != BFIR_OK) return rc; }
+    HIP_TRY(hipSetDevice(e->device));
+    // queued work may still read what was H before the last fade's swap, and the catch-up below reads the delay lines: the
+    // device is idle from here to the end of the call
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t n_rows = rows.taps.size();
+    rc = fade_prepare(e, (int)n_rows);
+    if (rc != BFIR_OK) return rc;
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = level(e, k);
+        const LevelSplit::Level &s = sp.lv[k];
+        if (k > 0 && !e->lv_active[k - 1]) continue;
+        l->nblk2 = s.nb;
+        if (s.nb_max > 0) {
+            rc = load_filters(l, l->H2, 0, s.rows, s.nb_max, scale);
+            if (rc != BFIR_OK) return rc;
+        } else {
+            // The new set does not reach the level.  A matrix engine: every count 0, its products with the new set are stored
+            // as zeros.  A diagonal engine: one all-zero partition, so its products with the new set are zero.
+            HIP_TRY(hipMemset(l->H2, 0, n_rows * l->B * cbuf_bytes(l)));
+            if (!e->matrix) l->nblk2.assign(n_rows, 1);
+        }
+        // the matrix MAC takes the counts by value (MatArgs.nblk)
+        if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk2, l->nblk2.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
+    }
+    if (e->matrix) {
+        // Front end: a level pairs channels only while every input is read under BOTH sets (an input is read if any filter of
+        // its column has taps on any level); after the fade the new set decides (fade_swap_sets, lfade_finish).  The head of an
+        // engine without taps beyond D_1 and an odd output count is direct, as bfir_engine_set_coeff_matrix_levels has it.
+        const bool read_old = every_input_read(e, [&](int k, int n) { return level(e, k)->nblk[n]; });
+        const bool read_new = every_input_read(e, [&](int k, int n) { return sp.lv[k].nb[n]; });
+        bool tail_old = false, tail_new = false;
+        for (int i = 0; i < e->n_tail; i++) { tail_old = tail_old || e->lv_active[i]; tail_new = tail_new || sp.lv[i + 1].nb_max > 0; }
+        for (int i = 0; i < e->n_tail; i++) {
+            bfir_engine *t = e->tail[i];
+            t->pair_new = read_new;
+            if (t->pair_cap) matrix_take_path(t, read_old && read_new);
+        }
+        if (e->pair_cap) {
+            const bool odd = (e->Co & 1) != 0;
+            e->pair_new = read_new && !(odd && !tail_new);
+            matrix_take_path(e, e->pair_new && read_old && !(odd && !tail_old));
+        }
+    }
+    rc = lfade_catch_up(e, fade_blocks, sp);
+    if (rc != BFIR_OK) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipGetLastError());
-    e->fade_f = (float)(1.0 / (double)(float)(fade_blocks * e->L - 1));
-    e->fade_d = 1.0 / (double)(fade_blocks * e->L - 1);
-    e->fade_len = fade_blocks; e->fade_pos = 0;
-    bfir_logf("bfir matrix engine: crossfade over %d blocks on %d levels; a launch that needs both sets runs %s.", fade_blocks,
-              e->n_tail + 1, chunk_takes_duo(e) ? "k_mac_duo" : "k_mac_matrix twice");
+    fade_begin(e, fade_blocks);
+    if (e->matrix)
+        bfir_logf("bfir matrix engine: crossfade over %d blocks on %d levels; a launch that needs both sets runs %s.", fade_blocks,
+                  e->n_tail + 1, chunk_takes_duo(e) ? "k_mac_duo" : "k_mac_matrix twice");
     return BFIR_OK;
+}
+
+extern "C" int bfir_engine_set_coeff_nup_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
+                                              int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || n_coeffs < 0) return BFIR_ERR_ARG;
+    return set_coeff_split_fade(e, diagonal_rows(e, coeffs, n_coeffs, length), scale, fade_blocks);
+}
+
+extern "C" int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
+                                                 int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->levels) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || n_coeffs < 0) return BFIR_ERR_ARG;
+    return set_coeff_split_fade(e, diagonal_rows(e, coeffs, n_coeffs, length), scale, fade_blocks);
+}
+
+// every filter of its own length, partition counts per filter and level, and the front-end rule of
+// bfir_engine_set_coeff_matrix_fade
+extern "C" int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const void *const *coeffs, const int *lengths, double scale,
+                                                        int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || !lengths) return BFIR_ERR_ARG;
+    return set_coeff_split_fade(e, matrix_rows(e, coeffs, lengths, 0), scale, fade_blocks);
 }
 
 extern "C" int bfir_engine_fade_remaining_levels(const bfir_engine *e)
@@ -2797,9 +2725,8 @@ static void nup_reset(bfir_engine *e)
 {
     (void)hipDeviceSynchronize();
     if (e->fade_len > 0) fade_swap_sets(e);   // a fade ends at once, with the new set active at every level
-    bfir_engine *lv[BFIR_MAX_LEVELS] = {e, e->tail[0], e->tail[1], e->tail[2]};
-    for (bfir_engine *l : lv) {
-        if (!l) continue;
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = level(e, k);
         (void)hipMemset(l->X, 0, (size_t)l->GC * l->ring * cbuf_bytes(l));
         for (int st = 0; st < 2; st++)
             for (int i = 0; i < 2; i++) (void)hipMemset(l->tails[st][i], 0, (size_t)l->L * l->C * l->in_bytes);
