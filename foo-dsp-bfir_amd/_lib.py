@@ -56,6 +56,7 @@ SIGNATURES = {
     "bfir_engine_create_batch": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_create_big": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_create_matrix": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
+    "bfir_engine_create_mimo": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_destroy": (None, [_vp]),
     "bfir_engine_is_initialized": (_ci, [_vp]),
     "bfir_engine_set_coeff": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _ci, _cd]),

@@ -12,6 +12,7 @@
 // GC = n_eng * C global channels.  A matrix engine (bfir_engine_create_matrix: one engine, C = n_in inputs, Co = n_out
 // outputs, one filter per (output, input) pair) keeps the input side -- X, tails, saved -- for its C inputs and the output
 // side -- Y, the overflow statistics, the output frames -- for its Co outputs; H is [Co][C][B][N], the MAC k_mac_matrix.
+// A mimo engine (bfir_engine_create_mimo) is a matrix engine with up to 64 of each and k_mac_mimo as its MAC.
 // A run of n blocks is cut into chunks of at most `chunk` blocks.  A chunk is front (fwd; stage_in before it on the
 // staging path), MAC and back (inv; stage_out after it on the staging path), software-pipelined over three streams.
 // What is written once here, because every path shares it: the path an engine takes (choose_path), the coefficient
@@ -103,6 +104,11 @@ struct bfir_engine {
     int L = 0, N = 0, B = 0, s = 0, C = 0, n_eng = 1, GC = 0;
     bool matrix = false;            // n_in -> n_out with one filter per pair (matrix.hip); diagonal: output c = input c * h_c
     int Co = 0, GCo = 0;            // output channels per engine / in all: C and GC, or a matrix engine's n_out
+    // a matrix engine created by bfir_engine_create_mimo: up to BFIR_MIMO_MAXCHANNELS inputs and outputs, no delays.  Its
+    // partition counts are also kept in HBM (d_nblk, d_nblk2: [o C + i]) for k_mac_mimo (mimo.hip), which runs its MAC when
+    // mimo_mac is set: always past 8 channels on either side, where k_mac_matrix cannot run; with both counts within 8 --
+    // the same bits either way -- only on BFIR_MIMO_MAC=1, read at creation (choose_path)
+    bool mimo = false, mimo_mac = false;
     int in_bytes = 0, out_bytes = 0, in_fmt = 0, out_fmt = 0;
     double in_scale = 1.0, out_scale = 1.0, of_max = 1.0;
     FftPlan plan;
@@ -433,6 +439,11 @@ static void choose_path(bfir_engine *e)
     // both sets of a fading multi-level matrix engine in one MAC launch (k_mac_duo), the default: lower than two launches of
     // k_mac_matrix in every paired run ("Crossfades on multi-level matrix engines"); BFIR_MFADE_DUO=0 keeps the two
     if (const char *mv = getenv("BFIR_MFADE_DUO")) e->mfade_duo = atoi(mv) != 0;
+    // k_mac_matrix stays the default where it can run: k_mac_mimo was not faster there ("k_mac_mimo")
+    if (e->mimo) {
+        const char *mm = getenv("BFIR_MIMO_MAC");
+        e->mimo_mac = e->C > BFIR_MAT_MAX || e->Co > BFIR_MAT_MAX || (mm && atoi(mm) != 0);
+    }
     if (const char *qv = getenv("BFIR_INV_QUAD")) e->inv_quad = atoi(qv) != 0;
     if (const char *wv = getenv("BFIR_FWD_WIDE")) e->fwd_wide = atoi(wv) != 0;
     if (const char *pm = getenv("BFIR_PIPE")) { e->pipe3 = atoi(pm) >= 3; e->serial = atoi(pm) == 1; }
@@ -452,7 +463,7 @@ static void log_creation(const bfir_engine *e)
         return;
     }
     // a matrix engine's path=pair can give way to direct mode while an input feeds no output (bfir_engine_set_coeff_matrix logs it)
-    if (e->matrix) snprintf(shape, sizeof(shape), "matrix %d -> %d", e->C, e->Co);
+    if (e->matrix) snprintf(shape, sizeof(shape), "%s %d -> %d", e->mimo ? "mimo" : "matrix", e->C, e->Co);
     else snprintf(shape, sizeof(shape), "%d x %d channels", e->n_eng, e->C);
     bfir_logf("bfir engine: %s, partition %d, %d blocks, realsize %d on device %d. path=%s layout=%s run=%s",
               shape, e->L, e->B, e->s, e->device,
@@ -462,16 +473,19 @@ static void log_creation(const bfir_engine *e)
 
 // matrix: `channels` inputs, `channels_out` outputs, one engine (bfir_engine_create_matrix); else channels_out == channels
 // nup_level: 0, or 1 / 2 for the head / tail level of a two-level engine (bfir_engine_create_nup)
+// max_channels: the channel cap of the calling kind -- BFIR_MIMO_MAXCHANNELS for a mimo engine (a matrix engine with that cap)
 static bfir_engine *engine_create(int n_engines, int filter_length, int filter_blocks, int realsize, int channels,
                                   int channels_out, bool matrix, int in_format, int out_format, int sampling_rate,
-                                  int apply_dither, int device, int *err, int nup_level = 0, int ring_extra = 0, bool big = false)
+                                  int apply_dither, int device, int *err, int nup_level = 0, int ring_extra = 0, bool big = false,
+                                  int max_channels = BFIR_MAXCHANNELS)
 {
+    const bool mimo = matrix && max_channels > BFIR_MAXCHANNELS;
     int dummy;
     if (!err) err = &dummy;
     *err = BFIR_OK;
     // brutefir.cpp:652 (channel limit), fftw_convolver.cpp:64-74 (realsize, length)
-    if (channels < 1 || channels > BFIR_MAXCHANNELS || channels_out < 1 || channels_out > BFIR_MAXCHANNELS) {
-        bfir_logf("Number of channels (%d) exceeds limit (%d).", std::max(channels, channels_out), BFIR_MAXCHANNELS);
+    if (channels < 1 || channels > max_channels || channels_out < 1 || channels_out > max_channels) {
+        bfir_logf("Number of channels (%d) exceeds limit (%d).", std::max(channels, channels_out), max_channels);
         *err = BFIR_ERR_ARG; return nullptr;
     }
     if (realsize != 4 && realsize != 8) { bfir_logf("Invalid real size %d.", realsize); *err = BFIR_ERR_ARG; return nullptr; }
@@ -490,6 +504,7 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
     e->L = filter_length; e->N = 2 * filter_length; e->B = filter_blocks; e->s = realsize;
     e->C = channels; e->n_eng = n_engines; e->GC = n_engines * channels;
     e->matrix = matrix; e->Co = channels_out; e->GCo = n_engines * channels_out;
+    e->mimo = mimo;
     e->in_bytes = fmt_bytes(in_format); e->out_bytes = fmt_bytes(out_format);
     e->in_fmt = in_format; e->out_fmt = out_format;
     // setup_input: normalised scale 1/2^(bits-1); setup_output: full scale; overflow max
@@ -527,10 +542,11 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
         if (hipEventCreateWithFlags(ev, hipEventDisableTiming) != hipSuccess) return fail(BFIR_ERR_HIP);
     const size_t cb = cbuf_bytes(e), Ls = (size_t)e->L * e->s;
     const size_t n_filters = matrix ? (size_t)e->Co * e->C : (size_t)e->GC;
+    const size_t nblk_bytes = sizeof(int) * (mimo ? n_filters : (size_t)e->GC);   // a mimo engine: the table of k_mac_mimo
     if (hipMalloc(&e->H, n_filters * e->B * cb) != hipSuccess ||
         hipMalloc(&e->saved[0], (size_t)e->GC * Ls) != hipSuccess ||
         hipMalloc(&e->saved[1], (size_t)e->GC * Ls) != hipSuccess ||
-        hipMalloc((void **)&e->d_nblk, sizeof(int) * e->GC) != hipSuccess ||
+        hipMalloc((void **)&e->d_nblk, nblk_bytes) != hipSuccess ||
         hipMalloc((void **)&e->d_of, sizeof(DevOverflow) * e->GCo * BFIR_OF_SHARDS) != hipSuccess ||
         hipMalloc((void **)&e->d_bad, sizeof(int)) != hipSuccess)
         return fail(BFIR_ERR_HIP);
@@ -539,7 +555,7 @@ static bfir_engine *engine_create(int n_engines, int filter_length, int filter_b
         (void)hipMemset(e->saved[i], 0, (size_t)e->GC * Ls);
         e->hist[i].ptr = e->saved[i]; e->hist[i].ch_stride = e->L;
     }
-    (void)hipMemset(e->d_nblk, 0, sizeof(int) * e->GC);
+    (void)hipMemset(e->d_nblk, 0, nblk_bytes);
     (void)hipMemset(e->d_of, 0, sizeof(DevOverflow) * e->GCo * BFIR_OF_SHARDS);
     (void)hipMemset(e->d_bad, 0x7f, sizeof(int));
     if (apply_dither && !fmt_info(out_format).isfloat) {
@@ -602,6 +618,30 @@ static bool length_supported(int filter_length, int realsize)
 {
     return filter_length >= 16 && filter_length <= 16384 &&
            ((size_t)filter_length + (size_t)filter_length / 32) * 2 * (size_t)realsize <= 160 * 1024;
+}
+
+// A matrix engine of up to BFIR_MIMO_MAXCHANNELS inputs and outputs: everything bfir_engine_create_matrix makes, with the
+// wider cap, the partition counts in HBM and k_mac_mimo (mimo.hip) as its MAC.  Every refusal but BFIR_ERR_NO_DEVICE comes
+// before the device is touched.
+extern "C" bfir_engine *bfir_engine_create_mimo(int filter_length, int filter_blocks, int realsize, int n_inputs, int n_outputs,
+                                                int in_format, int out_format, int device, int *err)
+{
+    int dummy;
+    if (!err) err = &dummy;
+    if (n_inputs < 1 || n_inputs > BFIR_MIMO_MAXCHANNELS || n_outputs < 1 || n_outputs > BFIR_MIMO_MAXCHANNELS) {
+        bfir_logf("Number of channels (%d -> %d) exceeds limit (%d).", n_inputs, n_outputs, BFIR_MIMO_MAXCHANNELS);
+        *err = BFIR_ERR_ARG; return nullptr;
+    }
+    // float frames only (no staging kernels, no dither)
+    if (!fmt_is_native(in_format) || !fmt_is_native(out_format)) { *err = BFIR_ERR_UNSUPPORTED; return nullptr; }
+    // a power of two outside the lengths bfir_engine_create takes; everything else is engine_create's to judge
+    const bool pow2 = filter_length >= 1 && !(filter_length & (filter_length - 1));
+    if (pow2 && (realsize == 4 || realsize == 8) && !length_supported(filter_length, realsize)) {
+        bfir_logf("bfir engine: partition %d with realsize %d is outside a mimo engine's range.", filter_length, realsize);
+        *err = BFIR_ERR_UNSUPPORTED; return nullptr;
+    }
+    return engine_create(1, filter_length, filter_blocks, realsize, n_inputs, n_outputs, true, in_format, out_format, 44100, 0,
+                         device, err, 0, 0, false, BFIR_MIMO_MAXCHANNELS);
 }
 
 // Partitions past one workgroup's transform: 2^15 (fp64: 2^14) .. 2^20 samples, the lengths big_split takes.
@@ -1028,6 +1068,8 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
     if (rc == BFIR_OK) rc = load_filters(e, e->H, 0, rows, nb, scale);
     if (rc != BFIR_OK) return rc;
     for (size_t n = 0; n < rows.taps.size(); n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
+    // ... k_mac_mimo from its table (the device is idle)
+    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk, e->nblk.data(), sizeof(int) * e->nblk.size(), hipMemcpyHostToDevice));
     if (e->pair_cap) matrix_take_path(e, every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
     e->eng_init[0] = 1;
     return BFIR_OK;
@@ -1212,7 +1254,8 @@ static int fade_prepare(bfir_engine *e, int n_rows)
         bfir_engine *l = level(e, k);
         if (l->H2) continue;
         HIP_TRY(hipMalloc(&l->H2, (size_t)n_rows * l->B * cbuf_bytes(l)));
-        HIP_TRY(hipMalloc((void **)&l->d_nblk2, sizeof(int) * l->GC));   // not read by the matrix MAC; swapped with d_nblk
+        // not read by k_mac_matrix; swapped with d_nblk.  A mimo engine: the second table of k_mac_mimo
+        HIP_TRY(hipMalloc((void **)&l->d_nblk2, sizeof(int) * (l->mimo ? (size_t)n_rows : (size_t)l->GC)));
     }
     for (int i = 0; i < e->n_tail; i++) {
         bfir_engine *t = e->tail[i];
@@ -1255,6 +1298,7 @@ static int set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_coeff
     e->nblk2.assign(e->nblk.size(), 0);
     for (size_t n = 0; n < rows.taps.size(); n++) e->nblk2[n] = (e->matrix && !coeffs[n]) ? 0 : nb;
     if (!e->matrix) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
+    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->nblk2.size(), hipMemcpyHostToDevice));
     if (e->matrix && e->pair_cap) {
         // no channel pairs around an unread input, per set: the fade's forward transforms take the pair path only if every
         // input is read under BOTH sets; after the fade the new set decides
@@ -1499,8 +1543,22 @@ static MatArgs matrix_mac_args(const bfir_engine *e, int base_slot, void *Y, int
     return a;
 }
 
+// ... and of a mimo engine's where k_mac_mimo runs it: the same, with the counts in the engine's table in HBM
+static MimoArgs mimo_mac_args(const bfir_engine *e, int base_slot, void *Y, int tc, bool second = false)
+{
+    MimoArgs a;
+    a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
+    a.h = second ? e->H2 : e->H; a.h_pair_stride = (long)e->B * e->N;
+    a.nblk = second ? e->d_nblk2 : e->d_nblk;
+    a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
+    a.n_t = tc; a.n_in = e->C; a.n_out = e->Co; a.N = e->N; a.realsize = e->s;
+    a.interleaved = e->ilv;
+    return a;
+}
+
 // The MAC of tc blocks of an engine, a level included, from delay-line slot base_slot on into Y (y_ch_stride reals per
-// channel) with the active or the second set: k_mac on a diagonal engine, k_mac_matrix on a matrix engine.
+// channel) with the active or the second set: k_mac on a diagonal engine, k_mac_matrix on a matrix engine, k_mac_mimo
+// on a mimo engine (mimo_mac).
 static int queue_mac(const bfir_engine *e, int base_slot, void *Y, long y_ch_stride, int tc, bool second, hipStream_t s)
 {
     if (!e->matrix) {
@@ -1508,6 +1566,11 @@ static int queue_mac(const bfir_engine *e, int base_slot, void *Y, long y_ch_str
         a.y_ch_stride = y_ch_stride;
         launch_mac(a, s);
         return BFIR_OK;
+    }
+    if (e->mimo_mac) {
+        MimoArgs a = mimo_mac_args(e, base_slot, Y, tc, second);
+        a.y_ch_stride = y_ch_stride;
+        return launch_mac_mimo(a, s) != 0 ? BFIR_ERR_UNSUPPORTED : BFIR_OK;
     }
     MatArgs a = matrix_mac_args(e, base_slot, Y, tc, second);
     a.y_ch_stride = y_ch_stride;
@@ -1517,7 +1580,8 @@ static int queue_mac(const bfir_engine *e, int base_slot, void *Y, long y_ch_str
 // a chunk the matrix MAC cannot take is refused before anything is queued (never skipped)
 static int matrix_chunk_ok(const bfir_engine *e, int tc)
 {
-    if (e->matrix && !mac_matrix_supported(matrix_mac_args(e, 0, nullptr, tc))) {
+    if (e->matrix && !(e->mimo_mac ? mac_mimo_supported(mimo_mac_args(e, 0, nullptr, tc))
+                                   : mac_matrix_supported(matrix_mac_args(e, 0, nullptr, tc)))) {
         bfir_logf("bfir engine: %d blocks per launch are past the matrix MAC's grid.", tc);
         return BFIR_ERR_UNSUPPORTED;
     }
@@ -2275,7 +2339,7 @@ extern "C" int bfir_engine_delay_init(bfir_engine *e, int side, int max_delay, i
 {
     if (!e || !delay_side_ok(side) || max_delay < 0 || max_delay > (1 << 24) || step_count < 0 || step_count == 1) return BFIR_ERR_ARG;
     if (step_count >= 2 && (half_filter_length < 1 || half_filter_length > 128)) return BFIR_ERR_ARG;
-    if (e->n_eng > 1) return BFIR_ERR_UNSUPPORTED;
+    if (e->n_eng > 1 || e->mimo) return BFIR_ERR_UNSUPPORTED;   // batches; a mimo engine (DelayTab holds BFIR_DELAY_CH channels)
     if (step_count >= 2 && !fmt_is_native(side == BFIR_DELAY_INPUT ? e->in_fmt : e->out_fmt)) return BFIR_ERR_UNSUPPORTED;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
@@ -2304,6 +2368,7 @@ extern "C" int bfir_engine_delay_init(bfir_engine *e, int side, int max_delay, i
 extern "C" int bfir_engine_set_delay(bfir_engine *e, int side, const int *delay, const int *subdelay, int n_channels)
 {
     if (!e || !delay || !delay_side_ok(side)) return BFIR_ERR_ARG;
+    if (e->mimo) return BFIR_ERR_UNSUPPORTED;
     bfir_engine::DelaySide &d = e->dly[side];
     if (!d.on) return BFIR_ERR_STATE;
     if (n_channels != delay_channels(e, side)) return BFIR_ERR_ARG;
@@ -2322,6 +2387,7 @@ extern "C" int bfir_engine_set_delay(bfir_engine *e, int side, const int *delay,
 extern "C" int bfir_engine_get_delay(const bfir_engine *e, int side, int *delay, int *subdelay, int n_channels)
 {
     if (!e || !delay || !subdelay || !delay_side_ok(side)) return BFIR_ERR_ARG;
+    if (e->mimo) return BFIR_ERR_UNSUPPORTED;
     const bfir_engine::DelaySide &d = e->dly[side];
     if (!d.on) return BFIR_ERR_STATE;
     if (n_channels != delay_channels(e, side)) return BFIR_ERR_ARG;
@@ -2332,6 +2398,7 @@ extern "C" int bfir_engine_get_delay(const bfir_engine *e, int side, int *delay,
 extern "C" int bfir_engine_delay_latency(const bfir_engine *e, int side)
 {
     if (!e || !delay_side_ok(side)) return BFIR_ERR_ARG;
+    if (e->mimo) return BFIR_ERR_UNSUPPORTED;
     return e->dly[side].on ? e->dly[side].h : 0;
 }
 
@@ -2473,6 +2540,8 @@ static int ensure_chunk(bfir_engine *e, int n_blocks)
             return BFIR_ERR_UNSUPPORTED;
         }
     }
+    // a mimo engine: a launch past k_mac_mimo's grid is refused here, before anything is allocated or queued
+    if (e->mimo_mac && want > e->chunk) { const int rc = matrix_chunk_ok(e, want); if (rc != BFIR_OK) return rc; }
     if (want > e->chunk) {
         const int rc = alloc_work(e, want);
         if (rc != BFIR_OK || !e->nup) return rc;

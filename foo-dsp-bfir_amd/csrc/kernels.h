@@ -179,6 +179,23 @@ struct MatArgs {
 bool mac_matrix_supported(const MatArgs &a);               // the grid of the launch fits
 int launch_mac_matrix(const MatArgs &a, hipStream_t s);    // 0, or -1 if !mac_matrix_supported(a) (nothing launched)
 
+// mimo.hip: k_mac_mimo, the same sums for a mimo engine (bfir_engine_create_mimo: up to BFIR_MIMO_MAX inputs and outputs),
+// one fma chain per (output, bin, block) as above: the bits of launch_mac_matrix wherever both can run.  MimoArgs is MatArgs
+// with the partition counts in HBM, [o n_in + i] (the engine rewrites the table when the filters are set), and the kernel
+// differs from k_mac_matrix in its grid alone: workgroups of one wave over 64 bins, every (bin tile, output tile, time
+// tile) in grid x with the time tiles fastest, so that what an XCD runs at one time shares one slice of H in its L2.
+constexpr int BFIR_MIMO_MAX = 64;          // inputs / outputs of a mimo engine (BFIR_MIMO_MAXCHANNELS)
+struct MimoArgs {
+    const void *x; long x_ch_stride; int ring, base_slot;     // delay line [n_in][ring][N]
+    const void *h; long h_pair_stride;                       // [n_out][n_in][B][N]: pair (o, i) at (o n_in + i) h_pair_stride
+    const int *nblk;                                         // device [n_out n_in]: partitions of h_{o,i}; wave-uniform reads
+    void *y; long y_ch_stride;                               // [n_out][n_t][N]
+    int n_t, n_in, n_out, N, realsize;
+    int interleaved;                                         // layout of x, h and y, as in FwdArgs
+};
+bool mac_mimo_supported(const MimoArgs &a);                // the grid of the launch fits
+int launch_mac_mimo(const MimoArgs &a, hipStream_t s);     // 0, or -1 if !mac_mimo_supported(a) (nothing launched)
+
 // mfade.hip: k_mac_duo, the matrix MAC of a chunk that needs BOTH filter sets of a crossfaded coefficient change on a
 // multi-level matrix engine (bfir_engine_set_coeff_matrix_levels_fade): one pass over the delay line computes
 //   Y [o][t] = sum_i sum_{p < a.nblk[o][i]} X[i][slot(t - p)] * H [o][i][p]     (a: the old set, exactly launch_mac_matrix(a))

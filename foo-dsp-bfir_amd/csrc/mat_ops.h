@@ -1,5 +1,6 @@
-// mat_ops.h -- the two per-term operations the matrix MAC kernels share (matrix.hip: k_mac_matrix; mfade.hip: k_mac_duo):
-// one complex multiply-add in the order of every MAC here, and the load of one bin of a spectrum in either layout.
+// mat_ops.h -- what the matrix MAC kernels share (matrix.hip: k_mac_matrix; mfade.hip: k_mac_duo; mimo.hip: k_mac_mimo):
+// one complex multiply-add in the order of every MAC here, the load of one bin of a spectrum in either layout, and the
+// sums of one lane of k_mac_matrix and k_mac_mimo (mat_tile, mat_lane), which differ in their grids alone.
 #pragma once
 #include "kernels.h"
 
@@ -31,6 +32,107 @@ __device__ __forceinline__ void mat_ld(const T *__restrict__ s, int ore, int oim
         re = v.x; im = v.y;
     } else {
         re = s[ore]; im = s[oim];
+    }
+}
+
+// The sums of one lane -- one bin, the tile of TT output blocks from t0, the NO outputs from o0 -- into its accumulators.  A is
+// MatArgs (k_mac_matrix: the partition counts by value) or MimoArgs (k_mac_mimo: a table in HBM): a.nblk[o n_in + i] either
+// way, wave-uniform.  Per input the lane walks the partitions in order with a window of TT delay-line spectra in registers,
+// X[t0 + j - p] for j < TT: step p loads ONE new spectrum and the NO filter spectra H[o][i][p], then does NO x TT complex
+// MACs.  Operands are fetched one step ahead.
+template <typename T, bool ILV, int NO, int TT, bool DCNY, typename A>
+__device__ __forceinline__ void mat_tile(const A &a, int o0, int t0, int ore, int oim, bool k0,
+                                         T (&ar)[NO][TT], T (&ai)[NO][TT])
+{
+    const long N = a.N;
+    const int ring = a.ring;
+    const int sl = (a.base_slot + t0) % ring;                    // delay-line slot of block t0
+    for (int i = 0; i < a.n_in; i++) {
+        int nb[NO], nbm = 0, om = 0;
+#pragma unroll
+        for (int o = 0; o < NO; o++) {
+            nb[o] = o0 + o < a.n_out ? a.nblk[(o0 + o) * a.n_in + i] : 0;
+            if (nb[o] > nbm) { nbm = nb[o]; om = o; }
+        }
+        if (nbm == 0) continue;                                  // no filter of this tile reads input i
+        const T *__restrict__ Xi = (const T *)a.x + (long)i * a.x_ch_stride;
+        // filter spectra of (o, i); a pair without a filter is pointed at one with nbm partitions (loaded, never used)
+        const T *__restrict__ Hp[NO];
+#pragma unroll
+        for (int o = 0; o < NO; o++)
+            Hp[o] = (const T *)a.h + ((long)(o0 + (nb[o] > 0 ? o : om)) * a.n_in + i) * a.h_pair_stride;
+        // window: slot (j - p) mod TT holds X[t0 + j - p].  In the last tile of a launch the blocks t0 + j >= n_t are slots
+        // the NEXT chunk's forward transform may be writing at this moment (ring = 2 chunk + B keeps the read in bounds):
+        // their values only reach accumulators that are never stored, so that race is harmless and needs no wait
+        T wr[TT], wi[TT];
+#pragma unroll
+        for (int j = 0; j < TT; j++) {
+            int sj = sl + j; if (sj >= ring) sj -= ring;
+            mat_ld<T, ILV>(Xi + (long)sj * N, ore, oim, wr[j], wi[j]);
+        }
+        T qxr = (T)0, qxi = (T)0, qhr[NO], qhi[NO];              // operands of the next step (step 0 takes no new X)
+#pragma unroll
+        for (int o = 0; o < NO; o++) mat_ld<T, ILV>(Hp[o], ore, oim, qhr[o], qhi[o]);
+        for (int p0 = 0; p0 < nbm; p0 += TT) {
+#pragma unroll
+            for (int ii = 0; ii < TT; ii++) {
+                const int p = p0 + ii;
+                if (p < nbm) {                                   // wave-uniform
+                    if (p > 0) { wr[(TT - ii) % TT] = qxr; wi[(TT - ii) % TT] = qxi; }
+                    // prefetch step p + 1 (clamped to the last step: in range, not used); each H register pair is
+                    // reloaded as soon as its output's MACs have read it, so H costs 2 NO registers, not 4 NO
+                    const int pn = p + 1 < nbm ? p + 1 : p;
+                    int sn = sl - pn; if (sn < 0) sn += ring;       // X[t0 - pn] enters the window at step pn
+                    mat_ld<T, ILV>(Xi + (long)sn * N, ore, oim, qxr, qxi);
+#pragma unroll
+                    for (int o = 0; o < NO; o++) {
+                        if (p < nb[o]) {                         // wave-uniform: pairs without this partition are skipped
+#pragma unroll
+                            for (int j = 0; j < TT; j++) {
+                                const int idx = (j - ii + TT) % TT;
+                                mat_cmac<DCNY>(ar[o][j], ai[o][j], wr[idx], wi[idx], qhr[o], qhi[o], k0);
+                            }
+                        }
+                        const int po = pn < nb[o] ? pn : (nb[o] > 0 ? nb[o] - 1 : pn);
+                        mat_ld<T, ILV>(Hp[o] + (long)po * N, ore, oim, qhr[o], qhi[o]);
+                    }
+                }
+            }
+        }
+    }
+}
+
+
+// ... and the whole of that lane: accumulate (the wave that holds bin 0 carries DC | Nyquist as two real sums), then store
+// every (output, block) of the tile exactly once, outputs without any filter as zeros.
+template <typename T, bool ILV, int NO, int TT, typename A>
+__device__ __forceinline__ void mat_lane(const A &a, int k, bool wave0, int o0, int t0)
+{
+    const int ore = ILV ? 2 * k : 8 * (k >> 2) + (k & 3), oim = ILV ? ore + 1 : ore + 4;
+    T ar[NO][TT], ai[NO][TT];
+#pragma unroll
+    for (int o = 0; o < NO; o++)
+#pragma unroll
+        for (int j = 0; j < TT; j++) { ar[o][j] = (T)0; ai[o][j] = (T)0; }
+    if (wave0) mat_tile<T, ILV, NO, TT, true>(a, o0, t0, ore, oim, k == 0, ar, ai);
+    else mat_tile<T, ILV, NO, TT, false>(a, o0, t0, ore, oim, false, ar, ai);
+#pragma unroll
+    for (int o = 0; o < NO; o++) {
+        if (o0 + o >= a.n_out) break;
+        T *__restrict__ Y = (T *)a.y + (long)(o0 + o) * a.y_ch_stride;
+#pragma unroll
+        for (int j = 0; j < TT; j++) {
+            if (t0 + j < a.n_t) {
+                T *yo = Y + (long)(t0 + j) * a.N;
+                if constexpr (ILV) {
+                    using V2 = typename Vec2<T>::type;
+                    V2 v; v.x = ar[o][j]; v.y = ai[o][j];
+                    *(V2 *)(yo + ore) = v;
+                } else {
+                    yo[ore] = ar[o][j]; yo[oim] = ai[o][j];
+                }
+            }
+        }
     }
 }
 

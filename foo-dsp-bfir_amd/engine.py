@@ -295,6 +295,8 @@ class BrutefirMatrix(Brutefir):
     run / run_device / sync / reset / set_chunk / set_profiling / profile / close are Brutefir's; overflow(o) is
     output o's."""
 
+    _create = "bfir_engine_create_matrix"   # the entry point of the kind (BrutefirMimo: the wider one)
+
     def __init__(self, filter_length, filter_blocks, realsize, n_in, n_out, in_format=None, out_format=None, device=0):
         dflt = SAMPLE_FORMAT_FLOAT_LE if realsize == 4 else SAMPLE_FORMAT_FLOAT64_LE
         self.L, self.B, self.s = filter_length, filter_blocks, realsize
@@ -305,10 +307,10 @@ class BrutefirMatrix(Brutefir):
         self.n_engines, self.device = 1, device
         self._lib = _lib.load()
         err = C.c_int(0)
-        self._h = self._lib.bfir_engine_create_matrix(filter_length, filter_blocks, realsize, n_in, n_out,
-                                                      self.in_format, self.out_format, device, C.byref(err))
+        self._h = getattr(self._lib, self._create)(filter_length, filter_blocks, realsize, n_in, n_out,
+                                                   self.in_format, self.out_format, device, C.byref(err))
         if not self._h:
-            raise BfirError(err.value, "bfir_engine_create_matrix")
+            raise BfirError(err.value, self._create)
 
     def set_coeff(self, rows, length=None, coeff_blocks=None, scale=1.0):
         """rows[o][i]: taps of h_{o,i} (working precision) or None = no path from input i to output o.
@@ -359,6 +361,17 @@ class BrutefirMatrix(Brutefir):
         if rc != 0:
             raise BfirError(rc, "bfir_engine_read_coeff_matrix")
         return dst
+
+
+class BrutefirMimo(BrutefirMatrix):
+    """BrutefirMatrix with up to 64 inputs and outputs (bfir_engine_create_mimo): the same methods, and the same bytes
+    wherever both exist.  No delays: delay_init raises BfirError(ERR_UNSUPPORTED)."""
+
+    _create = "bfir_engine_create_mimo"
+
+    def delay_init(self, side, max_delay, step_count=0, half_filter_length=0, kaiser_beta=9.0):
+        rc = super().delay_init(side, max_delay, step_count, half_filter_length, kaiser_beta)
+        raise BfirError(rc, "bfir_engine_delay_init")
 
 
 class BrutefirNup(Brutefir):

@@ -79,6 +79,19 @@ public:
         m_err = err;
         memset(m_last, 0, sizeof(m_last));
     }
+    // A mimo engine (bfir_engine_create_mimo): n_inputs -> n_outputs with up to BFIR_MIMO_MAXCHANNELS of each, one filter
+    // per (output, input) pair on uniform partitions.  Float frames only, no dither, no delays.  Coefficients:
+    // set_coeff_matrix(coeffs, length, coeff_blocks, scale).
+    struct mimo_io { int n_inputs, n_outputs; };
+    brutefir(int filter_length, int filter_blocks, int realsize, mimo_io io, int in_format, int out_format, int device = 0)
+        : m_channels(io.n_outputs)
+    {
+        int err = 0;
+        m_e = bfir_engine_create_mimo(filter_length, filter_blocks, realsize, io.n_inputs, io.n_outputs, in_format, out_format,
+                                      device, &err);
+        m_err = err;
+        memset(m_last, 0, sizeof(m_last));
+    }
     ~brutefir() { bfir_engine_destroy(m_e); }
     brutefir(const brutefir &) = delete;
     brutefir &operator=(const brutefir &) = delete;
@@ -144,6 +157,19 @@ public:
     {
         if (!m_e) return -1;
         return bfir_engine_set_coeff_levels(m_e, (const void *const *)coeffs, n_coeffs, length, scale);
+    }
+
+    // A mimo engine's filters: coeffs[o * n_inputs + i] the `length` taps of h_{o,i} or null (no path), at most coeff_blocks
+    // partitions of each (bfir_engine_set_coeff_matrix); and partition spectrum `block` of h_{output,input}.
+    int set_coeff_matrix(void **coeffs, int length, int coeff_blocks, double scale)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_matrix(m_e, (const void *const *)coeffs, length, coeff_blocks, scale);
+    }
+    int read_coeff_matrix(int output, int input, int block, void *dst)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_read_coeff_matrix(m_e, output, input, block, dst);
     }
 
     // A multi-level matrix engine's filters: coeffs[o * n_inputs + i] the taps of h_{o,i} or null (no path), lengths[o *
@@ -232,7 +258,7 @@ public:
     void check_overflows()
     {
         if (!m_e) return;
-        bfir_overflow of[BFIR_MAXCHANNELS];
+        bfir_overflow of[BFIR_MIMO_MAXCHANNELS];
         bool changed = false, any = false;
         for (int n = 0; n < m_channels; n++) {
             bfir_engine_get_overflow(m_e, n, &of[n]);
@@ -266,6 +292,6 @@ private:
     bfir_engine *m_e = nullptr;
     int m_channels = 0, m_err = 0;
     int m_filter_length = 0, m_realsize = 0, m_rate = -1;   // of the first constructor: what the file form of set_coeff needs
-    bfir_overflow m_last[BFIR_MAXCHANNELS];
+    bfir_overflow m_last[BFIR_MIMO_MAXCHANNELS];   // the widest kind: the outputs of a mimo engine
     bfir_log_fn m_log = nullptr;
 };

@@ -33,6 +33,7 @@ extern "C" {
 
 /* limits and sample format codes: brutefir/global.h:21-34 */
 #define BFIR_MAXCHANNELS 8
+#define BFIR_MIMO_MAXCHANNELS 64 /* inputs / outputs of bfir_engine_create_mimo: the GPU's width, not the plug-in's */
 #define BFIR_SAMPLE_FORMAT_S8 1
 #define BFIR_SAMPLE_FORMAT_S16_LE 2
 #define BFIR_SAMPLE_FORMAT_S16_BE 3
@@ -142,6 +143,29 @@ bfir_engine *bfir_engine_create_big(int filter_length, int filter_blocks, int re
  * and _read_coeff return BFIR_ERR_UNSUPPORTED on a matrix engine, the two matrix calls below the same on others. */
 bfir_engine *bfir_engine_create_matrix(int filter_length, int filter_blocks, int realsize, int n_inputs,
                                        int n_outputs, int in_format, int out_format, int device, int *err);
+
+/* A matrix engine as bfir_engine_create_matrix defines it, of up to BFIR_MIMO_MAXCHANNELS inputs and outputs ("mimo"):
+ * uniform partitions of the lengths bfir_engine_create takes for realsize, FLOAT_LE / FLOAT64_LE frames, no dither, one
+ * engine.  coeffs[o * n_inputs + i], NULL = no path.  Checked before the device is touched: a count outside 1 ...
+ * BFIR_MIMO_MAXCHANNELS is BFIR_ERR_ARG; an integer or big-endian frame format and a partition length outside the range
+ * are BFIR_ERR_UNSUPPORTED; valid arguments without a GPU give BFIR_ERR_NO_DEVICE.
+ * With unchanged meaning on it: bfir_engine_set_coeff_matrix, _read_coeff_matrix, _set_coeff_matrix_fade, _fade_remaining,
+ * _run, _run_device, _sync, _reset, _get_overflow (channel = output, 0 ... n_outputs - 1), _set_chunk, _set_profiling,
+ * _get_profile, _is_initialized, _destroy.  BFIR_ERR_UNSUPPORTED on it: the diagonal, nup, levels and matrix-levels
+ * coefficient and fade calls, and the four delay calls (the delay table holds BFIR_MAXCHANNELS channels).  A launch
+ * (bfir_engine_set_chunk) past the MAC kernel's grid is refused with BFIR_ERR_UNSUPPORTED before anything is allocated or
+ * queued; the default never gets there.
+ * Every output sample is one fma chain per (output, bin, block) -- inputs in index order, partitions in order, a filter
+ * with fewer partitions or none skipped, never multiplied by zero -- so two byte identities hold:
+ *   1. with both counts <= BFIR_MAXCHANNELS the output bytes are those of bfir_engine_create_matrix with the same arguments;
+ *   2. a matrix whose filters form blocks of at most 8 x 8 on the diagonal, with even block boundaries (channels that share
+ *      a transform on the pair path stay together), gives for each block the bytes of a bfir_engine_create_matrix engine
+ *      run on that block's channels; a diagonal matrix therefore the bytes of bfir_engine_create on each group of 8.
+ * As on every matrix engine the bytes do not depend on bfir_engine_set_chunk or on how the blocks arrive.
+ * BFIR_MIMO_MAC=0|1, read at creation, forbids or forces the wide MAC kernel (k_mac_mimo) on an engine whose counts are
+ * both <= 8, where the matrix engine's kernel can run instead: the same bits, the default is the matrix engine's. */
+bfir_engine *bfir_engine_create_mimo(int filter_length, int filter_blocks, int realsize, int n_inputs, int n_outputs,
+                                     int in_format, int out_format, int device, int *err);
 
 /* Two partition lengths in one engine ("nup": non-uniform partitioning): a long impulse response at a small block length
  * without a partition count that grows with it.  The head level convolves taps [0, D), D = head_blocks * filter_length,
