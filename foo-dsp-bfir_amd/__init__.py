@@ -7,14 +7,14 @@ from ._lib import (DELAY_INPUT, DELAY_OUTPUT, ERR_ARG, ERR_COEFF, ERR_HIP, ERR_I
                    ERR_UNSUPPORTED, BfirError, BufferFormat, Overflow, SampleFormat, MIXMODE_INPUT, MIXMODE_OUTPUT,
                    SAMPLE_FORMAT_FLOAT64_LE, SAMPLE_FORMAT_FLOAT_LE, load, library_path)
 from .convolver import Dither, FftwConvolver, TdConv
-from .engine import Brutefir, BrutefirBig, BrutefirLevels, BrutefirMatrix, BrutefirMatrixLevels, BrutefirMimo, BrutefirNup, pinned_frames, subdelay_filter
+from .engine import Brutefir, BrutefirBig, BrutefirLevels, BrutefirMatrix, BrutefirMatrixLevels, BrutefirMimo, BrutefirMimoLevels, BrutefirNup, pinned_frames, subdelay_filter
 from .equalizer import Equalizer, FftPlan
 from . import buffer
 from .resample import Resampler, resample_filter, resample_taps
 
 build = _build.build
 
-__all__ = ["Brutefir", "BrutefirBig", "BrutefirMatrix", "BrutefirMimo", "BrutefirNup", "BrutefirLevels", "BrutefirMatrixLevels", "pinned_frames", "subdelay_filter", "Resampler", "resample_filter", "resample_taps", "buffer", "DELAY_INPUT", "DELAY_OUTPUT", "FftwConvolver", "TdConv", "Dither", "Equalizer", "FftPlan", "BfirError", "BufferFormat", "Overflow", "SampleFormat",
+__all__ = ["Brutefir", "BrutefirBig", "BrutefirMatrix", "BrutefirMimo", "BrutefirNup", "BrutefirLevels", "BrutefirMatrixLevels", "BrutefirMimoLevels", "pinned_frames", "subdelay_filter", "Resampler", "resample_filter", "resample_taps", "buffer", "DELAY_INPUT", "DELAY_OUTPUT", "FftwConvolver", "TdConv", "Dither", "Equalizer", "FftPlan", "BfirError", "BufferFormat", "Overflow", "SampleFormat",
            "MIXMODE_INPUT", "MIXMODE_OUTPUT", "SAMPLE_FORMAT_FLOAT_LE", "SAMPLE_FORMAT_FLOAT64_LE",
            "build", "load", "library_path", "ERR_ARG", "ERR_COEFF", "ERR_HIP", "ERR_NO_DEVICE",
            "ERR_NONFINITE", "ERR_STATE", "ERR_UNSUPPORTED", "ERR_IO"]

@@ -82,6 +82,7 @@ SIGNATURES = {
     "bfir_engine_set_coeff_levels": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd]),
     "bfir_engine_read_coeff_levels": (_ci, [_vp, _ci, _ci, _ci, _vp]),
     "bfir_engine_create_matrix_levels": (_vp, [_ci, _ci, _pi, _pi, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
+    "bfir_engine_create_mimo_levels": (_vp, [_ci, _ci, _pi, _pi, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_set_coeff_matrix_levels": (_ci, [_vp, C.POINTER(_vp), _pi, _cd]),
     "bfir_engine_read_coeff_matrix_levels": (_ci, [_vp, _ci, _ci, _ci, _ci, _vp]),
     "bfir_engine_set_coeff_nup_fade": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd, _ci]),

@@ -12,7 +12,8 @@
 // GC = n_eng * C global channels.  A matrix engine (bfir_engine_create_matrix: one engine, C = n_in inputs, Co = n_out
 // outputs, one filter per (output, input) pair) keeps the input side -- X, tails, saved -- for its C inputs and the output
 // side -- Y, the overflow statistics, the output frames -- for its Co outputs; H is [Co][C][B][N], the MAC k_mac_matrix.
-// A mimo engine (bfir_engine_create_mimo) is a matrix engine with up to 64 of each and k_mac_mimo as its MAC.
+// A mimo engine (bfir_engine_create_mimo) is a matrix engine with up to 64 of each and k_mac_mimo as its MAC; a multi-level
+// mimo engine (bfir_engine_create_mimo_levels) a multi-level matrix engine whose levels are mimo engines.
 // A run of n blocks is cut into chunks of at most `chunk` blocks.  A chunk is front (fwd; stage_in before it on the
 // staging path), MAC and back (inv; stage_out after it on the staging path), software-pipelined over three streams.
 // What is written once here, because every path shares it: the path an engine takes (choose_path), the coefficient
@@ -208,7 +209,9 @@ struct bfir_engine {
     bool levels = false;                   // created by bfir_engine_create_levels: a kind of its own at the C ABI
     // created by bfir_engine_create_matrix_levels, a kind of its own too: the head and every tail are matrix engines -- the
     // delay lines, raw tails and pbuf count by the C inputs; the products, the time rings, tout, the overflow shards and the
-    // output frames by the Co outputs -- and every level's MAC is k_mac_matrix
+    // output frames by the Co outputs -- and every level's MAC is k_mac_matrix.  bfir_engine_create_mimo_levels makes the same
+    // with `mimo` set on every level: up to BFIR_MIMO_MAXCHANNELS of each, every level's counts in its d_nblk / d_nblk2 too,
+    // and k_mac_mimo as the MAC of every level where mimo_mac is set
     bool mlevels = false;
     // the head of a split engine: its contributing chunks take the fused back end (nup.hip, levels.hip, mlevels.hip).  A
     // diagonal engine's is its pair path; a matrix engine's is chosen by the output side alone (choose_path), whatever the
@@ -247,7 +250,8 @@ struct bfir_engine {
     int lf_mode = 0; long long lf_j1 = -1;
     bool lf_stop = false;                  // on a tail: the new set does not reach this level, it stops when the fade ends
     // Every level of a multi-level matrix engine: a launch that needs both sets of a fade runs k_mac_duo (mfade.hip) instead
-    // of k_mac_matrix twice.  BFIR_MFADE_DUO=0|1, read at creation (choose_path)
+    // of k_mac_matrix twice.  BFIR_MFADE_DUO=0|1, read at creation (choose_path).  A level with mimo_mac set: k_wduo (wduo.hip)
+    // instead of k_mac_mimo twice
     bool mfade_duo = true;
     // The channel-pair inverse with 16-byte frame stores (k_inv_quad_ps, quad.hip; InvPairArgs.quad): by default for launches
     // that fill the GPU.  BFIR_INV_QUAD=0|1 forbids it / takes it wherever it applies, read at creation (choose_path)
@@ -437,7 +441,8 @@ static void choose_path(bfir_engine *e)
             e->ilv = true;
     }
     // both sets of a fading multi-level matrix engine in one MAC launch (k_mac_duo), the default: lower than two launches of
-    // k_mac_matrix in every paired run ("Crossfades on multi-level matrix engines"); BFIR_MFADE_DUO=0 keeps the two
+    // k_mac_matrix in every paired run ("Crossfades on multi-level matrix engines"); BFIR_MFADE_DUO=0 keeps the two.
+    // The same switch and default on a level whose MAC is k_mac_mimo: k_wduo against two launches of it ("k_wduo")
     if (const char *mv = getenv("BFIR_MFADE_DUO")) e->mfade_duo = atoi(mv) != 0;
     // k_mac_matrix stays the default where it can run: k_mac_mimo was not faster there ("k_mac_mimo")
     if (e->mimo) {
@@ -702,11 +707,13 @@ static int alloc_zring(bfir_engine *e, int i, int chunk)
 
 // The head (level 0) and its tails, for arguments that have passed the checks of the two entry points below.
 // matrix: `channels` inputs and `channels_out` outputs at every level (bfir_engine_create_matrix_levels); else the two are equal
+// max_channels: the channel cap of every level, as in engine_create (bfir_engine_create_mimo_levels: every level a mimo engine)
 static bfir_engine *create_split(int filter_length, int n_levels, const int *blocks, const int *ratios, int realsize, int channels,
-                                 int channels_out, bool matrix, int in_format, int out_format, int device, int *err)
+                                 int channels_out, bool matrix, int in_format, int out_format, int device, int *err,
+                                 int max_channels = BFIR_MAXCHANNELS)
 {
     bfir_engine *e = engine_create(1, filter_length, blocks[0], realsize, channels, channels_out, matrix, in_format, out_format,
-                                   44100, 0, device, err, 1);
+                                   44100, 0, device, err, 1, 0, false, max_channels);
     if (!e) return nullptr;
     auto fail = [&](int code) { *err = code; bfir_engine_destroy(e); return (bfir_engine *)nullptr; };
     int r = 1, D = blocks[0];
@@ -714,7 +721,7 @@ static bfir_engine *create_split(int filter_length, int n_levels, const int *blo
         r *= ratios[k];
         // ceil(D_k / r) + 1 slots on top: the blocks a fade's catch-up runs again (at most that many) and their history
         bfir_engine *t = engine_create(1, r * filter_length, blocks[k], realsize, channels, channels_out, matrix, in_format,
-                                       out_format, 44100, 0, device, err, 2, (D + r - 1) / r + 1);
+                                       out_format, 44100, 0, device, err, 2, (D + r - 1) / r + 1, false, max_channels);
         if (!t) return fail(*err);
         e->tail[k - 1] = t; e->lv_r[k - 1] = r; e->lv_D[k - 1] = D; e->n_tail = k;
         D += blocks[k] * r;
@@ -823,6 +830,34 @@ extern "C" bfir_engine *bfir_engine_create_matrix_levels(int filter_length, int 
     for (int i = 0; i < e->n_tail; i++) n += snprintf(desc + n, sizeof(desc) - n, ", %d x %d", e->tail[i]->L, e->tail[i]->B);
     bfir_logf("bfir engine: matrix %d -> %d, %d levels, %s; back end %s.", e->C, e->Co, n_levels, desc,
               e->back_fused ? "fused" : "general");
+    return e;
+}
+
+// bfir_engine_create_matrix_levels with the channel cap of a mimo engine: the head and every tail are mimo engines, so a
+// level's MAC is k_mac_mimo (two sets: k_wduo) where either count passes 8 and its partition counts are tables in HBM.
+// Every refusal but BFIR_ERR_NO_DEVICE comes before the device is touched.
+extern "C" bfir_engine *bfir_engine_create_mimo_levels(int filter_length, int n_levels, const int *blocks, const int *ratios,
+                                                       int realsize, int n_inputs, int n_outputs, int in_format, int out_format,
+                                                       int device, int *err)
+{
+    int dummy;
+    if (!err) err = &dummy;
+    *err = BFIR_ERR_ARG;
+    if (n_inputs < 1 || n_inputs > BFIR_MIMO_MAXCHANNELS || n_outputs < 1 || n_outputs > BFIR_MIMO_MAXCHANNELS) {
+        bfir_logf("Number of channels (%d -> %d) exceeds limit (%d).", n_inputs, n_outputs, BFIR_MIMO_MAXCHANNELS);
+        return nullptr;
+    }
+    *err = check_levels_args(filter_length, n_levels, blocks, ratios, realsize, in_format, out_format);
+    if (*err != BFIR_OK) return nullptr;
+    bfir_engine *e = create_split(filter_length, n_levels, blocks, ratios, realsize, n_inputs, n_outputs, true, in_format, out_format,
+                                  device, err, BFIR_MIMO_MAXCHANNELS);
+    if (!e) return nullptr;
+    e->mlevels = true;
+    char desc[160];
+    int n = snprintf(desc, sizeof(desc), "%d x %d", e->L, e->B);
+    for (int i = 0; i < e->n_tail; i++) n += snprintf(desc + n, sizeof(desc) - n, ", %d x %d", e->tail[i]->L, e->tail[i]->B);
+    bfir_logf("bfir engine: mimo %d -> %d, %d levels, %s; back end %s; MAC %s.", e->C, e->Co, n_levels, desc,
+              e->back_fused ? "fused" : "general", e->mimo_mac ? "k_mac_mimo" : "k_mac_matrix");
     return e;
 }
 
@@ -1143,8 +1178,9 @@ static int set_coeff_split(bfir_engine *e, const FilterRows &rows, double scale)
             if (rc != BFIR_OK) return rc;
         }
         l->nblk = s.nb;
-        // the matrix MAC takes the counts by value (MatArgs.nblk)
+        // the matrix MAC takes the counts by value (MatArgs.nblk), k_mac_mimo from the level's table (the device is idle)
         if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
+        else if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->nblk.size(), hipMemcpyHostToDevice));
     }
     for (int i = 0; i < e->n_tail; i++) {
         const bool active = sp.lv[i + 1].nb_max > 0;
@@ -1602,10 +1638,29 @@ static MatDuoArgs matrix_duo_args(const bfir_engine *e, int base_slot, void *Y, 
     return d;
 }
 
-// ... whose grid differs from k_mac_matrix's (other time tiles): refused before anything is queued, as matrix_chunk_ok
+// ... and where the level's MAC is k_mac_mimo: k_wduo (wduo.hip), both tables in HBM
+static WduoArgs wduo_args(const bfir_engine *e, int base_slot, void *Y, void *Y2, long y2_ch_stride, int tc)
+{
+    WduoArgs d;
+    d.a = mimo_mac_args(e, base_slot, Y, tc);
+    d.h2 = e->H2; d.nblk2 = e->d_nblk2;
+    d.y2 = Y2; d.y2_ch_stride = y2_ch_stride;
+    return d;
+}
+
+// the one launch for both sets of tc blocks from base_slot on: Y as queue_mac gives it (e->chunk blocks per channel), Y2
+static int queue_duo(const bfir_engine *e, int base_slot, void *Y, void *Y2, long y2_ch_stride, int tc, hipStream_t s)
+{
+    const int rc = e->mimo_mac ? launch_wduo(wduo_args(e, base_slot, Y, Y2, y2_ch_stride, tc), s)
+                               : launch_mac_duo(matrix_duo_args(e, base_slot, Y, Y2, y2_ch_stride, tc), s);
+    return rc != 0 ? BFIR_ERR_UNSUPPORTED : BFIR_OK;
+}
+
+// ... whose grid differs from the one-set MAC's (other tiles): refused before anything is queued, as matrix_chunk_ok
 static int matrix_fade_chunk_ok(const bfir_engine *e, int tc)
 {
-    if (chunk_takes_duo(e) && !mac_duo_supported(matrix_duo_args(e, 0, nullptr, nullptr, 0, tc))) {
+    if (chunk_takes_duo(e) && !(e->mimo_mac ? wduo_supported(wduo_args(e, 0, nullptr, nullptr, 0, tc))
+                                            : mac_duo_supported(matrix_duo_args(e, 0, nullptr, nullptr, 0, tc)))) {
         bfir_logf("bfir engine: %d fading blocks per launch are past the matrix MAC's grid.", tc);
         return BFIR_ERR_UNSUPPORTED;
     }
@@ -1774,6 +1829,17 @@ static void queue_stage_out(bfir_engine *e, const Chunk &c, const void *src, lon
     a.realsize = e->s; a.L = e->L; a.max = e->of_max;
     a.overflow = e->d_of; a.of_shard_stride = e->GCo; a.bad_block = e->d_bad; a.block_base = c.block_base; a.bad_host = e->bad_host_cur;
     a.dither_tab = e->d_dither_tab; a.dither_size = e->dither_size; a.dither_state = e->d_dither_state;
+    // the kernel takes up to BFIR_MAXCHANNELS channels of a frame: the outputs of a wider engine (mimo, one engine, float
+    // frames) go in groups of that many, each a channel subset of the Co-wide frame with its own overflow records
+    for (int c0 = BFIR_MAXCHANNELS; c0 < e->Co; c0 += BFIR_MAXCHANNELS) {
+        StageOutArgs g = a;
+        g.C = std::min(BFIR_MAXCHANNELS, e->Co - c0);
+        g.raw = (char *)c.d_out + (size_t)c0 * e->out_bytes;
+        g.src = (const char *)src + (size_t)c0 * src_ch_stride * e->s;
+        g.overflow = e->d_of + c0;
+        launch_stage_out(g, st);
+    }
+    a.C = std::min(BFIR_MAXCHANNELS, e->Co);
     launch_stage_out(a, st);
 }
 
@@ -1982,7 +2048,7 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     {
         ProfScope ps(e, BFIR_K_MAC, sm);
         if (duo) {   // a multi-level matrix engine: both sets in one pass over the delay line
-            if (launch_mac_duo(matrix_duo_args(e, c.base_slot, c.Y, c.Y2, c.y2_ch_stride, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
+            if ((rc = queue_duo(e, c.base_slot, c.Y, c.Y2, c.y2_ch_stride, tc, sm)) != BFIR_OK) return rc;
         }
         else if ((rc = queue_mac(e, c.base_slot, c.Y, (long)e->chunk * e->N, tc, false, sm)) != BFIR_OK) return rc;
         // the same delay line through the same kernels with the new set, behind the first
@@ -2119,8 +2185,9 @@ static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double s
             HIP_TRY(hipMemset(l->H2, 0, n_rows * l->B * cbuf_bytes(l)));
             if (!e->matrix) l->nblk2.assign(n_rows, 1);
         }
-        // the matrix MAC takes the counts by value (MatArgs.nblk)
+        // the matrix MAC takes the counts by value (MatArgs.nblk), k_mac_mimo and k_wduo from the level's second table
         if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk2, l->nblk2.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
+        else if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk2, l->nblk2.data(), sizeof(int) * l->nblk2.size(), hipMemcpyHostToDevice));
     }
     if (e->matrix) {
         // Front end: a level pairs channels only while every input is read under BOTH sets (an input is read if any filter of
@@ -2148,7 +2215,7 @@ static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double s
     fade_begin(e, fade_blocks);
     if (e->matrix)
         bfir_logf("bfir matrix engine: crossfade over %d blocks on %d levels; a launch that needs both sets runs %s.", fade_blocks,
-                  e->n_tail + 1, chunk_takes_duo(e) ? "k_mac_duo" : "k_mac_matrix twice");
+                  e->n_tail + 1, chunk_takes_duo(e) ? (e->mimo_mac ? "k_wduo" : "k_mac_duo") : (e->mimo_mac ? "k_mac_mimo twice" : "k_mac_matrix twice"));
     return BFIR_OK;
 }
 
@@ -2542,6 +2609,16 @@ static int ensure_chunk(bfir_engine *e, int n_blocks)
     }
     // a mimo engine: a launch past k_mac_mimo's grid is refused here, before anything is allocated or queued
     if (e->mimo_mac && want > e->chunk) { const int rc = matrix_chunk_ok(e, want); if (rc != BFIR_OK) return rc; }
+    // ... and on a multi-level mimo engine one past the grid of any level's MAC, the fading form included
+    if (e->mimo && e->mlevels && want > e->chunk) {
+        for (int k = 0; k <= e->n_tail; k++) {
+            const bfir_engine *l = level(e, k);
+            const int lw = k == 0 ? want : (want + e->lv_r[k - 1] - 1) / e->lv_r[k - 1];
+            int rc = matrix_chunk_ok(l, lw);
+            if (rc == BFIR_OK && (k == 0 ? e->fade_len > 0 : l->lf_mode == 1)) rc = matrix_fade_chunk_ok(l, lw);
+            if (rc != BFIR_OK) return rc;
+        }
+    }
     if (want > e->chunk) {
         const int rc = alloc_work(e, want);
         if (rc != BFIR_OK || !e->nup) return rc;

@@ -210,6 +210,19 @@ struct MatDuoArgs {
 bool mac_duo_supported(const MatDuoArgs &d);               // the grid of the launch fits
 int launch_mac_duo(const MatDuoArgs &d, hipStream_t s);    // 0, or -1 if !mac_duo_supported(d) (nothing launched)
 
+// wduo.hip: k_wduo, the same one pass over the delay line for a level of a multi-level mimo engine
+// (bfir_engine_create_mimo_levels) -- to k_mac_duo what k_mac_mimo is to k_mac_matrix: the sums of k_mac_duo lane for lane
+// (duo_lane, mat_ops.h), both count tables in HBM, k_mac_mimo's grid.  Y and Y2 are bit for bit what launch_mac_mimo(a) and
+// launch_mac_mimo of the new set (h2, nblk2, y2, y2_ch_stride) write.
+struct WduoArgs {
+    MimoArgs a;                                              // the old set and everything both sets share
+    const void *h2;                                          // [n_out][n_in][B][N], pairs a.h_pair_stride apart as in a.h
+    const int *nblk2;                                        // device [n_out n_in], as a.nblk
+    void *y2; long y2_ch_stride;                             // [n_out][..][N]
+};
+bool wduo_supported(const WduoArgs &d);                    // the grid of the launch fits
+int launch_wduo(const WduoArgs &d, hipStream_t s);         // 0, or -1 if !wduo_supported(d) (nothing launched)
+
 // a11 + a12: inverse real FFT of Y[gc][t] (grouped layout, times in_scale),
 // first L samples to dst + gc*dst_ch_stride + t*L.
 struct InvArgs {

@@ -1,6 +1,7 @@
 // mat_ops.h -- what the matrix MAC kernels share (matrix.hip: k_mac_matrix; mfade.hip: k_mac_duo; mimo.hip: k_mac_mimo):
 // one complex multiply-add in the order of every MAC here, the load of one bin of a spectrum in either layout, and the
-// sums of one lane of k_mac_matrix and k_mac_mimo (mat_tile, mat_lane), which differ in their grids alone.
+// sums of one lane of k_mac_matrix and k_mac_mimo (mat_tile, mat_lane), which differ in their grids alone, and likewise of
+// k_mac_duo and k_wduo (wduo.hip), the two-set forms (duo_tile, duo_lane).
 #pragma once
 #include "kernels.h"
 
@@ -130,6 +131,124 @@ __device__ __forceinline__ void mat_lane(const A &a, int k, bool wave0, int o0, 
                     *(V2 *)(yo + ore) = v;
                 } else {
                     yo[ore] = ar[o][j]; yo[oim] = ai[o][j];
+                }
+            }
+        }
+    }
+}
+
+// The sums of one lane under the TWO filter sets of a crossfaded coefficient change (k_mac_duo, mfade.hip; k_wduo, wduo.hip):
+// mat_tile's loop with two H pointer sets and two count tables.  D is MatDuoArgs (the counts by value) or WduoArgs (two
+// tables in HBM): d.a.nblk / d.nblk2 [o n_in + i] either way, wave-uniform.  Per input the window of TT delay-line spectra is
+// set up ONCE and step p loads ONE new spectrum for both sets; the step loop runs to the larger of the two sets' maxima and
+// every (set, output) is guarded by its own wave-uniform p < nb.
+template <typename T, bool ILV, int NO, int TT, bool DCNY, typename D>
+__device__ __forceinline__ void duo_tile(const D &d, int o0, int t0, int ore, int oim, bool k0,
+                                         T (&ar)[2][NO][TT], T (&ai)[2][NO][TT])
+{
+    const auto &a = d.a;
+    const long N = a.N;
+    const int ring = a.ring;
+    const int sl = (a.base_slot + t0) % ring;                    // delay-line slot of block t0
+    for (int i = 0; i < a.n_in; i++) {
+        int nb[2][NO], nbm = 0, sm = 0, om = 0;
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+#pragma unroll
+            for (int o = 0; o < NO; o++) {
+                nb[s][o] = o0 + o < a.n_out ? (s ? d.nblk2 : a.nblk)[(o0 + o) * a.n_in + i] : 0;
+                if (nb[s][o] > nbm) { nbm = nb[s][o]; sm = s; om = o; }
+            }
+        if (nbm == 0) continue;                                  // no filter of this tile reads input i under either set
+        const T *__restrict__ Xi = (const T *)a.x + (long)i * a.x_ch_stride;
+        // filter spectra of (set, o, i); one without a filter is pointed at the one with nbm partitions (loaded, never used)
+        const T *__restrict__ Hp[2][NO];
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+#pragma unroll
+            for (int o = 0; o < NO; o++) {
+                const bool own = nb[s][o] > 0;
+                const T *base = (const T *)((own ? s : sm) ? d.h2 : a.h);
+                Hp[s][o] = base + ((long)(o0 + (own ? o : om)) * a.n_in + i) * a.h_pair_stride;
+            }
+        // the window of mat_tile: slot (j - p) mod TT holds X[t0 + j - p]; blocks t0 + j >= n_t only reach accumulators that
+        // are never stored
+        T wr[TT], wi[TT];
+#pragma unroll
+        for (int j = 0; j < TT; j++) {
+            int sj = sl + j; if (sj >= ring) sj -= ring;
+            mat_ld<T, ILV>(Xi + (long)sj * N, ore, oim, wr[j], wi[j]);
+        }
+        T qxr = (T)0, qxi = (T)0, qhr[2][NO], qhi[2][NO];        // operands of the next step (step 0 takes no new X)
+#pragma unroll
+        for (int s = 0; s < 2; s++)
+#pragma unroll
+            for (int o = 0; o < NO; o++) mat_ld<T, ILV>(Hp[s][o], ore, oim, qhr[s][o], qhi[s][o]);
+        for (int p0 = 0; p0 < nbm; p0 += TT) {
+#pragma unroll
+            for (int ii = 0; ii < TT; ii++) {
+                const int p = p0 + ii;
+                if (p < nbm) {                                   // wave-uniform
+                    if (p > 0) { wr[(TT - ii) % TT] = qxr; wi[(TT - ii) % TT] = qxi; }
+                    // prefetch step p + 1 (clamped to the last step: in range, not used)
+                    const int pn = p + 1 < nbm ? p + 1 : p;
+                    int sn = sl - pn; if (sn < 0) sn += ring;       // X[t0 - pn] enters the window at step pn
+                    mat_ld<T, ILV>(Xi + (long)sn * N, ore, oim, qxr, qxi);
+#pragma unroll
+                    for (int s = 0; s < 2; s++)
+#pragma unroll
+                        for (int o = 0; o < NO; o++) {
+                            if (p < nb[s][o]) {                  // wave-uniform: a (set, pair) without this partition is skipped
+#pragma unroll
+                                for (int j = 0; j < TT; j++) {
+                                    const int idx = (j - ii + TT) % TT;
+                                    mat_cmac<DCNY>(ar[s][o][j], ai[s][o][j], wr[idx], wi[idx], qhr[s][o], qhi[s][o], k0);
+                                }
+                            }
+                            const int po = pn < nb[s][o] ? pn : (nb[s][o] > 0 ? nb[s][o] - 1 : pn);
+                            mat_ld<T, ILV>(Hp[s][o] + (long)po * N, ore, oim, qhr[s][o], qhi[s][o]);
+                        }
+                }
+            }
+        }
+    }
+}
+
+// ... and the whole of that lane, as mat_lane: accumulate under both sets, then store every (set, output, block) of the tile
+// exactly once, outputs without any filter as zeros.
+template <typename T, bool ILV, int NO, int TT, typename D>
+__device__ __forceinline__ void duo_lane(const D &d, int k, bool wave0, int o0, int t0)
+{
+    const auto &a = d.a;
+    const int ore = ILV ? 2 * k : 8 * (k >> 2) + (k & 3), oim = ILV ? ore + 1 : ore + 4;
+    T ar[2][NO][TT], ai[2][NO][TT];
+#pragma unroll
+    for (int s = 0; s < 2; s++)
+#pragma unroll
+        for (int o = 0; o < NO; o++)
+#pragma unroll
+            for (int j = 0; j < TT; j++) { ar[s][o][j] = (T)0; ai[s][o][j] = (T)0; }
+    if (wave0) duo_tile<T, ILV, NO, TT, true>(d, o0, t0, ore, oim, k == 0, ar, ai);
+    else duo_tile<T, ILV, NO, TT, false>(d, o0, t0, ore, oim, false, ar, ai);
+#pragma unroll
+    for (int s = 0; s < 2; s++) {
+        T *__restrict__ Ys = (T *)(s ? d.y2 : a.y);
+        const long ch_stride = s ? d.y2_ch_stride : a.y_ch_stride;
+#pragma unroll
+        for (int o = 0; o < NO; o++) {
+            if (o0 + o >= a.n_out) break;
+            T *__restrict__ Y = Ys + (long)(o0 + o) * ch_stride;
+#pragma unroll
+            for (int j = 0; j < TT; j++) {
+                if (t0 + j < a.n_t) {
+                    T *yo = Y + (long)(t0 + j) * a.N;
+                    if constexpr (ILV) {
+                        using V2 = typename Vec2<T>::type;
+                        V2 v; v.x = ar[s][o][j]; v.y = ai[s][o][j];
+                        *(V2 *)(yo + ore) = v;
+                    } else {
+                        yo[ore] = ar[s][o][j]; yo[oim] = ai[s][o][j];
+                    }
                 }
             }
         }

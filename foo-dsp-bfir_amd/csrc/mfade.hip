@@ -11,7 +11,7 @@
 // with partition count 0 -- a NULL filter, or one that does not reach this level in that set -- is skipped, never
 // multiplied by zero.
 //
-// It is mat_tile's loop with two H pointer sets and two count tables: one lane owns one bin, a tile of TT consecutive blocks
+// It is mat_tile's loop with two H pointer sets and two count tables (duo_tile, duo_lane in mat_ops.h, shared with k_wduo): one lane owns one bin, a tile of TT consecutive blocks
 // and the accumulators of NO outputs under both sets (4 NO TT registers).  Per input the window of TT delay-line spectra is
 // set up ONCE and step p loads ONE new spectrum for both sets (two launches of k_mac_matrix do each twice); the step loop
 // runs to the larger of the two sets' maxima and every (set, output) is guarded by its own wave-uniform p < nb.  Each
@@ -26,82 +26,6 @@
 
 namespace bfir {
 
-namespace {
-
-template <typename T, bool ILV, int NO, int TT, bool DCNY>
-__device__ __forceinline__ void duo_tile(const MatDuoArgs &d, int o0, int t0, int ore, int oim, bool k0,
-                                         T (&ar)[2][NO][TT], T (&ai)[2][NO][TT])
-{
-    const MatArgs &a = d.a;
-    const long N = a.N;
-    const int ring = a.ring;
-    const int sl = (a.base_slot + t0) % ring;                    // delay-line slot of block t0
-    for (int i = 0; i < a.n_in; i++) {
-        int nb[2][NO], nbm = 0, sm = 0, om = 0;
-#pragma unroll
-        for (int s = 0; s < 2; s++)
-#pragma unroll
-            for (int o = 0; o < NO; o++) {
-                nb[s][o] = o0 + o < a.n_out ? (s ? d.nblk2 : a.nblk)[(o0 + o) * a.n_in + i] : 0;
-                if (nb[s][o] > nbm) { nbm = nb[s][o]; sm = s; om = o; }
-            }
-        if (nbm == 0) continue;                                  // no filter of this tile reads input i under either set
-        const T *__restrict__ Xi = (const T *)a.x + (long)i * a.x_ch_stride;
-        // filter spectra of (set, o, i); one without a filter is pointed at the one with nbm partitions (loaded, never used)
-        const T *__restrict__ Hp[2][NO];
-#pragma unroll
-        for (int s = 0; s < 2; s++)
-#pragma unroll
-            for (int o = 0; o < NO; o++) {
-                const bool own = nb[s][o] > 0;
-                const T *base = (const T *)((own ? s : sm) ? d.h2 : a.h);
-                Hp[s][o] = base + ((long)(o0 + (own ? o : om)) * a.n_in + i) * a.h_pair_stride;
-            }
-        // the window of mat_tile: slot (j - p) mod TT holds X[t0 + j - p]; blocks t0 + j >= n_t only reach accumulators that
-        // are never stored
-        T wr[TT], wi[TT];
-#pragma unroll
-        for (int j = 0; j < TT; j++) {
-            int sj = sl + j; if (sj >= ring) sj -= ring;
-            mat_ld<T, ILV>(Xi + (long)sj * N, ore, oim, wr[j], wi[j]);
-        }
-        T qxr = (T)0, qxi = (T)0, qhr[2][NO], qhi[2][NO];        // operands of the next step (step 0 takes no new X)
-#pragma unroll
-        for (int s = 0; s < 2; s++)
-#pragma unroll
-            for (int o = 0; o < NO; o++) mat_ld<T, ILV>(Hp[s][o], ore, oim, qhr[s][o], qhi[s][o]);
-        for (int p0 = 0; p0 < nbm; p0 += TT) {
-#pragma unroll
-            for (int ii = 0; ii < TT; ii++) {
-                const int p = p0 + ii;
-                if (p < nbm) {                                   // wave-uniform
-                    if (p > 0) { wr[(TT - ii) % TT] = qxr; wi[(TT - ii) % TT] = qxi; }
-                    // prefetch step p + 1 (clamped to the last step: in range, not used)
-                    const int pn = p + 1 < nbm ? p + 1 : p;
-                    int sn = sl - pn; if (sn < 0) sn += ring;       // X[t0 - pn] enters the window at step pn
-                    mat_ld<T, ILV>(Xi + (long)sn * N, ore, oim, qxr, qxi);
-#pragma unroll
-                    for (int s = 0; s < 2; s++)
-#pragma unroll
-                        for (int o = 0; o < NO; o++) {
-                            if (p < nb[s][o]) {                  // wave-uniform: a (set, pair) without this partition is skipped
-#pragma unroll
-                                for (int j = 0; j < TT; j++) {
-                                    const int idx = (j - ii + TT) % TT;
-                                    mat_cmac<DCNY>(ar[s][o][j], ai[s][o][j], wr[idx], wi[idx], qhr[s][o], qhi[s][o], k0);
-                                }
-                            }
-                            const int po = pn < nb[s][o] ? pn : (nb[s][o] > 0 ? nb[s][o] - 1 : pn);
-                            mat_ld<T, ILV>(Hp[s][o] + (long)po * N, ore, oim, qhr[s][o], qhi[s][o]);
-                        }
-                }
-            }
-        }
-    }
-}
-
-}  // namespace
-
 // grid: as k_mac_matrix -- x = (bin tile, time tile) through the XCD remap, y = output tile of NO outputs
 template <typename T, bool ILV, int NO, int TT>
 __global__ __launch_bounds__(256, 4) void k_mac_duo(MatDuoArgs d, int nbt, int nTT)
@@ -113,40 +37,8 @@ __global__ __launch_bounds__(256, 4) void k_mac_duo(MatDuoArgs d, int nbt, int n
     const int N2 = a.N / 2;
     if (k >= N2) return;
     const int t0 = tt * TT, o0 = blockIdx.y * NO;
-    const int ore = ILV ? 2 * k : 8 * (k >> 2) + (k & 3), oim = ILV ? ore + 1 : ore + 4;
-    T ar[2][NO][TT], ai[2][NO][TT];
-#pragma unroll
-    for (int s = 0; s < 2; s++)
-#pragma unroll
-        for (int o = 0; o < NO; o++)
-#pragma unroll
-            for (int j = 0; j < TT; j++) { ar[s][o][j] = (T)0; ai[s][o][j] = (T)0; }
     const bool wave0 = __builtin_amdgcn_readfirstlane((int)(bt == 0 && threadIdx.x < 64)) != 0;
-    if (wave0) duo_tile<T, ILV, NO, TT, true>(d, o0, t0, ore, oim, k == 0, ar, ai);
-    else duo_tile<T, ILV, NO, TT, false>(d, o0, t0, ore, oim, false, ar, ai);
-#pragma unroll
-    for (int s = 0; s < 2; s++) {
-        T *__restrict__ Ys = (T *)(s ? d.y2 : a.y);
-        const long ch_stride = s ? d.y2_ch_stride : a.y_ch_stride;
-#pragma unroll
-        for (int o = 0; o < NO; o++) {
-            if (o0 + o >= a.n_out) break;
-            T *__restrict__ Y = Ys + (long)(o0 + o) * ch_stride;
-#pragma unroll
-            for (int j = 0; j < TT; j++) {
-                if (t0 + j < a.n_t) {
-                    T *yo = Y + (long)(t0 + j) * a.N;
-                    if constexpr (ILV) {
-                        using V2 = typename Vec2<T>::type;
-                        V2 v; v.x = ar[s][o][j]; v.y = ai[s][o][j];
-                        *(V2 *)(yo + ore) = v;
-                    } else {
-                        yo[ore] = ar[s][o][j]; yo[oim] = ai[s][o][j];
-                    }
-                }
-            }
-        }
-    }
+    duo_lane<T, ILV, NO, TT>(d, k, wave0, o0, t0);
 }
 
 // Output tile NO: 2 from two outputs on (fp32), 1 (fp64), more outputs in grid y; time tile TT: 1 for the latency path (up to

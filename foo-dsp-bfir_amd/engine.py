@@ -514,6 +514,8 @@ class BrutefirMatrixLevels(BrutefirMatrix):
     run / run_device / sync / reset / overflow / check_overflows / set_chunk / set_profiling / profile / close are
     BrutefirMatrix's; reset() discards all signal state of all levels.  The crossfade of this kind is fade_to_rows."""
 
+    _create = "bfir_engine_create_matrix_levels"   # the entry point of the kind (BrutefirMimoLevels: the wider one)
+
     def __init__(self, filter_length, blocks, ratios, realsize, n_in, n_out, in_format=None, out_format=None, device=0):
         dflt = SAMPLE_FORMAT_FLOAT_LE if realsize == 4 else SAMPLE_FORMAT_FLOAT64_LE
         blocks, ratios = [int(b) for b in blocks], [int(r) for r in ratios]
@@ -529,11 +531,11 @@ class BrutefirMatrixLevels(BrutefirMatrix):
         self._lib = _lib.load()
         err = C.c_int(0)
         n = len(blocks)
-        self._h = self._lib.bfir_engine_create_matrix_levels(filter_length, n, (C.c_int * max(1, n))(*blocks),
-                                                             (C.c_int * max(1, n))(*ratios), realsize, n_in, n_out, self.in_format,
-                                                             self.out_format, device, C.byref(err))
+        self._h = getattr(self._lib, self._create)(filter_length, n, (C.c_int * max(1, n))(*blocks),
+                                                   (C.c_int * max(1, n))(*ratios), realsize, n_in, n_out, self.in_format,
+                                                   self.out_format, device, C.byref(err))
         if not self._h:
-            raise BfirError(err.value, "bfir_engine_create_matrix_levels")
+            raise BfirError(err.value, self._create)
 
     @staticmethod
     def geometry(filter_length, blocks, ratios):
@@ -586,3 +588,14 @@ class BrutefirMatrixLevels(BrutefirMatrix):
         if rc != 0:
             raise BfirError(rc, "bfir_engine_read_coeff_matrix_levels")
         return dst
+
+
+class BrutefirMimoLevels(BrutefirMatrixLevels):
+    """BrutefirMatrixLevels with up to 64 inputs and outputs (bfir_engine_create_mimo_levels): the same methods, and the
+    same bytes wherever both exist.  No delays: delay_init raises BfirError(ERR_UNSUPPORTED)."""
+
+    _create = "bfir_engine_create_mimo_levels"
+
+    def delay_init(self, side, max_delay, step_count=0, half_filter_length=0, kaiser_beta=9.0):
+        rc = super().delay_init(side, max_delay, step_count, half_filter_length, kaiser_beta)
+        raise BfirError(rc, "bfir_engine_delay_init")

@@ -92,6 +92,18 @@ public:
         m_err = err;
         memset(m_last, 0, sizeof(m_last));
     }
+    // A multi-level mimo engine (bfir_engine_create_mimo_levels): the matrix form on two to four partition lengths with up
+    // to BFIR_MIMO_MAXCHANNELS inputs and outputs.  Float frames only, no dither, no delays.  Coefficients:
+    // set_coeff_matrix_levels(coeffs, lengths, scale).
+    brutefir(int filter_length, const multi_level &levels, int realsize, mimo_io io, int in_format, int out_format, int device = 0)
+        : m_channels(io.n_outputs)
+    {
+        int err = 0;
+        m_e = bfir_engine_create_mimo_levels(filter_length, levels.n_levels, levels.blocks, levels.ratios, realsize, io.n_inputs,
+                                             io.n_outputs, in_format, out_format, device, &err);
+        m_err = err;
+        memset(m_last, 0, sizeof(m_last));
+    }
     ~brutefir() { bfir_engine_destroy(m_e); }
     brutefir(const brutefir &) = delete;
     brutefir &operator=(const brutefir &) = delete;

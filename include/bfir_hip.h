@@ -261,6 +261,43 @@ int bfir_engine_set_coeff_matrix_levels(bfir_engine *e, const void *const *coeff
 /* partition spectrum `block` of h_{output,input} on level `level`: 2 L_level reals, grouped layout */
 int bfir_engine_read_coeff_matrix_levels(bfir_engine *e, int level, int output, int input, int block, void *dst);
 
+/* bfir_engine_create_matrix_levels with the channel cap of bfir_engine_create_mimo: n_inputs -> n_outputs with up to
+ * BFIR_MIMO_MAXCHANNELS of each, every filter on the same two to four partition lengths -- long room responses at a short
+ * block length through one wide matrix (the reference stops at BF_MAXCHANNELS, brutefir/global.h:21, and at uniform
+ * partitions, brutefir/brutefir.cpp:738-810).  The head and every tail level are mimo engines; FLOAT_LE / FLOAT64_LE frames,
+ * no dither, one engine.  Checked before the device is touched, in this order: a count outside 1 ... BFIR_MIMO_MAXCHANNELS
+ * is BFIR_ERR_ARG; whatever bfir_engine_create_levels refuses about filter_length, n_levels, blocks, ratios and realsize
+ * keeps its code; an integer or big-endian frame format is BFIR_ERR_UNSUPPORTED; valid arguments without a GPU give
+ * BFIR_ERR_NO_DEVICE.  Device memory that does not suffice: BFIR_ERR_HIP, everything already allocated freed.  The filters
+ * alone take
+ *   n_inputs * n_outputs * 2 * realsize * D_(n_levels)  bytes,  D_(n_levels) = sum_k blocks[k] * L_k  the capacity in taps,
+ * and twice that from the first crossfade on (64 x 64, fp32, 65536 taps: 2 GiB per set); beside them every level keeps a
+ * delay line of n_inputs * (2 chunk_k + blocks[k] + ceil(D_k / L_k) + 1) spectra and two product buffers of n_outputs *
+ * chunk_k spectra of 2 L_k reals, chunk_k = ceil(blocks per launch / (L_k / L_0)).
+ * With unchanged meaning on it: bfir_engine_set_coeff_matrix_levels, _read_coeff_matrix_levels,
+ * _set_coeff_matrix_levels_fade, _fade_remaining_levels, _run, _run_device, _sync, _reset, _get_overflow (channel = output,
+ * 0 ... n_outputs - 1), _set_chunk, _set_profiling, _get_profile, _is_initialized, _destroy.  BFIR_ERR_UNSUPPORTED on it:
+ * every other coefficient, read and fade call, and the four delay calls (the delay table holds BFIR_MAXCHANNELS channels).
+ * A launch (bfir_engine_set_chunk) past the grid of any level's MAC kernel, the one of a fading launch included, is refused
+ * with BFIR_ERR_UNSUPPORTED before anything is allocated or queued; the default never gets there.
+ * A level's MAC is k_mac_mimo where either count passes BFIR_MAXCHANNELS; within it the matrix engine's kernel unless
+ * BFIR_MIMO_MAC=1 (the same bits).  The chain of bfir_engine_create_mimo holds per level, so:
+ *   1. with both counts <= BFIR_MAXCHANNELS the output bytes are those of bfir_engine_create_matrix_levels with the same
+ *      arguments, plain and through a crossfade;
+ *   2. filters that all end at or before D_1 give the bytes of bfir_engine_create_mimo(L_0, blocks[0], ...);
+ *   3. a matrix whose filters form blocks of at most 8 x 8 on the diagonal, every block with even input and output counts
+ *      and every block with taps on the same levels, gives for each block the bytes of a bfir_engine_create_matrix_levels
+ *      engine run on that block's channels and lengths (a block without taps on a level that another block reaches has that
+ *      level's zeros ADDED to its samples, which turns a sample of -0.0 into +0.0);
+ *   4. the bytes do not depend on bfir_engine_set_chunk, on how the blocks arrive (one call, many, one block at a time on
+ *      the latency path, host or device pointers), or on BFIR_MFADE_DUO.
+ * BFIR_MFADE_DUO=0|1, read at creation: a launch of a level that needs both filter sets of a crossfade runs the level's MAC
+ * twice (0) or both sets in one pass over the delay line (1: k_mac_duo, or k_wduo on a level whose MAC is k_mac_mimo).  The
+ * default is 1 on every level: the one pass was the faster form in the measurements of both kernels. */
+bfir_engine *bfir_engine_create_mimo_levels(int filter_length, int n_levels, const int *blocks, const int *ratios,
+                                            int realsize, int n_inputs, int n_outputs, int in_format, int out_format,
+                                            int device, int *err);
+
 void bfir_engine_destroy(bfir_engine *e);
 
 /* brutefir::is_initialized */
