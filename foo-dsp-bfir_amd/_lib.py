@@ -74,6 +74,8 @@ SIGNATURES = {
     "bfir_engine_read_coeff_matrix": (_ci, [_vp, _ci, _ci, _ci, _vp]),
     "bfir_engine_set_coeff_fade": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _ci, _cd, _ci]),
     "bfir_engine_set_coeff_matrix_fade": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd, _ci]),
+    "bfir_engine_set_coeff_matrix_pairs": (_ci, [_vp, _ci, _pi, _pi, C.POINTER(_vp), _ci, _ci, _cd]),
+    "bfir_engine_set_coeff_matrix_pairs_fade": (_ci, [_vp, _ci, _pi, _pi, C.POINTER(_vp), _ci, _ci, _cd, _ci]),
     "bfir_engine_fade_remaining": (_ci, [_vp]),
     "bfir_engine_create_nup": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_set_coeff_nup": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd]),

@@ -174,6 +174,12 @@ struct bfir_engine {
     float fade_f = 0.f; double fade_d = 0.0;   // 1 / (real)(fade_len L - 1) as the reference computes it (:298, :308)
     bool fade_fused = false;               // k_inv_fade serves this engine (fp32 pairs, FLOAT_LE out, a plan of 2L points)
     bool pair_new = false;                 // matrix engines: the path the NEW set alone asks for (after the fade)
+    // the fade is a patch (bfir_engine_set_coeff_matrix_pairs_fade): H2 is H with a list of pairs replaced, and a fade chunk
+    // runs k_patch_pairs (patch.hip) over d_patch, the table of the listed pairs, behind the old set's MAC instead of the MAC
+    // with H2.  Every way a fade ends clears it (fade_swap_sets, a plain set call), and so does fade_begin for every fade:
+    // the pairs call sets it behind fade_begin
+    bool fade_patch = false;
+    int *d_patch = nullptr; size_t patch_ints = 0;   // [Co + 1] row starts, then [entries][3]: input, nb_new, nb_old (PatchArgs)
     void *Yf[2] = {nullptr, nullptr};      // products with H2: [GCo][yf_blocks][N], one per chunk parity like Yb
     int yf_blocks = 0;
     void *ft[2] = {nullptr, nullptr};      // general back end: planar y_old / y_new, [GCo][ft_blocks][L] each
@@ -880,7 +886,7 @@ extern "C" void bfir_engine_destroy(bfir_engine *e)
     big_plan_destroy(&e->bplan);
     for (int st = 0; st < 2; st++) for (int i = 0; i < 2; i++) if (e->tails[st][i]) (void)hipFree(e->tails[st][i]);
     void *bufs[] = {e->H, e->saved[0], e->saved[1], e->d_nblk, e->d_of, e->d_bad, e->d_dither_tab, e->d_dither_state,
-                    e->H2, e->d_nblk2, e->Yf[0], e->Yf[1], e->ft[0], e->ft[1]};
+                    e->H2, e->d_nblk2, e->Yf[0], e->Yf[1], e->ft[0], e->ft[1], e->d_patch};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (auto &sp : e->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -1086,6 +1092,16 @@ static void matrix_take_path(bfir_engine *e, bool pair)
     e->pair = pair; e->direct = !pair;
 }
 
+// The partition counts of a uniform matrix engine's active set are new in e->nblk (the device is idle): k_mac_mimo's table,
+// the path, and the engine has its coefficients.
+static int matrix_counts_set(bfir_engine *e)
+{
+    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk, e->nblk.data(), sizeof(int) * e->nblk.size(), hipMemcpyHostToDevice));
+    if (e->pair_cap) matrix_take_path(e, every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
+    e->eng_init[0] = 1;
+    return BFIR_OK;
+}
+
 // the n_out x n_in filters of a matrix engine: coeffs[o n_in + i], NULL = no path from input i to output o
 extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *coeffs, int length, int coeff_blocks,
                                             double scale)
@@ -1096,6 +1112,7 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     e->fade_len = e->fade_pos = 0;                              // a plain change during a fade cancels it
+    e->fade_patch = false;
     e->eng_init[0] = 0;
     const int nb = std::min(coeff_blocks, e->B);
     const FilterRows rows = matrix_rows(e, coeffs, nullptr, length);
@@ -1103,11 +1120,7 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
     if (rc == BFIR_OK) rc = load_filters(e, e->H, 0, rows, nb, scale);
     if (rc != BFIR_OK) return rc;
     for (size_t n = 0; n < rows.taps.size(); n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
-    // ... k_mac_mimo from its table (the device is idle)
-    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk, e->nblk.data(), sizeof(int) * e->nblk.size(), hipMemcpyHostToDevice));
-    if (e->pair_cap) matrix_take_path(e, every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
-    e->eng_init[0] = 1;
-    return BFIR_OK;
+    return matrix_counts_set(e);
 }
 
 // The rows of a set call on a split engine, cut at every D_k: level k (0: the head) gets taps [D_k, D_(k+1)) of every row
@@ -1269,6 +1282,7 @@ static void fade_swap_sets(bfir_engine *e)
     std::swap(e->d_nblk, e->d_nblk2);
     std::swap(e->nblk, e->nblk2);
     e->fade_len = e->fade_pos = 0;
+    e->fade_patch = false;
     if (e->matrix && e->pair_cap) matrix_take_path(e, e->pair_new);
     if (e->nup) lfade_finish(e, true);
 }
@@ -1309,6 +1323,7 @@ static void fade_begin(bfir_engine *e, int fade_blocks)
     e->fade_f = (float)(1.0 / (double)(float)(fade_blocks * e->L - 1));
     e->fade_d = 1.0 / (double)(fade_blocks * e->L - 1);
     e->fade_len = fade_blocks; e->fade_pos = 0;
+    e->fade_patch = false;                                      // a pairs fade sets it behind this call
 }
 
 // a uniform engine, diagonal (coeffs[n] for channel n < n_coeffs) or matrix (coeffs[o n_in + i], NULL = no path)
@@ -1360,6 +1375,136 @@ extern "C" int bfir_engine_set_coeff_matrix_fade(bfir_engine *e, const void *con
     if (!e) return BFIR_ERR_ARG;
     if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;
     return set_coeff_fade(e, coeffs, 0, length, coeff_blocks, scale, fade_blocks);
+}
+
+// ---------------------------------------------------------------------------
+// a list of (output, input) pairs of a uniform matrix or mimo engine replaced: bfir_engine_set_coeff_matrix_pairs, _fade
+// ---------------------------------------------------------------------------
+namespace {
+struct PairList {
+    FilterRows rows;             // the listed filters in list order, all of `length` taps (NULL: the path is removed)
+    std::vector<int> row;        // where each goes: filter o C + i
+};
+}
+
+// What both pairs calls ask of their list; host arithmetic alone.
+static int pairs_list(const bfir_engine *e, int n_pairs, const int *outputs, const int *inputs, const void *const *coeffs, int length,
+                      int coeff_blocks, PairList &pl)
+{
+    if (!outputs || !inputs || !coeffs || n_pairs < 1 || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
+    std::vector<char> listed((size_t)e->Co * e->C, 0);
+    pl.rows = FilterRows((size_t)n_pairs);
+    pl.row.resize((size_t)n_pairs);
+    for (int k = 0; k < n_pairs; k++) {
+        if (outputs[k] < 0 || outputs[k] >= e->Co || inputs[k] < 0 || inputs[k] >= e->C) return BFIR_ERR_ARG;
+        const int n = outputs[k] * e->C + inputs[k];
+        if (listed[n]) return BFIR_ERR_ARG;                     // the same pair twice
+        listed[n] = 1;
+        pl.row[k] = n; pl.rows.taps[k] = coeffs[k]; pl.rows.len[k] = coeffs[k] ? length : 0;
+    }
+    return BFIR_OK;
+}
+
+// The listed filters into Hdst (H, or H2 holding a copy of H), nb partitions each as load_filters gives them; the row of a
+// removed path reads as zeros, as bfir_engine_set_coeff_matrix leaves the row of a NULL.  The spectrum of a row does not
+// depend on the rows transformed with it (one workgroup per row and partition, k_fwd's planar form), so row by row gives
+// the bytes of the whole matrix in one call.
+static int load_pairs(bfir_engine *e, void *Hdst, const PairList &pl, int nb, double scale)
+{
+    const size_t row_bytes = (size_t)e->B * cbuf_bytes(e);
+    for (size_t k = 0; k < pl.row.size(); k++) {
+        if (!pl.rows.taps[k]) {   // on the stream that owns every write to the store
+            HIP_TRY(hipMemsetAsync((char *)Hdst + (size_t)pl.row[k] * row_bytes, 0, row_bytes, e->stream));
+            continue;
+        }
+        FilterRows one(1);
+        one.taps[0] = pl.rows.taps[k]; one.len[0] = pl.rows.len[k];
+        const int rc = load_filters(e, Hdst, pl.row[k], one, nb, scale);
+        if (rc != BFIR_OK) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_pairs(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                  const void *const *coeffs, int length, int coeff_blocks, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    PairList pl;
+    int rc = pairs_list(e, n_pairs, outputs, inputs, coeffs, length, coeff_blocks, pl);
+    if (rc != BFIR_OK) return rc;
+    if (!bfir_engine_is_initialized(e)) return BFIR_ERR_STATE;   // nothing to patch
+    const int nb = std::min(coeff_blocks, e->B);
+    // a NaN / Inf tap is refused before anything is uploaded: the engine keeps its filters, and a fade goes on
+    rc = check_rows(e, pl.rows, (size_t)nb * e->L, scale);
+    if (rc != BFIR_OK) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    e->fade_len = e->fade_pos = 0;                              // during a fade: a hard cut, the old set stays and is patched
+    e->fade_patch = false;
+    rc = load_pairs(e, e->H, pl, nb, scale);
+    if (rc != BFIR_OK) return rc;
+    for (size_t k = 0; k < pl.row.size(); k++) e->nblk[pl.row[k]] = coeffs[k] ? nb : 0;
+    return matrix_counts_set(e);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_pairs_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                       const void *const *coeffs, int length, int coeff_blocks, double scale,
+                                                       int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (e->n_eng > 1 || e->d_dither_tab) return BFIR_ERR_UNSUPPORTED;   // as every fade: HP-TPDF dither is a recursion over the output
+    PairList pl;
+    int rc = pairs_list(e, n_pairs, outputs, inputs, coeffs, length, coeff_blocks, pl);
+    if (rc == BFIR_OK) rc = check_fade_args(e, fade_blocks);
+    if (rc != BFIR_OK) return rc;
+    const int nb = std::min(coeff_blocks, e->B);
+    rc = check_rows(e, pl.rows, (size_t)nb * e->L, scale);
+    if (rc != BFIR_OK) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    // queued work may still read what was H before the last fade's swap, or the table: both are written on an idle device
+    HIP_TRY(hipDeviceSynchronize());
+    const size_t P = (size_t)e->Co * e->C;
+    rc = fade_prepare(e, (int)P);
+    if (rc != BFIR_OK) return rc;
+    // the merged set: the whole store copied, then the listed rows -- the copy on the stream the rows are loaded on (a
+    // non-blocking stream: a copy on the null stream would not be ordered before them, nor waited for by the host), and
+    // complete before the first row is written
+    HIP_TRY(hipMemcpyAsync(e->H2, e->H, P * e->B * cbuf_bytes(e), hipMemcpyDeviceToDevice, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    rc = load_pairs(e, e->H2, pl, nb, scale);
+    if (rc != BFIR_OK) return rc;
+    e->nblk2 = e->nblk;
+    for (size_t k = 0; k < pl.row.size(); k++) e->nblk2[pl.row[k]] = coeffs[k] ? nb : 0;
+    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->nblk2.size(), hipMemcpyHostToDevice));
+    // k_patch_pairs' table: per output its listed pairs in input order
+    std::vector<char> listed(P, 0);
+    for (int n : pl.row) listed[n] = 1;
+    std::vector<int> tab((size_t)e->Co + 1);
+    for (int o = 0; o < e->Co; o++) {
+        tab[o] = (int)(tab.size() - (e->Co + 1)) / 3;
+        for (int i = 0; i < e->C; i++) {
+            const int n = o * e->C + i;
+            if (listed[n]) { tab.push_back(i); tab.push_back(e->nblk2[n]); tab.push_back(e->nblk[n]); }
+        }
+    }
+    tab[e->Co] = (int)pl.row.size();
+    if (tab.size() > e->patch_ints) {
+        if (e->d_patch) (void)hipFree(e->d_patch);
+        e->d_patch = nullptr; e->patch_ints = 0;
+        HIP_TRY(hipMalloc((void **)&e->d_patch, sizeof(int) * tab.size()));
+        e->patch_ints = tab.size();
+    }
+    HIP_TRY(hipMemcpy(e->d_patch, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    if (e->pair_cap) {   // set_coeff_fade's rule: channel pairs only while every input is read under BOTH sets
+        e->pair_new = every_input_read(e, [&](int, int n) { return e->nblk2[n]; });
+        matrix_take_path(e, e->pair_new && every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
+    }
+    fade_begin(e, fade_blocks);
+    e->fade_patch = true;
+    return BFIR_OK;
 }
 
 extern "C" int bfir_engine_fade_remaining(const bfir_engine *e)
@@ -1662,6 +1807,30 @@ static int matrix_fade_chunk_ok(const bfir_engine *e, int tc)
     if (chunk_takes_duo(e) && !(e->mimo_mac ? wduo_supported(wduo_args(e, 0, nullptr, nullptr, 0, tc))
                                             : mac_duo_supported(matrix_duo_args(e, 0, nullptr, nullptr, 0, tc)))) {
         bfir_logf("bfir engine: %d fading blocks per launch are past the matrix MAC's grid.", tc);
+        return BFIR_ERR_UNSUPPORTED;
+    }
+    return BFIR_OK;
+}
+
+// The new set's products of a patch fade's chunk from the old set's (k_patch_pairs, patch.hip), behind the old set's MAC
+static PatchArgs patch_args(const bfir_engine *e, int base_slot, void *Y, void *Y2, long y2_ch_stride, int tc)
+{
+    PatchArgs a;
+    a.x = e->X; a.x_ch_stride = (long)e->ring * e->N; a.ring = e->ring; a.base_slot = base_slot;
+    a.h = e->H; a.h2 = e->H2; a.h_pair_stride = (long)e->B * e->N;
+    a.row = e->d_patch; a.ent = e->d_patch + e->Co + 1;
+    a.y = Y; a.y_ch_stride = (long)e->chunk * e->N;
+    a.y2 = Y2; a.y2_ch_stride = y2_ch_stride;
+    a.n_t = tc; a.n_in = e->C; a.n_out = e->Co; a.N = e->N; a.realsize = e->s;
+    a.interleaved = e->ilv;
+    return a;
+}
+
+// ... whose grid is its own: refused before anything is queued, as matrix_fade_chunk_ok
+static int patch_chunk_ok(const bfir_engine *e, int tc)
+{
+    if (!patch_supported(patch_args(e, 0, nullptr, nullptr, 0, tc))) {
+        bfir_logf("bfir engine: %d fading blocks per launch are past the pair-list kernel's grid.", tc);
         return BFIR_ERR_UNSUPPORTED;
     }
     return BFIR_OK;
@@ -2025,6 +2194,8 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     if (both) { c.Y2 = e->Yf[e->pipe3 ? par : 0]; c.y2_ch_stride = (long)e->yf_blocks * e->N; c.m0 = e->fade_pos * e->L; }
     const bool duo = both && chunk_takes_duo(e);
     if (duo) { rc = matrix_fade_chunk_ok(e, tc); if (rc != BFIR_OK) return rc; }
+    const bool patch = c.fade && e->fade_patch;                 // a pair list fades: the new set's products from the old set's
+    if (patch) { rc = patch_chunk_ok(e, tc); if (rc != BFIR_OK) return rc; }
     rc = chunk_aligned(e, p, c);
     if (rc != BFIR_OK) return rc;
     if (c.fade && e->fade_fused && (((uintptr_t)d_out | (uintptr_t)out_stride) & 3)) {
@@ -2052,7 +2223,10 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
         }
         else if ((rc = queue_mac(e, c.base_slot, c.Y, (long)e->chunk * e->N, tc, false, sm)) != BFIR_OK) return rc;
         // the same delay line through the same kernels with the new set, behind the first
-        if (both && !duo && (rc = queue_mac(e, c.base_slot, c.Y2, c.y2_ch_stride, tc, true, sm)) != BFIR_OK) return rc;
+        if (patch) {
+            if (launch_patch(patch_args(e, c.base_slot, c.Y, c.Y2, c.y2_ch_stride, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
+        }
+        else if (both && !duo && (rc = queue_mac(e, c.base_slot, c.Y2, c.y2_ch_stride, tc, true, sm)) != BFIR_OK) return rc;
     }
     if (!il) {
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));

@@ -223,6 +223,25 @@ struct WduoArgs {
 bool wduo_supported(const WduoArgs &d);                    // the grid of the launch fits
 int launch_wduo(const WduoArgs &d, hipStream_t s);         // 0, or -1 if !wduo_supported(d) (nothing launched)
 
+// patch.hip: k_patch_pairs, the new set's products of a fade that replaces a list of pairs of a matrix or mimo engine
+// (bfir_engine_set_coeff_matrix_pairs_fade), from the old set's products y, which launch_mac_matrix / launch_mac_mimo has
+// just written:  Y2[o][t] = Y[o][t] + sum over the listed pairs (o, i) of row o, in input order, of
+//   sum_{p < nb_new} X[i][slot(t - p)] * H2[o][i][p]  -  sum_{p < nb_old} X[i][slot(t - p)] * H[o][i][p]
+// continuing ONE fma chain per (output, bin, block): the new filter's terms first, then the old filter's with H negated.  A
+// row without listed pairs is copied; a pair without partitions in a set causes no loads for that set.
+struct PatchArgs {
+    const void *x; long x_ch_stride; int ring, base_slot;     // delay line [n_in][ring][N]
+    const void *h, *h2; long h_pair_stride;                   // old and new set, [n_out][n_in][B][N] each
+    const int *row;                                           // device [n_out + 1]: the entries of row o are row[o] .. row[o + 1] - 1
+    const int *ent;                                           // device [entries][3]: input, nb_new, nb_old; wave-uniform reads
+    const void *y; long y_ch_stride;                          // [n_out][..][N], read
+    void *y2; long y2_ch_stride;                              // [n_out][..][N], written
+    int n_t, n_in, n_out, N, realsize;
+    int interleaved;                                          // layout of x, h, h2, y and y2, as in FwdArgs
+};
+bool patch_supported(const PatchArgs &a);                   // the grid of the launch fits
+int launch_patch(const PatchArgs &a, hipStream_t s);        // 0, or -1 if !patch_supported(a) (nothing launched)
+
 // a11 + a12: inverse real FFT of Y[gc][t] (grouped layout, times in_scale),
 // first L samples to dst + gc*dst_ch_stride + t*L.
 struct InvArgs {

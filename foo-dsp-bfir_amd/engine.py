@@ -337,6 +337,31 @@ class BrutefirMatrix(Brutefir):
         return self._lib.bfir_engine_set_coeff_matrix_fade(self._h, ptrs, length, coeff_blocks, float(scale),
                                                            int(fade_blocks))
 
+    def _pair_args(self, pairs, filters, length, coeff_blocks):
+        """The list arguments of the two pairs calls; the arrays are returned too, to keep them alive over the call."""
+        assert len(pairs) == len(filters)
+        rd = _real_dtype(self.s)
+        arrs = [None if h is None else np.ascontiguousarray(h, dtype=rd) for h in filters]
+        given = [a for a in arrs if a is not None]
+        length = (given[0].size if given else 0) if length is None else length
+        coeff_blocks = self.B if coeff_blocks is None else coeff_blocks
+        assert all(a.size >= length for a in given), "every filter of a pairs call holds `length` taps"
+        outs = (C.c_int * len(pairs))(*[int(o) for o, _ in pairs])
+        ins = (C.c_int * len(pairs))(*[int(i) for _, i in pairs])
+        ptrs = (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
+        return (len(pairs), outs, ins, ptrs, length, coeff_blocks), arrs
+
+    def set_coeff_pairs(self, pairs, filters, length=None, coeff_blocks=None, scale=1.0):
+        """bfir_engine_set_coeff_matrix_pairs: filters[k] (taps in working precision, or None = the path is removed)
+        replaces h_{o,i} for pairs[k] = (o, i); every other pair keeps its filter.  Returns 0 or an ERR_* code."""
+        args, _keep = self._pair_args(pairs, filters, length, coeff_blocks)
+        return self._lib.bfir_engine_set_coeff_matrix_pairs(self._h, *args, float(scale))
+
+    def set_coeff_pairs_fade(self, pairs, filters, fade_blocks, length=None, coeff_blocks=None, scale=1.0):
+        """bfir_engine_set_coeff_matrix_pairs_fade: the same change, crossfaded over the next `fade_blocks` blocks."""
+        args, _keep = self._pair_args(pairs, filters, length, coeff_blocks)
+        return self._lib.bfir_engine_set_coeff_matrix_pairs_fade(self._h, *args, float(scale), int(fade_blocks))
+
     def run(self, inbuf, outbuf=None):
         """inbuf: [n_blocks*L, n_in] frames in the input format.  Returns (rc, outbuf [n_blocks*L, n_out])."""
         x = np.ascontiguousarray(inbuf, dtype=_FMT_DTYPES[self.in_format])

@@ -183,6 +183,23 @@ public:
         if (!m_e) return -1;
         return bfir_engine_read_coeff_matrix(m_e, output, input, block, dst);
     }
+    // A list of a mimo engine's pairs replaced: coeffs[k] the new h_{outputs[k],inputs[k]} or null (the path is removed), every
+    // other pair keeps its filter (bfir_engine_set_coeff_matrix_pairs); and the same change crossfaded over the next
+    // fade_blocks blocks (bfir_engine_set_coeff_matrix_pairs_fade).
+    int set_coeff_matrix_pairs(int n_pairs, const int *outputs, const int *inputs, void **coeffs, int length, int coeff_blocks,
+                               double scale)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_matrix_pairs(m_e, n_pairs, outputs, inputs, (const void *const *)coeffs, length, coeff_blocks,
+                                                  scale);
+    }
+    int set_coeff_matrix_pairs_fade(int n_pairs, const int *outputs, const int *inputs, void **coeffs, int length, int coeff_blocks,
+                                    double scale, int fade_blocks)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_matrix_pairs_fade(m_e, n_pairs, outputs, inputs, (const void *const *)coeffs, length,
+                                                       coeff_blocks, scale, fade_blocks);
+    }
 
     // A multi-level matrix engine's filters: coeffs[o * n_inputs + i] the taps of h_{o,i} or null (no path), lengths[o *
     // n_inputs + i] its tap count, each filter split between the levels (bfir_engine_set_coeff_matrix_levels).

@@ -348,6 +348,38 @@ int bfir_engine_set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_
  * feeds an output under BOTH sets; after the fade the new set decides. */
 int bfir_engine_set_coeff_matrix_fade(bfir_engine *e, const void *const *coeffs, int length,
                                       int coeff_blocks, double scale, int fade_blocks);
+/* A LIST of pairs of a matrix engine replaced (bfir_engine_create_matrix, bfir_engine_create_mimo): coeffs[k], k < n_pairs,
+ * is the new h_{outputs[k], inputs[k]}, `length` taps in working precision, or NULL = the path is removed; length /
+ * coeff_blocks / scale as bfir_engine_set_coeff_matrix.  The MERGED set is the active set with exactly the listed pairs
+ * replaced: every other pair keeps its spectra and its partition count byte for byte, and only the listed filters are
+ * uploaded and transformed.  One moving source of a 64 x 64 renderer is one column: 64 filters out of 4096.
+ * The plain call leaves the engine, byte for byte, as bfir_engine_set_coeff_matrix with the merged set would: filter store,
+ * partition counts and the choice between the channel-pair and the direct path.  The delay line is kept.  During a fade it
+ * cancels the fade (the old set stays active) and then patches the old set.
+ * The fade call is bfir_engine_set_coeff_matrix_fade with the merged set as the new set -- the same blocks t0 .. t0 + K - 1,
+ * blend and f, bfir_engine_fade_remaining, bfir_engine_read_coeff_matrix reading the old set until the fade's last block
+ * is queued, a plain set call cancelling it, bfir_engine_reset ending it with the merged set active, the pair-path rule --
+ * with one difference: during the fade y_new is NOT the new set's own fma chain.  Its spectra are the old set's products
+ * plus the listed pairs' difference,
+ *     Y2[o] = Y[o] + sum over the listed (o, i), in input order, of
+ *             ( sum_{p < nb_new} X_i[t - p] H2_{o,i,p}  -  sum_{p < nb_old} X_i[t - p] H_{o,i,p} ),
+ * the new filter's terms first, then the old filter's, in one fma chain behind Y[o].  So the fading blocks agree with those
+ * of bfir_engine_set_coeff_matrix_fade to the merged set within rounding, NOT bitwise; an output without a listed pair is
+ * blended with itself (y_new = y_old bitwise).  Before t0 the bytes are those of an engine that was never patched; from
+ * t0 + K on those of an engine that faded to the merged set with bfir_engine_set_coeff_matrix_fade.  As every fade, the
+ * output does not depend on how the blocks arrive.  A listed pair without a filter in either set is never loaded: nothing is
+ * multiplied by zero, an input no filter reads keeps its NaN to itself.
+ * All refusals come before the device is touched and change nothing.  BFIR_ERR_ARG: a null e, outputs, inputs or coeffs;
+ * n_pairs < 1; an index outside the matrix; the same pair listed twice; length < 0; coeff_blocks < 1; for the fade,
+ * fade_blocks < 1 or K L > 2^24.  BFIR_ERR_STATE: an engine without coefficients; for the fade, a fade pending or running.
+ * BFIR_ERR_UNSUPPORTED: an engine of any other kind (diagonal, batch, two-level, multi-level, multi-level matrix or mimo);
+ * for the fade, an engine that dithers its output.  BFIR_ERR_COEFF: a NaN/Inf tap, found before anything is uploaded -- the
+ * engine keeps its filters and, unlike after bfir_engine_set_coeff_matrix, stays initialised. */
+int bfir_engine_set_coeff_matrix_pairs(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                       const void *const *coeffs, int length, int coeff_blocks, double scale);
+int bfir_engine_set_coeff_matrix_pairs_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                            const void *const *coeffs, int length, int coeff_blocks, double scale,
+                                            int fade_blocks);
 /* Blocks of a pending or running fade still to be processed; 0 = none.  < 0: error. */
 int bfir_engine_fade_remaining(const bfir_engine *e);
 
