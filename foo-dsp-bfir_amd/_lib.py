@@ -90,6 +90,8 @@ SIGNATURES = {
     "bfir_engine_set_coeff_nup_fade": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd, _ci]),
     "bfir_engine_set_coeff_levels_fade": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd, _ci]),
     "bfir_engine_set_coeff_matrix_levels_fade": (_ci, [_vp, C.POINTER(_vp), _pi, _cd, _ci]),
+    "bfir_engine_set_coeff_matrix_levels_pairs": (_ci, [_vp, _ci, _pi, _pi, C.POINTER(_vp), _pi, _cd]),
+    "bfir_engine_set_coeff_matrix_levels_pairs_fade": (_ci, [_vp, _ci, _pi, _pi, C.POINTER(_vp), _pi, _cd, _ci]),
     "bfir_engine_fade_remaining_levels": (_ci, [_vp]),
     "bfir_subdelay_filter": (_ci, [_ci, _ci, _ci, _cd, _ci, _vp]),
     "bfir_engine_delay_init": (_ci, [_vp, _ci, _ci, _ci, _ci, _cd]),

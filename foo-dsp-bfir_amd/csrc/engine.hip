@@ -180,6 +180,12 @@ struct bfir_engine {
     // the pairs call sets it behind fade_begin
     bool fade_patch = false;
     int *d_patch = nullptr; size_t patch_ints = 0;   // [Co + 1] row starts, then [entries][3]: input, nb_new, nb_old (PatchArgs)
+    // A multi-level matrix or mimo engine (bfir_engine_set_coeff_matrix_levels_pairs_fade): fade_patch is set on the head and
+    // on every active tail, each level with a table of its own in its d_patch (the counts are per level), and a launch that
+    // needs both sets -- the head while it fades, a tail in lf_mode 1 -- runs the patch behind the old set's MAC instead of
+    // k_mac_duo / k_wduo.  lfade_finish clears it on the tails.  patch_fused: on a level whose MAC is k_mac_mimo the two
+    // launches are one, k_wpatch (wpatch.hip), the same bits; BFIR_PATCH_FUSED=0|1, read at creation (choose_path)
+    bool patch_fused = false;
     void *Yf[2] = {nullptr, nullptr};      // products with H2: [GCo][yf_blocks][N], one per chunk parity like Yb
     int yf_blocks = 0;
     void *ft[2] = {nullptr, nullptr};      // general back end: planar y_old / y_new, [GCo][ft_blocks][L] each
@@ -450,6 +456,9 @@ static void choose_path(bfir_engine *e)
     // k_mac_matrix in every paired run ("Crossfades on multi-level matrix engines"); BFIR_MFADE_DUO=0 keeps the two.
     // The same switch and default on a level whose MAC is k_mac_mimo: k_wduo against two launches of it ("k_wduo")
     if (const char *mv = getenv("BFIR_MFADE_DUO")) e->mfade_duo = atoi(mv) != 0;
+    // MAC and patch of a fading pair list in one launch (k_wpatch) on the levels of a multi-level engine whose MAC is
+    // k_mac_mimo, only on BFIR_PATCH_FUSED=1: the two launches measured faster ("Pair lists on multi-level engines")
+    if (const char *pf = getenv("BFIR_PATCH_FUSED")) e->patch_fused = atoi(pf) != 0;
     // k_mac_matrix stays the default where it can run: k_mac_mimo was not faster there ("k_mac_mimo")
     if (e->mimo) {
         const char *mm = getenv("BFIR_MIMO_MAC");
@@ -1168,36 +1177,14 @@ static int check_split_lengths(const bfir_engine *e, const FilterRows &r)
     return BFIR_OK;
 }
 
-// The filters of a two-level, multi-level or multi-level matrix engine, split at every D_k: taps [0, D_1) to the head,
-// [D_k, D_(k+1)) to level k.  Mid-stream every delay line is kept: the head takes the new filters from the next block,
-// level k from its next block that completes; what a level has already put into its time ring still plays.
-static int set_coeff_split(bfir_engine *e, const FilterRows &rows, double scale)
+// The partition counts of a split engine's active set are new on every level (sp: nb and nb_max; the device is idle): a
+// level the set newly reaches starts, one it no longer reaches stops, a matrix engine takes its path, and the engine has
+// its coefficients.
+static int split_counts_set(bfir_engine *e, const LevelSplit &sp)
 {
-    int rc = check_split_lengths(e, rows);
-    if (rc != BFIR_OK) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (e->fade_len > 0) { e->fade_len = e->fade_pos = 0; lfade_finish(e, false); }   // a plain change during a fade cancels it: a hard cut
-    e->eng_init[0] = 0;
-    rc = check_rows(e, rows, SIZE_MAX, scale);
-    if (rc != BFIR_OK) return rc;
-    const LevelSplit sp = split_rows(e, rows);
-    // the head, then level after level: the part of every filter that falls into the level and its partitions there
-    for (int k = 0; k <= e->n_tail; k++) {
-        bfir_engine *l = level(e, k);
-        const LevelSplit::Level &s = sp.lv[k];
-        if (s.nb_max > 0) {   // a level on which no filter has taps does no work at all (a matrix head: its MAC stores zeros)
-            rc = load_filters(l, l->H, 0, s.rows, s.nb_max, scale);
-            if (rc != BFIR_OK) return rc;
-        }
-        l->nblk = s.nb;
-        // the matrix MAC takes the counts by value (MatArgs.nblk), k_mac_mimo from the level's table (the device is idle)
-        if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
-        else if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->nblk.size(), hipMemcpyHostToDevice));
-    }
     for (int i = 0; i < e->n_tail; i++) {
         const bool active = sp.lv[i + 1].nb_max > 0;
-        if (active && !e->lv_active[i]) { rc = level_start(e, i); if (rc != BFIR_OK) return rc; }
+        if (active && !e->lv_active[i]) { const int rc = level_start(e, i); if (rc != BFIR_OK) return rc; }
         e->lv_active[i] = active;
         e->tail[i]->eng_init[0] = 1;
     }
@@ -1219,6 +1206,36 @@ static int set_coeff_split(bfir_engine *e, const FilterRows &rows, double scale)
     }
     e->eng_init[0] = 1;
     return BFIR_OK;
+}
+
+// The filters of a two-level, multi-level or multi-level matrix engine, split at every D_k: taps [0, D_1) to the head,
+// [D_k, D_(k+1)) to level k.  Mid-stream every delay line is kept: the head takes the new filters from the next block,
+// level k from its next block that completes; what a level has already put into its time ring still plays.
+static int set_coeff_split(bfir_engine *e, const FilterRows &rows, double scale)
+{
+    int rc = check_split_lengths(e, rows);
+    if (rc != BFIR_OK) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (e->fade_len > 0) { e->fade_len = e->fade_pos = 0; e->fade_patch = false; lfade_finish(e, false); }   // a plain change during a fade cancels it: a hard cut
+    e->eng_init[0] = 0;
+    rc = check_rows(e, rows, SIZE_MAX, scale);
+    if (rc != BFIR_OK) return rc;
+    const LevelSplit sp = split_rows(e, rows);
+    // the head, then level after level: the part of every filter that falls into the level and its partitions there
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = level(e, k);
+        const LevelSplit::Level &s = sp.lv[k];
+        if (s.nb_max > 0) {   // a level on which no filter has taps does no work at all (a matrix head: its MAC stores zeros)
+            rc = load_filters(l, l->H, 0, s.rows, s.nb_max, scale);
+            if (rc != BFIR_OK) return rc;
+        }
+        l->nblk = s.nb;
+        // the matrix MAC takes the counts by value (MatArgs.nblk), k_mac_mimo from the level's table (the device is idle)
+        if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
+        else if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->nblk.size(), hipMemcpyHostToDevice));
+    }
+    return split_counts_set(e, sp);
 }
 
 extern "C" int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
@@ -1267,6 +1284,7 @@ static void lfade_finish(bfir_engine *e, bool take_new)
     for (int i = 0; i < e->n_tail; i++) {
         bfir_engine *t = e->tail[i];
         if (take_new && e->mlevels && t->pair_cap) matrix_take_path(t, t->pair_new);   // after the fade the new set decides
+        t->fade_patch = false;
         if (!t->lf_mode) continue;
         if (take_new && t->lf_mode == 1) tail_swap_sets(t);
         if (take_new || t->lf_mode == 2) std::swap(t->zring, t->zring2);
@@ -1826,14 +1844,60 @@ static PatchArgs patch_args(const bfir_engine *e, int base_slot, void *Y, void *
     return a;
 }
 
-// ... whose grid is its own: refused before anything is queued, as matrix_fade_chunk_ok
+// MAC and patch in one launch (k_wpatch, wpatch.hip): a level of a multi-level engine whose MAC is k_mac_mimo, where the
+// switch asks for it.  A uniform engine keeps its two launches, and so does a level on k_mac_matrix.
+static bool chunk_takes_wpatch(const bfir_engine *e) { return e->patch_fused && e->mimo_mac && (e->mlevels || e->nup_tail); }
+
+static WpatchArgs wpatch_args(const bfir_engine *e, int base_slot, void *Y, long y_ch_stride, void *Y2, long y2_ch_stride, int tc)
+{
+    WpatchArgs d;
+    d.a = mimo_mac_args(e, base_slot, Y, tc);
+    d.a.y_ch_stride = y_ch_stride;
+    d.h2 = e->H2;
+    d.row = e->d_patch; d.ent = e->d_patch + e->Co + 1;
+    d.y2 = Y2; d.y2_ch_stride = y2_ch_stride;
+    return d;
+}
+
+// ... whose grid is its own (k_wpatch: k_mac_mimo's, but for one instance): refused before anything is queued, as
+// matrix_fade_chunk_ok
 static int patch_chunk_ok(const bfir_engine *e, int tc)
 {
-    if (!patch_supported(patch_args(e, 0, nullptr, nullptr, 0, tc))) {
+    const long ys = (long)e->chunk * e->N;
+    if (!patch_supported(patch_args(e, 0, nullptr, nullptr, 0, tc)) ||
+        (chunk_takes_wpatch(e) && !wpatch_supported(wpatch_args(e, 0, nullptr, ys, nullptr, 0, tc)))) {
         bfir_logf("bfir engine: %d fading blocks per launch are past the pair-list kernel's grid.", tc);
         return BFIR_ERR_UNSUPPORTED;
     }
     return BFIR_OK;
+}
+
+// The old set's products of tc blocks from base_slot on into Y and, behind them, the patch into Y2: the MAC queue_mac
+// launches and k_patch_pairs, or k_wpatch for both (the same bits).  spans (a chunk of a multi-level engine): every launch
+// is a BFIR_K_MAC span of its own, so the profile's launch count tells the one launch from the two.
+static int queue_mac_patch(bfir_engine *e, int base_slot, void *Y, long y_ch_stride, void *Y2, long y2_ch_stride, int tc,
+                           hipStream_t s, bool spans)
+{
+    const bool prof = e->profiling;
+    if (!spans) e->profiling = false;
+    int rc;
+    if (chunk_takes_wpatch(e)) {
+        ProfScope ps(e, BFIR_K_MAC, s);
+        rc = launch_wpatch(wpatch_args(e, base_slot, Y, y_ch_stride, Y2, y2_ch_stride, tc), s) != 0 ? BFIR_ERR_UNSUPPORTED : BFIR_OK;
+    } else {
+        {
+            ProfScope ps(e, BFIR_K_MAC, s);
+            rc = queue_mac(e, base_slot, Y, y_ch_stride, tc, false, s);
+        }
+        if (rc == BFIR_OK) {
+            ProfScope ps(e, BFIR_K_MAC, s);
+            PatchArgs a = patch_args(e, base_slot, Y, Y2, y2_ch_stride, tc);
+            a.y_ch_stride = y_ch_stride;
+            rc = launch_patch(a, s) != 0 ? BFIR_ERR_UNSUPPORTED : BFIR_OK;
+        }
+    }
+    e->profiling = prof;
+    return rc;
 }
 
 // what the path's kernels ask of the caller's frame buffers (the staging kernels: nothing)
@@ -2192,9 +2256,11 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
     c.fade = e->fade_len > 0;
     const bool both = c.fade || e->lf_mode == 1;   // ... or, a tail level of a fading engine, all up to its last old block: both sets
     if (both) { c.Y2 = e->Yf[e->pipe3 ? par : 0]; c.y2_ch_stride = (long)e->yf_blocks * e->N; c.m0 = e->fade_pos * e->L; }
-    const bool duo = both && chunk_takes_duo(e);
+    // a pair list fades: the new set's products from the old set's, wherever both are needed (a uniform engine or the head
+    // of a split one while it fades, a tail level up to its last old block)
+    const bool patch = both && e->fade_patch;
+    const bool duo = both && !patch && chunk_takes_duo(e);
     if (duo) { rc = matrix_fade_chunk_ok(e, tc); if (rc != BFIR_OK) return rc; }
-    const bool patch = c.fade && e->fade_patch;                 // a pair list fades: the new set's products from the old set's
     if (patch) { rc = patch_chunk_ok(e, tc); if (rc != BFIR_OK) return rc; }
     rc = chunk_aligned(e, p, c);
     if (rc != BFIR_OK) return rc;
@@ -2216,17 +2282,19 @@ static int run_chunk(bfir_engine *e, const void *d_in, long in_stride, void *d_o
         HIP_TRY(hipStreamWaitEvent(sm, e->ev_fwd[par], 0));
         if (e->pipe3 && e->chunk_seq >= 2) HIP_TRY(hipStreamWaitEvent(sm, e->ev_inv[par], 0));   // inv(k-2) has read Yb[par]
     }
-    {
+    if (patch && (e->mlevels || e->nup_tail)) {   // the old set's MAC and the patch behind it, or k_wpatch: a span per launch
+        if ((rc = queue_mac_patch(e, c.base_slot, c.Y, (long)e->chunk * e->N, c.Y2, c.y2_ch_stride, tc, sm, true)) != BFIR_OK) return rc;
+    } else {
         ProfScope ps(e, BFIR_K_MAC, sm);
         if (duo) {   // a multi-level matrix engine: both sets in one pass over the delay line
             if ((rc = queue_duo(e, c.base_slot, c.Y, c.Y2, c.y2_ch_stride, tc, sm)) != BFIR_OK) return rc;
         }
+        else if (patch) {   // a uniform engine: the old set's MAC and the patch behind it, one span
+            if ((rc = queue_mac_patch(e, c.base_slot, c.Y, (long)e->chunk * e->N, c.Y2, c.y2_ch_stride, tc, sm, false)) != BFIR_OK) return rc;
+        }
         else if ((rc = queue_mac(e, c.base_slot, c.Y, (long)e->chunk * e->N, tc, false, sm)) != BFIR_OK) return rc;
         // the same delay line through the same kernels with the new set, behind the first
-        if (patch) {
-            if (launch_patch(patch_args(e, c.base_slot, c.Y, c.Y2, c.y2_ch_stride, tc), sm) != 0) return BFIR_ERR_UNSUPPORTED;
-        }
-        else if (both && !duo && (rc = queue_mac(e, c.base_slot, c.Y2, c.y2_ch_stride, tc, true, sm)) != BFIR_OK) return rc;
+        if (both && !duo && !patch && (rc = queue_mac(e, c.base_slot, c.Y2, c.y2_ch_stride, tc, true, sm)) != BFIR_OK) return rc;
     }
     if (!il) {
         HIP_TRY(hipEventRecord(e->ev_mac[par], sm));
@@ -2285,7 +2353,10 @@ static long long floor_div(long long a, long long b) { return a >= 0 ? a / b : -
 // the new set -- their MAC again, with the new set alone, on the delay line the level still holds, into the second ring.
 // A level that restarted mid-stream less than that many blocks ago (bfir_engine_set_coeff_levels) has only those since,
 // the ones before read as zero under the new set.  Then the level's place in the lf_mode schedule.
-static int lfade_catch_up(bfir_engine *e, int fade_blocks, const LevelSplit &sp)
+// A pair list (patch): the new set's products are the old set's plus the listed pairs' difference here too, as in every
+// launch of the fade that takes both sets -- the old set's MAC of those blocks again into the level's product buffer (the
+// chain that produced them: the same bits) and the patch behind it.
+static int lfade_catch_up(bfir_engine *e, int fade_blocks, const LevelSplit &sp, bool patch)
 {
     const long long a_f = (long long)e->blockcounter;
     for (int i = 0; i < e->n_tail; i++) {
@@ -2301,7 +2372,8 @@ static int lfade_catch_up(bfir_engine *e, int fade_blocks, const LevelSplit &sp)
         for (long long j = j0; j < t->z_next;) {
             const int n = (int)std::min<long long>(t->z_next - j, t->yf_blocks);
             const long long bc = (long long)t->blockcounter - (t->z_next - j);   // the level's own count of block j
-            rc = queue_mac(t, (int)(bc % t->ring), t->Yf[0], yf_stride, n, true, e->stream);
+            if (patch) rc = queue_mac_patch(t, (int)(bc % t->ring), t->Yb[0], (long)t->chunk * t->N, t->Yf[0], yf_stride, n, e->stream, false);
+            else rc = queue_mac(t, (int)(bc % t->ring), t->Yf[0], yf_stride, n, true, e->stream);
             if (rc != BFIR_OK) return rc;   // a matrix level: checked before anything changed, not reached
             inv_to_ring(t, t->Yf[0], yf_stride, t->zring2, j, n, e->stream);
             j += n;
@@ -2314,15 +2386,78 @@ static int lfade_catch_up(bfir_engine *e, int fade_blocks, const LevelSplit &sp)
     return BFIR_OK;
 }
 
+// The listed filters of a pairs call on a multi-level matrix engine, split at every D_k (spl: row j of it is filter
+// list[j] = o C + i), merged into the active set's counts: nb and nb_max of every level of the merged set.  No rows.
+static LevelSplit merged_counts(const bfir_engine *e, const LevelSplit &spl, const std::vector<int> &list)
+{
+    LevelSplit sp;
+    for (int k = 0; k <= e->n_tail; k++) {
+        LevelSplit::Level &s = sp.lv[k];
+        s.nb = level(e, k)->nblk;
+        for (size_t j = 0; j < list.size(); j++) s.nb[list[j]] = spl.lv[k].nb[j];
+        for (int nb : s.nb) s.nb_max = std::max(s.nb_max, nb);
+    }
+    return sp;
+}
+
+// The listed rows' part of level l into Hdst (H, or H2 holding a copy of H), row by row on the stream that owns every write
+// to the level's store: the spectrum of a row does not depend on the rows transformed with it (load_pairs).  A listed
+// filter that does not reach the level gets its row cleared.
+static int load_level_pairs(bfir_engine *l, void *Hdst, const LevelSplit::Level &sl, const std::vector<int> &list, double scale)
+{
+    const size_t row_bytes = (size_t)l->B * cbuf_bytes(l);
+    for (size_t j = 0; j < list.size(); j++) {
+        if (sl.nb[j] == 0) {
+            HIP_TRY(hipMemsetAsync((char *)Hdst + (size_t)list[j] * row_bytes, 0, row_bytes, l->stream));
+            continue;
+        }
+        FilterRows one(1);
+        one.taps[0] = sl.rows.taps[j]; one.len[0] = sl.rows.len[j];
+        const int rc = load_filters(l, Hdst, list[j], one, sl.nb[j], scale);
+        if (rc != BFIR_OK) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(l->stream));
+    return BFIR_OK;
+}
+
+// k_patch_pairs' table of one level in its d_patch: per output its listed pairs in input order, (input, nb_new, nb_old)
+static int patch_table_set(bfir_engine *l, const std::vector<int> &list)
+{
+    std::vector<char> listed((size_t)l->Co * l->C, 0);
+    for (int n : list) listed[n] = 1;
+    std::vector<int> tab((size_t)l->Co + 1);
+    for (int o = 0; o < l->Co; o++) {
+        tab[o] = (int)(tab.size() - (l->Co + 1)) / 3;
+        for (int i = 0; i < l->C; i++) {
+            const int n = o * l->C + i;
+            if (listed[n]) { tab.push_back(i); tab.push_back(l->nblk2[n]); tab.push_back(l->nblk[n]); }
+        }
+    }
+    tab[l->Co] = (int)list.size();
+    if (tab.size() > l->patch_ints) {
+        if (l->d_patch) (void)hipFree(l->d_patch);
+        l->d_patch = nullptr; l->patch_ints = 0;
+        HIP_TRY(hipMalloc((void **)&l->d_patch, sizeof(int) * tab.size()));
+        l->patch_ints = tab.size();
+    }
+    HIP_TRY(hipMemcpy(l->d_patch, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    return BFIR_OK;
+}
+
 // The crossfade of a two-level, multi-level or multi-level matrix engine: the split of set_coeff_split into H2 of every
 // level, the catch-up, and the head's fade as a uniform engine's.
-static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double scale, int fade_blocks)
+// list (bfir_engine_set_coeff_matrix_levels_pairs_fade): `rows` are the listed filters alone, row j the new filter list[j] =
+// o C + i, and the new set is the active one with those replaced.  Every level's H2 is its H copied and the listed rows'
+// part loaded, its table goes to its d_patch, and the launches that take both sets patch (fade_patch).
+static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double scale, int fade_blocks,
+                                const std::vector<int> *list = nullptr)
 {
     int rc = check_split_lengths(e, rows);
     if (rc == BFIR_OK) rc = check_fade_args(e, fade_blocks);
     if (rc != BFIR_OK) return rc;
     for (int n = 0; n < rows.n_required; n++) if (!rows.taps[n]) return BFIR_ERR_ARG;
-    const LevelSplit sp = split_rows(e, rows);
+    const LevelSplit spl = split_rows(e, rows);
+    const LevelSplit sp = list ? merged_counts(e, spl, *list) : spl;
     for (int i = 0; i < e->n_tail; i++) {
         // a level the old set does not reach runs no forward transforms: it has no delay line to fade on (per level, not
         // per filter: a filter of a matrix engine that is new on a running level fades in)
@@ -2337,12 +2472,16 @@ static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double s
     if (rc != BFIR_OK) return rc;
     // the catch-up's launches (up to a tail's chunk) must fit the matrix MAC's grid: refused before anything changes
     for (int i = 0; i < e->n_tail; i++)
-        if (e->lv_active[i]) { rc = matrix_chunk_ok(e->tail[i], e->tail[i]->chunk); if (rc != BFIR_OK) return rc; }
+        if (e->lv_active[i]) {
+            rc = matrix_chunk_ok(e->tail[i], e->tail[i]->chunk);
+            if (rc == BFIR_OK && list) rc = patch_chunk_ok(e->tail[i], e->tail[i]->chunk);
+            if (rc != BFIR_OK) return rc;
+        }
     HIP_TRY(hipSetDevice(e->device));
     // queued work may still read what was H before the last fade's swap, and the catch-up below reads the delay lines: the
     // device is idle from here to the end of the call
     HIP_TRY(hipDeviceSynchronize());
-    const size_t n_rows = rows.taps.size();
+    const size_t n_rows = list ? (size_t)e->Co * e->C : rows.taps.size();
     rc = fade_prepare(e, (int)n_rows);
     if (rc != BFIR_OK) return rc;
     for (int k = 0; k <= e->n_tail; k++) {
@@ -2350,7 +2489,14 @@ static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double s
         const LevelSplit::Level &s = sp.lv[k];
         if (k > 0 && !e->lv_active[k - 1]) continue;
         l->nblk2 = s.nb;
-        if (s.nb_max > 0) {
+        if (list) {
+            // the level's store copied on the stream its rows are loaded on, and complete before the first row is written
+            HIP_TRY(hipMemcpyAsync(l->H2, l->H, n_rows * l->B * cbuf_bytes(l), hipMemcpyDeviceToDevice, l->stream));
+            HIP_TRY(hipStreamSynchronize(l->stream));
+            rc = load_level_pairs(l, l->H2, spl.lv[k], *list, scale);
+            if (rc == BFIR_OK) rc = patch_table_set(l, *list);
+            if (rc != BFIR_OK) return rc;
+        } else if (s.nb_max > 0) {
             rc = load_filters(l, l->H2, 0, s.rows, s.nb_max, scale);
             if (rc != BFIR_OK) return rc;
         } else {
@@ -2382,12 +2528,18 @@ static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double s
             matrix_take_path(e, e->pair_new && read_old && !(odd && !tail_old));
         }
     }
-    rc = lfade_catch_up(e, fade_blocks, sp);
+    rc = lfade_catch_up(e, fade_blocks, sp, list != nullptr);
     if (rc != BFIR_OK) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipGetLastError());
     fade_begin(e, fade_blocks);
-    if (e->matrix)
+    if (list) {   // behind fade_begin, which clears it; every way the fade ends clears it again (fade_swap_sets, lfade_finish)
+        e->fade_patch = true;
+        for (int i = 0; i < e->n_tail; i++) e->tail[i]->fade_patch = e->lv_active[i];
+        bfir_logf("bfir matrix engine: crossfade of %d pairs over %d blocks on %d levels; a launch that needs both sets runs %s.",
+                  (int)list->size(), fade_blocks, e->n_tail + 1,
+                  chunk_takes_wpatch(e) ? "k_wpatch" : (e->mimo_mac ? "k_mac_mimo and k_patch_pairs" : "k_mac_matrix and k_patch_pairs"));
+    } else if (e->matrix)
         bfir_logf("bfir matrix engine: crossfade over %d blocks on %d levels; a launch that needs both sets runs %s.", fade_blocks,
                   e->n_tail + 1, chunk_takes_duo(e) ? (e->mimo_mac ? "k_wduo" : "k_mac_duo") : (e->mimo_mac ? "k_mac_mimo twice" : "k_mac_matrix twice"));
     return BFIR_OK;
@@ -2420,6 +2572,72 @@ extern "C" int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const vo
     if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
     if (!coeffs || !lengths) return BFIR_ERR_ARG;
     return set_coeff_split_fade(e, matrix_rows(e, coeffs, lengths, 0), scale, fade_blocks);
+}
+
+// ---------------------------------------------------------------------------
+// a list of (output, input) pairs of a multi-level matrix or mimo engine replaced:
+// bfir_engine_set_coeff_matrix_levels_pairs, _pairs_fade
+// ---------------------------------------------------------------------------
+// What both calls ask of their list, every filter of its own length; host arithmetic alone.
+static int pairs_list_levels(const bfir_engine *e, int n_pairs, const int *outputs, const int *inputs, const void *const *coeffs,
+                             const int *lengths, PairList &pl)
+{
+    if (!outputs || !inputs || !coeffs || !lengths || n_pairs < 1) return BFIR_ERR_ARG;
+    std::vector<char> listed((size_t)e->Co * e->C, 0);
+    pl.rows = FilterRows((size_t)n_pairs);
+    pl.row.resize((size_t)n_pairs);
+    for (int k = 0; k < n_pairs; k++) {
+        if (outputs[k] < 0 || outputs[k] >= e->Co || inputs[k] < 0 || inputs[k] >= e->C) return BFIR_ERR_ARG;
+        const int n = outputs[k] * e->C + inputs[k];
+        if (listed[n]) return BFIR_ERR_ARG;                     // the same pair twice
+        listed[n] = 1;
+        if (coeffs[k] && lengths[k] < 0) return BFIR_ERR_ARG;
+        pl.row[k] = n; pl.rows.taps[k] = coeffs[k]; pl.rows.len[k] = coeffs[k] ? lengths[k] : 0;
+    }
+    return check_split_lengths(e, pl.rows);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_pairs(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                         const void *const *coeffs, const int *lengths, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    PairList pl;
+    int rc = pairs_list_levels(e, n_pairs, outputs, inputs, coeffs, lengths, pl);
+    if (rc != BFIR_OK) return rc;
+    // nothing to patch; or a fade: a tail past its last old block already runs the new set, there is no ONE active set
+    if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
+    rc = check_rows(e, pl.rows, SIZE_MAX, scale);               // a NaN / Inf tap: the engine keeps its filters and stays initialised
+    if (rc != BFIR_OK) return rc;
+    const LevelSplit spl = split_rows(e, pl.rows);
+    const LevelSplit sp = merged_counts(e, spl, pl.row);
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = level(e, k);
+        int nb_old = 0;
+        for (int nb : l->nblk) nb_old = std::max(nb_old, nb);
+        // a level the active set does not reach was not loaded by the set call (set_coeff_split): its store reads as zeros
+        // before the first listed row goes in, as load_filters leaves the rows of the whole matrix
+        if (nb_old == 0 && sp.lv[k].nb_max > 0) HIP_TRY(hipMemset(l->H, 0, l->nblk.size() * l->B * cbuf_bytes(l)));
+        rc = load_level_pairs(l, l->H, spl.lv[k], pl.row, scale);
+        if (rc != BFIR_OK) return rc;
+        l->nblk = sp.lv[k].nb;
+        if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->nblk.size(), hipMemcpyHostToDevice));
+    }
+    return split_counts_set(e, sp);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_pairs_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                              const void *const *coeffs, const int *lengths, double scale,
+                                                              int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    PairList pl;
+    const int rc = pairs_list_levels(e, n_pairs, outputs, inputs, coeffs, lengths, pl);
+    if (rc != BFIR_OK) return rc;
+    return set_coeff_split_fade(e, pl.rows, scale, fade_blocks, &pl.row);
 }
 
 extern "C" int bfir_engine_fade_remaining_levels(const bfir_engine *e)
@@ -2519,10 +2737,14 @@ static int run_blocks(bfir_engine *e, const void *d_in, long in_stride, void *d_
     if (e->mlevels) {   // every level's MAC must take its longest launch of this call: refused before anything is queued
         int rc = matrix_chunk_ok(e, std::min(e->chunk, n));
         for (int i = 0; i < e->n_tail && rc == BFIR_OK; i++) rc = matrix_chunk_ok(e->tail[i], std::min(e->tail[i]->chunk, n));
-        if (rc == BFIR_OK && e->fade_len > 0) {   // ... and, fading, the launches that take both sets
-            rc = matrix_fade_chunk_ok(e, std::min(e->chunk, n));
+        if (rc == BFIR_OK && e->fade_len > 0) {   // ... and, fading, the launches that take both sets (a pair list: the patch)
+            auto both_ok = [&](const bfir_engine *l) {
+                const int tc = std::min(l->chunk, n);
+                return l->fade_patch ? patch_chunk_ok(l, tc) : matrix_fade_chunk_ok(l, tc);
+            };
+            rc = both_ok(e);
             for (int i = 0; i < e->n_tail && rc == BFIR_OK; i++)
-                if (e->tail[i]->lf_mode == 1) rc = matrix_fade_chunk_ok(e->tail[i], std::min(e->tail[i]->chunk, n));
+                if (e->tail[i]->lf_mode == 1) rc = both_ok(e->tail[i]);
         }
         if (rc != BFIR_OK) return rc;
     }

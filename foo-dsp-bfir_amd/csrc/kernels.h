@@ -242,6 +242,30 @@ struct PatchArgs {
 bool patch_supported(const PatchArgs &a);                   // the grid of the launch fits
 int launch_patch(const PatchArgs &a, hipStream_t s);        // 0, or -1 if !patch_supported(a) (nothing launched)
 
+// wpatch.hip: k_wpatch, the old set's products of a level whose MAC is k_mac_mimo AND the patch behind them in one launch:
+// a.y and y2 are bit for bit what launch_mac_mimo(a) followed by launch_patch(wpatch_patch_args(d)) write.
+struct WpatchArgs {
+    MimoArgs a;                                               // the old set's MAC
+    const void *h2;                                           // the new set, as a.h
+    const int *row, *ent;                                     // the table of the listed pairs, as PatchArgs has it
+    void *y2; long y2_ch_stride;                              // [n_out][..][N], written
+};
+// the patch of that launch as k_patch_pairs takes it: everything else is a's
+inline __host__ __device__ PatchArgs wpatch_patch_args(const WpatchArgs &d)
+{
+    PatchArgs p;
+    p.x = d.a.x; p.x_ch_stride = d.a.x_ch_stride; p.ring = d.a.ring; p.base_slot = d.a.base_slot;
+    p.h = d.a.h; p.h2 = d.h2; p.h_pair_stride = d.a.h_pair_stride;
+    p.row = d.row; p.ent = d.ent;
+    p.y = d.a.y; p.y_ch_stride = d.a.y_ch_stride;
+    p.y2 = d.y2; p.y2_ch_stride = d.y2_ch_stride;
+    p.n_t = d.a.n_t; p.n_in = d.a.n_in; p.n_out = d.a.n_out; p.N = d.a.N; p.realsize = d.a.realsize;
+    p.interleaved = d.a.interleaved;
+    return p;
+}
+bool wpatch_supported(const WpatchArgs &d);                 // the grid of the launch fits
+int launch_wpatch(const WpatchArgs &d, hipStream_t s);      // 0, or -1 if !wpatch_supported(d) (nothing launched)
+
 // a11 + a12: inverse real FFT of Y[gc][t] (grouped layout, times in_scale),
 // first L samples to dst + gc*dst_ch_stride + t*L.
 struct InvArgs {

@@ -1,7 +1,9 @@
 // mat_ops.h -- what the matrix MAC kernels share (matrix.hip: k_mac_matrix; mfade.hip: k_mac_duo; mimo.hip: k_mac_mimo):
 // one complex multiply-add in the order of every MAC here, the load of one bin of a spectrum in either layout, and the
 // sums of one lane of k_mac_matrix and k_mac_mimo (mat_tile, mat_lane), which differ in their grids alone, and likewise of
-// k_mac_duo and k_wduo (wduo.hip), the two-set forms (duo_tile, duo_lane).
+// k_mac_duo and k_wduo (wduo.hip), the two-set forms (duo_tile, duo_lane); the walk of a row's listed pairs that
+// k_patch_pairs (patch.hip) and k_wpatch (wpatch.hip) share (patch_pass, patch_row); and k_mac_mimo's choice of its register
+// tile and grid (mimo_no, mimo_tt, mimo_grid), which k_wpatch takes over.
 #pragma once
 #include "kernels.h"
 
@@ -253,6 +255,81 @@ __device__ __forceinline__ void duo_lane(const D &d, int k, bool wave0, int o0, 
             }
         }
     }
+}
+
+// The continuation of one output's fma chains through the listed pairs of its row: the one body of k_patch_pairs
+// (patch.hip, which documents the sum) and k_wpatch (wpatch.hip).
+//
+// One filter of a listed pair, nb > 0 partitions at Hp, into the accumulators of the lane's tile: mat_tile's walk for one
+// output -- the window of TT delay-line spectra X[t0 + j - p] in registers, step p loads ONE new spectrum and H[p], operands
+// fetched one step ahead.  NEG: the old filter, subtracted.
+template <typename T, bool ILV, int TT, bool DCNY, bool NEG>
+__device__ __forceinline__ void patch_pass(const PatchArgs &a, const T *__restrict__ Xi, const T *__restrict__ Hp, int nb,
+                                           int sl, int ore, int oim, bool k0, T (&ar)[TT], T (&ai)[TT])
+{
+    const long N = a.N;
+    const int ring = a.ring;
+    // blocks t0 + j >= n_t of the last tile: slots the next chunk's forward transform may be writing (in bounds: ring = 2
+    // chunk + B); their values only reach accumulators that are never stored
+    T wr[TT], wi[TT];
+#pragma unroll
+    for (int j = 0; j < TT; j++) {
+        int sj = sl + j; if (sj >= ring) sj -= ring;
+        mat_ld<T, ILV>(Xi + (long)sj * N, ore, oim, wr[j], wi[j]);
+    }
+    T qxr = (T)0, qxi = (T)0, qhr, qhi;                          // operands of the next step (step 0 takes no new X)
+    mat_ld<T, ILV>(Hp, ore, oim, qhr, qhi);
+    for (int p0 = 0; p0 < nb; p0 += TT) {
+#pragma unroll
+        for (int ii = 0; ii < TT; ii++) {
+            const int p = p0 + ii;
+            if (p < nb) {                                        // wave-uniform
+                if (p > 0) { wr[(TT - ii) % TT] = qxr; wi[(TT - ii) % TT] = qxi; }
+                const T hr = NEG ? -qhr : qhr, hi = NEG ? -qhi : qhi;
+                const int pn = p + 1 < nb ? p + 1 : p;           // prefetch step p + 1 (clamped: in range, not used)
+                int sn = sl - pn; if (sn < 0) sn += ring;        // X[t0 - pn] enters the window at step pn
+                mat_ld<T, ILV>(Xi + (long)sn * N, ore, oim, qxr, qxi);
+                mat_ld<T, ILV>(Hp + (long)pn * N, ore, oim, qhr, qhi);
+#pragma unroll
+                for (int j = 0; j < TT; j++) {
+                    const int idx = (j - ii + TT) % TT;
+                    mat_cmac<DCNY>(ar[j], ai[j], wr[idx], wi[idx], hr, hi, k0);
+                }
+            }
+        }
+    }
+}
+
+template <typename T, bool ILV, int TT, bool DCNY>
+__device__ __forceinline__ void patch_row(const PatchArgs &a, int o, int t0, int ore, int oim, bool k0, T (&ar)[TT], T (&ai)[TT])
+{
+    const int sl = (a.base_slot + t0) % a.ring;                  // delay-line slot of block t0
+    const int e1 = a.row[o + 1];
+    for (int e = a.row[o]; e < e1; e++) {                        // the row's listed pairs, in input order
+        const int i = a.ent[3 * e], nb_new = a.ent[3 * e + 1], nb_old = a.ent[3 * e + 2];
+        const T *__restrict__ Xi = (const T *)a.x + (long)i * a.x_ch_stride;
+        const long hoff = ((long)o * a.n_in + i) * a.h_pair_stride;
+        if (nb_new > 0) patch_pass<T, ILV, TT, DCNY, false>(a, Xi, (const T *)a.h2 + hoff, nb_new, sl, ore, oim, k0, ar, ai);
+        if (nb_old > 0) patch_pass<T, ILV, TT, DCNY, true>(a, Xi, (const T *)a.h + hoff, nb_old, sl, ore, oim, k0, ar, ai);
+    }
+}
+
+// k_mac_mimo's register tile and grid (mimo.hip), which k_wpatch (wpatch.hip) runs on as well.  The tile is k_mac_matrix's,
+// for its reason (64 accumulator registers, four waves per SIMD): NO = the output count rounded up to a power of two, at
+// most 4 (fp32) / 2 (fp64); TT = 1 on the latency path (launches of up to BFIR_MAT_SMALL_MAX blocks), else 8 (fp32; fp64
+// with one output) or 4 (fp64).
+constexpr int kMimoBins = 64;   // bins per workgroup: one wave
+inline int mimo_no(const MimoArgs &a) { const int cap = a.realsize == 4 ? 4 : 2; int no = 1; while (no < a.n_out && no < cap) no *= 2; return no; }
+inline int mimo_tt(const MimoArgs &a, int no)
+{
+    if (a.n_t <= BFIR_MAT_SMALL_MAX) return 1;
+    return a.realsize == 4 ? 8 : (no == 1 ? 8 : 4);
+}
+
+// workgroups of the launch: (bin tiles, output tiles, time tiles)
+inline void mimo_grid(const MimoArgs &a, int no, int tt, long &nbt, long &n_ot, long &nTT)
+{
+    nbt = (a.N / 2 + kMimoBins - 1) / kMimoBins; n_ot = (a.n_out + no - 1) / no; nTT = ((long)a.n_t + tt - 1) / tt;
 }
 
 }  // namespace bfir

@@ -27,8 +27,6 @@
 
 namespace bfir {
 
-constexpr int kMimoBins = 64;   // bins per workgroup: one wave
-
 template <typename T, bool ILV, int NO, int TT>
 __global__ __launch_bounds__(kMimoBins, 4) void k_mac_mimo(MimoArgs a, int n_ot, int nTT)
 {
@@ -40,22 +38,7 @@ __global__ __launch_bounds__(kMimoBins, 4) void k_mac_mimo(MimoArgs a, int n_ot,
     mat_lane<T, ILV, NO, TT>(a, k, bt == 0, ot * NO, tt * TT);
 }
 
-// The register tile is k_mac_matrix's, for its reason (64 accumulator registers, four waves per SIMD): NO = the output
-// count rounded up to a power of two, at most 4 (fp32) / 2 (fp64); TT = 1 on the latency path (launches of up to
-// BFIR_MAT_SMALL_MAX blocks), else 8 (fp32; fp64 with one output) or 4 (fp64).
-static int mimo_no(const MimoArgs &a) { const int cap = a.realsize == 4 ? 4 : 2; int no = 1; while (no < a.n_out && no < cap) no *= 2; return no; }
-static int mimo_tt(const MimoArgs &a, int no)
-{
-    if (a.n_t <= BFIR_MAT_SMALL_MAX) return 1;
-    return a.realsize == 4 ? 8 : (no == 1 ? 8 : 4);
-}
-
-// workgroups of the launch: (bin tiles, output tiles, time tiles)
-static void mimo_grid(const MimoArgs &a, int no, int tt, long &nbt, long &n_ot, long &nTT)
-{
-    nbt = (a.N / 2 + kMimoBins - 1) / kMimoBins; n_ot = (a.n_out + no - 1) / no; nTT = ((long)a.n_t + tt - 1) / tt;
-}
-
+// the register tile and the grid: mimo_no, mimo_tt, mimo_grid (mat_ops.h; k_wpatch, wpatch.hip, runs on them too)
 bool mac_mimo_supported(const MimoArgs &a)
 {
     if (a.n_in < 1 || a.n_in > BFIR_MIMO_MAX || a.n_out < 1 || a.n_out > BFIR_MIMO_MAX || a.n_t < 0) return false;

@@ -31,61 +31,7 @@
 
 namespace bfir {
 
-constexpr int kPatchBins = 64;   // bins per workgroup: one wave
-
-// One filter of a listed pair, nb > 0 partitions at Hp, into the accumulators of the lane's tile: mat_tile's walk for one
-// output -- the window of TT delay-line spectra X[t0 + j - p] in registers, step p loads ONE new spectrum and H[p], operands
-// fetched one step ahead.  NEG: the old filter, subtracted.
-template <typename T, bool ILV, int TT, bool DCNY, bool NEG>
-__device__ __forceinline__ void patch_pass(const PatchArgs &a, const T *__restrict__ Xi, const T *__restrict__ Hp, int nb,
-                                           int sl, int ore, int oim, bool k0, T (&ar)[TT], T (&ai)[TT])
-{
-    const long N = a.N;
-    const int ring = a.ring;
-    // blocks t0 + j >= n_t of the last tile: slots the next chunk's forward transform may be writing (in bounds: ring = 2
-    // chunk + B); their values only reach accumulators that are never stored
-    T wr[TT], wi[TT];
-#pragma unroll
-    for (int j = 0; j < TT; j++) {
-        int sj = sl + j; if (sj >= ring) sj -= ring;
-        mat_ld<T, ILV>(Xi + (long)sj * N, ore, oim, wr[j], wi[j]);
-    }
-    T qxr = (T)0, qxi = (T)0, qhr, qhi;                          // operands of the next step (step 0 takes no new X)
-    mat_ld<T, ILV>(Hp, ore, oim, qhr, qhi);
-    for (int p0 = 0; p0 < nb; p0 += TT) {
-#pragma unroll
-        for (int ii = 0; ii < TT; ii++) {
-            const int p = p0 + ii;
-            if (p < nb) {                                        // wave-uniform
-                if (p > 0) { wr[(TT - ii) % TT] = qxr; wi[(TT - ii) % TT] = qxi; }
-                const T hr = NEG ? -qhr : qhr, hi = NEG ? -qhi : qhi;
-                const int pn = p + 1 < nb ? p + 1 : p;           // prefetch step p + 1 (clamped: in range, not used)
-                int sn = sl - pn; if (sn < 0) sn += ring;        // X[t0 - pn] enters the window at step pn
-                mat_ld<T, ILV>(Xi + (long)sn * N, ore, oim, qxr, qxi);
-                mat_ld<T, ILV>(Hp + (long)pn * N, ore, oim, qhr, qhi);
-#pragma unroll
-                for (int j = 0; j < TT; j++) {
-                    const int idx = (j - ii + TT) % TT;
-                    mat_cmac<DCNY>(ar[j], ai[j], wr[idx], wi[idx], hr, hi, k0);
-                }
-            }
-        }
-    }
-}
-
-template <typename T, bool ILV, int TT, bool DCNY>
-__device__ __forceinline__ void patch_row(const PatchArgs &a, int o, int t0, int ore, int oim, bool k0, T (&ar)[TT], T (&ai)[TT])
-{
-    const int sl = (a.base_slot + t0) % a.ring;                  // delay-line slot of block t0
-    const int e1 = a.row[o + 1];
-    for (int e = a.row[o]; e < e1; e++) {                        // the row's listed pairs, in input order
-        const int i = a.ent[3 * e], nb_new = a.ent[3 * e + 1], nb_old = a.ent[3 * e + 2];
-        const T *__restrict__ Xi = (const T *)a.x + (long)i * a.x_ch_stride;
-        const long hoff = ((long)o * a.n_in + i) * a.h_pair_stride;
-        if (nb_new > 0) patch_pass<T, ILV, TT, DCNY, false>(a, Xi, (const T *)a.h2 + hoff, nb_new, sl, ore, oim, k0, ar, ai);
-        if (nb_old > 0) patch_pass<T, ILV, TT, DCNY, true>(a, Xi, (const T *)a.h + hoff, nb_old, sl, ore, oim, k0, ar, ai);
-    }
-}
+constexpr int kPatchBins = 64;   // bins per workgroup: one wave; the lane's walk: patch_pass, patch_row (mat_ops.h)
 
 template <typename T, bool ILV, int TT>
 __global__ __launch_bounds__(kPatchBins, 4) void k_patch_pairs(PatchArgs a, int nTT)

@@ -601,8 +601,33 @@ class BrutefirMatrixLevels(BrutefirMatrix):
         lens = (C.c_int * len(arrs))(*[0 if a is None else a.size for a in arrs])
         return self._lib.bfir_engine_set_coeff_matrix_levels_fade(self._h, ptrs, lens, float(scale), int(fade_blocks))
 
+    def _level_pair_args(self, pairs, filters):
+        """The list arguments of set_pairs / fade_to_pairs; the arrays are returned too, to keep them alive over the call."""
+        assert len(pairs) == len(filters)
+        rd = _real_dtype(self.s)
+        arrs = [None if h is None else np.ascontiguousarray(h, dtype=rd) for h in filters]
+        outs = (C.c_int * len(pairs))(*[int(o) for o, _ in pairs])
+        ins = (C.c_int * len(pairs))(*[int(i) for _, i in pairs])
+        ptrs = (C.c_void_p * len(arrs))(*[None if a is None else a.ctypes.data for a in arrs])
+        lens = (C.c_int * len(arrs))(*[0 if a is None else a.size for a in arrs])
+        return (len(pairs), outs, ins, ptrs, lens), arrs
+
+    def set_pairs(self, pairs, filters, scale=1.0):
+        """bfir_engine_set_coeff_matrix_levels_pairs: filters[k] (taps in working precision, each of its own length up to
+        max_taps, or None = the path is removed) replaces h_{o,i} for pairs[k] = (o, i); every other pair keeps its filter
+        on every level.  Returns 0 or an ERR_* code (ERR_STATE while a fade is pending or running).  The inherited
+        set_coeff_pairs / set_coeff_pairs_fade, the calls of the uniform kinds, keep returning ERR_UNSUPPORTED."""
+        args, _keep = self._level_pair_args(pairs, filters)
+        return self._lib.bfir_engine_set_coeff_matrix_levels_pairs(self._h, *args, float(scale))
+
+    def fade_to_pairs(self, pairs, filters, fade_blocks, scale=1.0):
+        """bfir_engine_set_coeff_matrix_levels_pairs_fade: the same change, crossfaded over the next `fade_blocks` blocks as
+        fade_to_rows fades to the merged set; the fading blocks agree with that fade within rounding, not bitwise."""
+        args, _keep = self._level_pair_args(pairs, filters)
+        return self._lib.bfir_engine_set_coeff_matrix_levels_pairs_fade(self._h, *args, float(scale), int(fade_blocks))
+
     def fade_remaining(self):
-        """Head blocks of a pending or running fade_to_rows still to be processed; 0 = none."""
+        """Head blocks of a pending or running fade_to_rows / fade_to_pairs still to be processed; 0 = none."""
         return self._lib.bfir_engine_fade_remaining_levels(self._h)
 
     def coeff_block(self, level, output, input, block):

@@ -234,6 +234,23 @@ public:
         if (!m_e) return -1;
         return bfir_engine_set_coeff_matrix_levels_fade(m_e, (const void *const *)coeffs, lengths, scale, fade_blocks);
     }
+    // A list of a multi-level matrix or mimo engine's pairs replaced: coeffs[k] the new h_{outputs[k],inputs[k]} with
+    // lengths[k] taps, or null (the path is removed); every other pair keeps its filter on every level
+    // (bfir_engine_set_coeff_matrix_levels_pairs); and the same change crossfaded over the next fade_blocks blocks
+    // (bfir_engine_set_coeff_matrix_levels_pairs_fade).
+    int set_coeff_matrix_levels_pairs(int n_pairs, const int *outputs, const int *inputs, void **coeffs, const int *lengths,
+                                      double scale)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_matrix_levels_pairs(m_e, n_pairs, outputs, inputs, (const void *const *)coeffs, lengths, scale);
+    }
+    int set_coeff_matrix_levels_pairs_fade(int n_pairs, const int *outputs, const int *inputs, void **coeffs, const int *lengths,
+                                           double scale, int fade_blocks)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_set_coeff_matrix_levels_pairs_fade(m_e, n_pairs, outputs, inputs, (const void *const *)coeffs, lengths,
+                                                              scale, fade_blocks);
+    }
     // head blocks of such a fade still to be processed; 0 = none
     int fade_remaining_levels() { return m_e ? bfir_engine_fade_remaining_levels(m_e) : -1; }
 

@@ -445,6 +445,53 @@ int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *const *coeffs,
  * second time ring and a second product buffer, sized by n_outputs where the first ones are. */
 int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const void *const *coeffs, const int *lengths, double scale,
                                              int fade_blocks);
+/* A LIST of pairs of a multi-level matrix or mimo engine replaced (bfir_engine_create_matrix_levels, _create_mimo_levels;
+ * bfir_engine_set_coeff_matrix_pairs and _pairs_fade keep refusing these kinds): coeffs[k], k < n_pairs, is the new
+ * h_{outputs[k], inputs[k]} with lengths[k] taps of its own, 0 .. D_(n_levels); a NULL pointer or 0 taps removes the path.
+ * The taps are split at every D_k as bfir_engine_set_coeff_matrix_levels splits them.  The MERGED set is the active set with
+ * exactly the listed pairs replaced: on every level every other pair keeps its spectra and its partition count, and only
+ * the listed filters are uploaded and transformed.  One moving source of a 64 x 64 renderer is one column: 64 filters out
+ * of 4096.
+ * The plain call leaves every level as bfir_engine_set_coeff_matrix_levels with the merged set, made at the same block,
+ * would: the filter store (byte for byte over the partitions below each pair's count, zeros past it), the counts, which
+ * levels are active -- a level the merged set newly reaches starts with its next block that begins, one it no longer
+ * reaches stops -- and the choice between the channel-pair and the direct path.  Every delay line is kept.  Unlike the
+ * uniform kind's call it does not cut a fade: while one is pending or running it returns BFIR_ERR_STATE, because a tail
+ * level that has passed its last old block already runs the new set and there is no single active set to patch.
+ * The fade call is bfir_engine_set_coeff_matrix_levels_fade to the merged set -- the same blocks a_f .. a_f + K - 1, blend
+ * and f, bfir_engine_fade_remaining_levels, bfir_engine_reset ending it with the merged set active at every level, a
+ * whole-matrix set call cutting it, the per-level refusal, the stop of a level the merged set leaves, the front-end rule --
+ * with one difference, the one bfir_engine_set_coeff_matrix_pairs_fade has: on every level the new set's product spectra
+ * are NOT the new set's own fma chain but the old set's products plus the listed pairs' difference,
+ *     Y2[o] = Y[o] + sum over the listed (o, i), in input order, of
+ *             ( sum_{p < nb_new} X_i[t - p] H2_{o,i,p}  -  sum_{p < nb_old} X_i[t - p] H_{o,i,p} ),
+ * the new filter's partitions first, then the old filter's negated, in one fma chain behind Y[o], with that level's counts.
+ * This holds for every launch that takes both sets: the head while it fades, a tail level up to its last old block, and
+ * the blocks a tail level had already run when the call was made.  An output without a listed pair is blended with itself.
+ * Identities (r_max = L_last / L_0):
+ *   - blocks before a_f are those of an engine that was never patched;
+ *   - blocks from a_f + K + r_max on are bitwise those of an engine that faded to the merged set with
+ *     bfir_engine_set_coeff_matrix_levels_fade at a_f, under that call's own condition (both sets read every input, or the
+ *     engine cannot pair channels): a tail level runs the merged set's own chain from the block after its last old one, and
+ *     the head first reads that block at most r_k - 1 blocks past the fade's end;
+ *   - the fading blocks and the r_max blocks behind them agree with that engine within rounding, NOT bitwise;
+ *   - the output does not depend on bfir_engine_set_chunk, on how the blocks arrive, or on BFIR_PATCH_FUSED.
+ * BFIR_PATCH_FUSED=0|1, read at creation, multi-level kinds only: on a level whose MAC is k_mac_mimo a launch that takes both
+ * sets runs the old set's MAC and the patch as two launches (0) or as one, k_wpatch (1); the same bits.  The default is 0:
+ * the two launches measured faster ("Pair lists on multi-level engines").  Levels on k_mac_matrix and uniform engines always take the two launches.
+ * A listed pair without a filter in either set is never loaded: nothing is multiplied by zero, an input no filter reads
+ * keeps its NaN to itself.
+ * All refusals come before the device is touched and change nothing.  BFIR_ERR_ARG: a null e, outputs, inputs, coeffs or
+ * lengths; n_pairs < 1; an index outside the matrix; the same pair listed twice; a length outside 0 .. D_(n_levels); for the
+ * fade, fade_blocks < 1 or K L > 2^24.  BFIR_ERR_STATE: an engine without coefficients, or a fade pending or running (both
+ * calls).  BFIR_ERR_UNSUPPORTED: every other kind of engine; for the fade, a merged set with taps on a level no filter of the
+ * old set reaches.  BFIR_ERR_COEFF: a NaN/Inf tap, found before anything is uploaded -- the engine keeps its filters and
+ * stays initialised. */
+int bfir_engine_set_coeff_matrix_levels_pairs(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                              const void *const *coeffs, const int *lengths, double scale);
+int bfir_engine_set_coeff_matrix_levels_pairs_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                   const void *const *coeffs, const int *lengths, double scale,
+                                                   int fade_blocks);
 /* Head blocks of a pending or running fade (fftw_convolver.cpp:275-321 over fade_blocks blocks) of an engine from
  * bfir_engine_create_nup, _levels or _matrix_levels still to be processed; 0 = none.  BFIR_ERR_UNSUPPORTED on every other kind
  * of engine. */
