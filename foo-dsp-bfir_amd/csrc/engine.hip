@@ -186,6 +186,13 @@ struct bfir_engine {
     // k_mac_duo / k_wduo.  lfade_finish clears it on the tails.  patch_fused: on a level whose MAC is k_mac_mimo the two
     // launches are one, k_wpatch (wpatch.hip), the same bits; BFIR_PATCH_FUSED=0|1, read at creation (choose_path)
     bool patch_fused = false;
+    // A coefficient bank (bfir_engine_bank_create; uniform matrix and mimo engines): n rows in the form of H's,
+    // [entries][B][N], each transformed once by bfir_engine_bank_load, with the partition count it was loaded with on the host
+    // (0: empty).  The set calls that name entries copy rows from it into H or H2 with k_bank_gather (bank.hip) over d_gather,
+    // the table of the listed rows; the engine's sets are copies and never point into the bank.
+    void *bank = nullptr;
+    std::vector<int> bank_nb;
+    int *d_gather = nullptr; size_t gather_ints = 0;   // [rows][3]: destination row, entry or -1, partitions (BankArgs)
     void *Yf[2] = {nullptr, nullptr};      // products with H2: [GCo][yf_blocks][N], one per chunk parity like Yb
     int yf_blocks = 0;
     void *ft[2] = {nullptr, nullptr};      // general back end: planar y_old / y_new, [GCo][ft_blocks][L] each
@@ -895,7 +902,7 @@ extern "C" void bfir_engine_destroy(bfir_engine *e)
     big_plan_destroy(&e->bplan);
     for (int st = 0; st < 2; st++) for (int i = 0; i < 2; i++) if (e->tails[st][i]) (void)hipFree(e->tails[st][i]);
     void *bufs[] = {e->H, e->saved[0], e->saved[1], e->d_nblk, e->d_of, e->d_bad, e->d_dither_tab, e->d_dither_state,
-                    e->H2, e->d_nblk2, e->Yf[0], e->Yf[1], e->ft[0], e->ft[1], e->d_patch};
+                    e->H2, e->d_nblk2, e->Yf[0], e->Yf[1], e->ft[0], e->ft[1], e->d_patch, e->bank, e->d_gather};
     for (void *b : bufs) if (b) (void)hipFree(b);
     for (auto &sp : e->spans) { (void)hipEventDestroy(sp.a); (void)hipEventDestroy(sp.b); }
     for (auto ev : e->ev_pool) (void)hipEventDestroy(ev);
@@ -1525,6 +1532,242 @@ extern "C" int bfir_engine_set_coeff_matrix_pairs_fade(bfir_engine *e, int n_pai
     return BFIR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// coefficient banks of a uniform matrix or mimo engine: filters transformed once into a store of the engine's own row form
+// (bfir_engine_bank_create, _bank_load), and the four set calls with bank entries in place of host taps
+// (bfir_engine_set_coeff_matrix_bank, _bank_fade, _pairs_bank, _pairs_bank_fade): one k_bank_gather launch (bank.hip) where
+// the calls with taps upload and transform
+// ---------------------------------------------------------------------------
+static bool bank_kind(const bfir_engine *e) { return e->matrix && !e->mlevels; }
+static int read_store_spectrum(bfir_engine *e, const void *store, int f, int block, void *dst);
+
+extern "C" int bfir_engine_bank_create(bfir_engine *e, int n_entries)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
+    if (n_entries < 1) return BFIR_ERR_ARG;
+    if (e->bank) return BFIR_ERR_STATE;
+    HIP_TRY(hipSetDevice(e->device));
+    if (hipMalloc(&e->bank, (size_t)n_entries * e->B * cbuf_bytes(e)) != hipSuccess) {
+        (void)hipGetLastError();
+        e->bank = nullptr;
+        return BFIR_ERR_HIP;
+    }
+    e->bank_nb.assign((size_t)n_entries, 0);                   // every entry empty; the store itself is not cleared
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_bank_destroy(bfir_engine *e)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
+    if (!e->bank) return BFIR_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    (void)hipFree(e->bank);
+    e->bank = nullptr;
+    e->bank_nb.clear();
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_bank_entries(const bfir_engine *e)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
+    return (int)e->bank_nb.size();
+}
+
+extern "C" int bfir_engine_bank_blocks(const bfir_engine *e, int entry)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
+    if (entry < 0 || (size_t)entry >= e->bank_nb.size()) return BFIR_ERR_ARG;
+    return e->bank_nb[entry];
+}
+
+extern "C" int bfir_engine_bank_load(bfir_engine *e, int first, int n, const void *const *coeffs, int length, int coeff_blocks,
+                                     double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || n < 1 || first < 0 || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
+    if (!e->bank) return BFIR_ERR_STATE;
+    if ((size_t)first + (size_t)n > e->bank_nb.size()) return BFIR_ERR_ARG;
+    const int nb = std::min(coeff_blocks, e->B);
+    FilterRows rows((size_t)n);
+    for (int k = 0; k < n; k++) { rows.taps[k] = coeffs[k]; rows.len[k] = coeffs[k] ? length : 0; }
+    // a NaN / Inf tap anywhere is refused before anything is uploaded: the bank is unchanged
+    int rc = check_rows(e, rows, (size_t)nb * e->L, scale);
+    if (rc != BFIR_OK) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());                            // the store is written on an idle device
+    for (int k = 0; k < n; k++) e->bank_nb[first + k] = 0;     // a failed load leaves them empty
+    rc = load_filters(e, e->bank, first, rows, nb, scale);      // one upload, one transform launch; the rows' other partitions cleared
+    if (rc != BFIR_OK) return rc;
+    for (int k = 0; k < n; k++) e->bank_nb[first + k] = coeffs[k] ? nb : 0;
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_bank_read(bfir_engine *e, int entry, int block, void *dst)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
+    if (!dst || block < 0 || block >= e->B) return BFIR_ERR_ARG;
+    if (!e->bank) return BFIR_ERR_STATE;
+    if (entry < 0 || (size_t)entry >= e->bank_nb.size()) return BFIR_ERR_ARG;
+    if (block >= e->bank_nb[entry]) {   // what a gather writes there: an empty entry has no spectra, a short one zeros behind its count
+        memset(dst, 0, cbuf_bytes(e));
+        return BFIR_OK;
+    }
+    return read_store_spectrum(e, e->bank, entry, block, dst);
+}
+
+namespace {
+struct BankList {
+    std::vector<int> row;        // the rows of the store that are written: filter o C + i
+    std::vector<int> ent;        // the bank entry of each, or -1: no path
+};
+}
+
+// What the four set calls ask of their list (outputs == nullptr: the whole matrix, entries[o C + i]); host arithmetic alone.
+static int bank_list(const bfir_engine *e, int n, const int *outputs, const int *inputs, const int *entries, BankList &bl)
+{
+    const int n_ent = (int)e->bank_nb.size();
+    std::vector<char> listed(outputs ? (size_t)e->Co * e->C : 0, 0);
+    bl.row.resize((size_t)n); bl.ent.resize((size_t)n);
+    for (int k = 0; k < n; k++) {
+        int r = k;
+        if (outputs) {
+            if (outputs[k] < 0 || outputs[k] >= e->Co || inputs[k] < 0 || inputs[k] >= e->C) return BFIR_ERR_ARG;
+            r = outputs[k] * e->C + inputs[k];
+            if (listed[r]) return BFIR_ERR_ARG;                 // the same pair twice
+            listed[r] = 1;
+        }
+        if (entries[k] < -1 || entries[k] >= n_ent) return BFIR_ERR_ARG;
+        bl.row[k] = r; bl.ent[k] = entries[k];
+    }
+    for (int en : bl.ent) if (en >= 0 && e->bank_nb[en] == 0) return BFIR_ERR_STATE;   // an empty entry
+    return BFIR_OK;
+}
+
+// The listed rows of Hdst (H, or H2) from the bank and their partition counts into cnt (nblk, or nblk2): the table goes up,
+// ONE gather is queued on the stream that owns every write to the store, and the host waits for it.  The device is idle.
+static int bank_gather(bfir_engine *e, void *Hdst, std::vector<int> &cnt, const BankList &bl)
+{
+    std::vector<int> tab;
+    tab.reserve(3 * bl.row.size());
+    for (size_t k = 0; k < bl.row.size(); k++) {
+        const int nb = bl.ent[k] < 0 ? 0 : e->bank_nb[bl.ent[k]];
+        tab.push_back(bl.row[k]); tab.push_back(bl.ent[k]); tab.push_back(nb);
+        cnt[bl.row[k]] = nb;
+    }
+    if (tab.size() > e->gather_ints) {
+        if (e->d_gather) (void)hipFree(e->d_gather);
+        e->d_gather = nullptr; e->gather_ints = 0;
+        HIP_TRY(hipMalloc((void **)&e->d_gather, sizeof(int) * tab.size()));
+        e->gather_ints = tab.size();
+    }
+    HIP_TRY(hipMemcpy(e->d_gather, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    BankArgs a;
+    a.bank = e->bank; a.dst = Hdst; a.tab = e->d_gather; a.n_rows = (int)bl.row.size();
+    a.part_bytes = cbuf_bytes(e); a.row_bytes = (unsigned long long)e->B * a.part_bytes;
+    if (launch_bank_gather(a, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    return BFIR_OK;
+}
+
+// The four calls.  pairs: a list (outputs, inputs, entries of n), else the whole matrix (entries[o C + i]); fade_blocks < 0:
+// the plain call.  The order of the refusals is that of the calls with taps, with the bank's own behind the arguments.
+static int set_coeff_bank(bfir_engine *e, bool pairs, int n, const int *outputs, const int *inputs, const int *entries,
+                          bool fade, int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
+    if (fade && (e->n_eng > 1 || e->d_dither_tab)) return BFIR_ERR_UNSUPPORTED;   // as every fade
+    const int P = e->Co * e->C;
+    if (!entries || (pairs && (!outputs || !inputs || n < 1))) return BFIR_ERR_ARG;
+    if (!e->bank) return BFIR_ERR_STATE;
+    BankList bl;
+    int rc = bank_list(e, pairs ? n : P, pairs ? outputs : nullptr, inputs, entries, bl);
+    if (rc == BFIR_OK && fade) rc = check_fade_args(e, fade_blocks);
+    if (rc != BFIR_OK) return rc;
+    if (pairs && !bfir_engine_is_initialized(e)) return BFIR_ERR_STATE;   // nothing to patch
+    if (bl.row.size() > 65535) return BFIR_ERR_UNSUPPORTED;      // the gather's grid; a matrix has 64 x 64 rows at most
+    HIP_TRY(hipSetDevice(e->device));
+    // queued work may still read the store, what was H before the last fade's swap, or a table: all written on an idle device
+    HIP_TRY(hipDeviceSynchronize());
+    if (!fade) {
+        e->fade_len = e->fade_pos = 0;                          // a plain change during a fade cancels it: the old set stays
+        e->fade_patch = false;
+        if (!pairs) e->eng_init[0] = 0;                         // as bfir_engine_set_coeff_matrix
+        rc = bank_gather(e, e->H, e->nblk, bl);
+        if (rc != BFIR_OK) return rc;
+        return matrix_counts_set(e);
+    }
+    rc = fade_prepare(e, P);
+    if (rc != BFIR_OK) return rc;
+    if (pairs) {
+        // the merged set: the whole store copied, then the listed rows, both on e->stream and so in order
+        HIP_TRY(hipMemcpyAsync(e->H2, e->H, (size_t)P * e->B * cbuf_bytes(e), hipMemcpyDeviceToDevice, e->stream));
+        e->nblk2 = e->nblk;
+    } else {
+        e->nblk2.assign(e->nblk.size(), 0);
+    }
+    rc = bank_gather(e, e->H2, e->nblk2, bl);
+    if (rc != BFIR_OK) return rc;
+    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->nblk2.size(), hipMemcpyHostToDevice));
+    if (pairs) {   // k_patch_pairs' table: per output its listed pairs in input order
+        std::vector<char> listed((size_t)P, 0);
+        for (int r : bl.row) listed[r] = 1;
+        std::vector<int> tab((size_t)e->Co + 1);
+        for (int o = 0; o < e->Co; o++) {
+            tab[o] = (int)(tab.size() - (e->Co + 1)) / 3;
+            for (int i = 0; i < e->C; i++) {
+                const int r = o * e->C + i;
+                if (listed[r]) { tab.push_back(i); tab.push_back(e->nblk2[r]); tab.push_back(e->nblk[r]); }
+            }
+        }
+        tab[e->Co] = (int)bl.row.size();
+        if (tab.size() > e->patch_ints) {
+            if (e->d_patch) (void)hipFree(e->d_patch);
+            e->d_patch = nullptr; e->patch_ints = 0;
+            HIP_TRY(hipMalloc((void **)&e->d_patch, sizeof(int) * tab.size()));
+            e->patch_ints = tab.size();
+        }
+        HIP_TRY(hipMemcpy(e->d_patch, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    }
+    if (e->pair_cap) {   // set_coeff_fade's rule: channel pairs only while every input is read under BOTH sets
+        e->pair_new = every_input_read(e, [&](int, int r) { return e->nblk2[r]; });
+        matrix_take_path(e, e->pair_new && every_input_read(e, [&](int, int r) { return e->nblk[r]; }));
+    }
+    fade_begin(e, fade_blocks);
+    e->fade_patch = pairs;
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_bank(bfir_engine *e, const int *entries)
+{
+    return set_coeff_bank(e, false, 0, nullptr, nullptr, entries, false, 0);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_bank_fade(bfir_engine *e, const int *entries, int fade_blocks)
+{
+    return set_coeff_bank(e, false, 0, nullptr, nullptr, entries, true, fade_blocks);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_pairs_bank(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                       const int *entries)
+{
+    return set_coeff_bank(e, true, n_pairs, outputs, inputs, entries, false, 0);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_pairs_bank_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                            const int *entries, int fade_blocks)
+{
+    return set_coeff_bank(e, true, n_pairs, outputs, inputs, entries, true, fade_blocks);
+}
+
 extern "C" int bfir_engine_fade_remaining(const bfir_engine *e)
 {
     if (!e) return BFIR_ERR_ARG;
@@ -1532,13 +1775,13 @@ extern "C" int bfir_engine_fade_remaining(const bfir_engine *e)
     return e->fade_len > 0 ? e->fade_len - e->fade_pos : 0;
 }
 
-// partition spectrum `block` of filter `f` (H row) to host, in the reference's grouped layout
-static int read_spectrum(bfir_engine *e, int f, int block, void *dst)
+// partition spectrum `block` of row `f` of a filter store (H, or the bank) to host, in the reference's grouped layout
+static int read_store_spectrum(bfir_engine *e, const void *store, int f, int block, void *dst)
 {
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     const size_t cb = cbuf_bytes(e);
-    HIP_TRY(hipMemcpy(dst, (char *)e->H + ((size_t)f * e->B + block) * cb, cb, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(dst, (const char *)store + ((size_t)f * e->B + block) * cb, cb, hipMemcpyDeviceToHost));
     if (e->big) {   // ... and natural bin order: bin k1 + M1 k2 is kept at position k1 M2 + k2 (bigconv.hip), in either layout
         const int l1 = e->bplan.log2m1, M2 = 1 << e->bplan.log2m2;
         const bool ilv = e->ilv;
@@ -1565,6 +1808,9 @@ static int read_spectrum(bfir_engine *e, int f, int block, void *dst)
     }
     return BFIR_OK;
 }
+
+// ... of filter `f` of the active set
+static int read_spectrum(bfir_engine *e, int f, int block, void *dst) { return read_store_spectrum(e, e->H, f, block, dst); }
 
 extern "C" int bfir_engine_read_coeff(bfir_engine *e, int channel, int block, void *dst)
 {

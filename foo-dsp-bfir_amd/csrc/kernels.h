@@ -266,6 +266,21 @@ inline __host__ __device__ PatchArgs wpatch_patch_args(const WpatchArgs &d)
 bool wpatch_supported(const WpatchArgs &d);                 // the grid of the launch fits
 int launch_wpatch(const WpatchArgs &d, hipStream_t s);      // 0, or -1 if !wpatch_supported(d) (nothing launched)
 
+// bank.hip: k_bank_gather, the listed rows of a filter store (H, or a fade's H2) from a coefficient bank, a store of the
+// same row form ([entries][B][N], bfir_engine_bank_create), in one launch.  Row tab[3 j] of dst gets the first tab[3 j + 2]
+// partitions of bank entry tab[3 j + 1] and zeros behind them; an entry of -1 gives a row of zeros.  A row is bytes: both
+// precisions and both layouts are one kernel.
+struct BankArgs {
+    const void *bank; void *dst;                              // 16-byte aligned
+    const int *tab;                                           // device [n_rows][3]: destination row, entry or -1, partitions (<= B)
+    int n_rows;
+    unsigned long long row_bytes, part_bytes;                 // B N realsize and N realsize, multiples of 16
+};
+constexpr int BFIR_BANK_SPAN = 4096;                        // the bytes one workgroup moves per step: 256 lanes of 16
+constexpr int BFIR_BANK_STEPS = 4;                          // steps per workgroup
+bool bank_gather_supported(const BankArgs &a);              // alignment, and the grid of the launch fits
+int launch_bank_gather(const BankArgs &a, hipStream_t s);   // 0, or -1 if !bank_gather_supported(a) (nothing launched)
+
 // a11 + a12: inverse real FFT of Y[gc][t] (grouped layout, times in_scale),
 // first L samples to dst + gc*dst_ch_stride + t*L.
 struct InvArgs {

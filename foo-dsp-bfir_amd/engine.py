@@ -362,6 +362,85 @@ class BrutefirMatrix(Brutefir):
         args, _keep = self._pair_args(pairs, filters, length, coeff_blocks)
         return self._lib.bfir_engine_set_coeff_matrix_pairs_fade(self._h, *args, float(scale), int(fade_blocks))
 
+    # A coefficient bank: filters transformed once and kept on the device, then named by index.  The calls below are
+    # set_coeff / set_coeff_fade / set_coeff_pairs / set_coeff_pairs_fade with a bank index (or None = no path) in place
+    # of every filter; they take no taps and copy rows on the device in one kernel launch.  The multi-level classes have no
+    # banks: there the library answers every one of these with ERR_UNSUPPORTED.
+
+    def bank_create(self, n):
+        """bfir_engine_bank_create: a bank of n empty entries on the engine's device.  Returns 0 or an ERR_* code
+        (ERR_STATE: the engine has one)."""
+        return self._lib.bfir_engine_bank_create(self._h, int(n))
+
+    def bank_destroy(self):
+        """bfir_engine_bank_destroy: frees the bank; the engine's active filters are copies and stay."""
+        return self._lib.bfir_engine_bank_destroy(self._h)
+
+    def bank_entries(self):
+        """bfir_engine_bank_entries: the entry count, 0 without a bank (< 0: an ERR_* code)."""
+        return self._lib.bfir_engine_bank_entries(self._h)
+
+    def bank_blocks(self, entry):
+        """bfir_engine_bank_blocks: the partition count entry `entry` was loaded with, 0 = empty (< 0: an ERR_* code)."""
+        return self._lib.bfir_engine_bank_blocks(self._h, int(entry))
+
+    def bank_load(self, first, filters, length=None, coeff_blocks=None, scale=1.0):
+        """bfir_engine_bank_load: filters[k] (taps in working precision, or None = the entry becomes empty) into entry
+        first + k, all in one upload and one transform launch; length / coeff_blocks / scale as set_coeff, and the entry's
+        partition count is min(coeff_blocks, B).  Returns 0 or an ERR_* code (ERR_COEFF: a NaN / Inf tap, the bank is
+        unchanged)."""
+        rd = _real_dtype(self.s)
+        arrs = [None if h is None else np.ascontiguousarray(h, dtype=rd) for h in filters]
+        given = [a for a in arrs if a is not None]
+        length = (given[0].size if given else 0) if length is None else length
+        coeff_blocks = self.B if coeff_blocks is None else coeff_blocks
+        assert all(a.size >= length for a in given), "every filter of a bank_load call holds `length` taps"
+        ptrs = (C.c_void_p * max(1, len(arrs)))(*[None if a is None else a.ctypes.data for a in arrs])
+        return self._lib.bfir_engine_bank_load(self._h, int(first), len(arrs), ptrs, length, coeff_blocks, float(scale))
+
+    def bank_read(self, entry, block):
+        """bfir_engine_bank_read: partition spectrum `block` of a bank entry, as coeff_block gives the engine's; zeros at
+        and past the entry's partition count."""
+        dst = np.zeros(2 * self.L, dtype=_real_dtype(self.s))
+        rc = self._lib.bfir_engine_bank_read(self._h, int(entry), int(block), dst.ctypes.data)
+        if rc != 0:
+            raise BfirError(rc, "bfir_engine_bank_read")
+        return dst
+
+    @staticmethod
+    def _bank_ints(entries):
+        return (C.c_int * max(1, len(entries)))(*[-1 if en is None else int(en) for en in entries])
+
+    def set_coeff_bank(self, rows):
+        """bfir_engine_set_coeff_matrix_bank: rows[o][i] is the bank entry of h_{o,i}, or None = no path.  The engine is left
+        as set_coeff with the entries' taps leaves it, every filter at its entry's partition count.  Returns 0 or an ERR_*
+        code (ERR_STATE: no bank, or an empty entry)."""
+        assert len(rows) == self.n_out and all(len(r) == self.n_in for r in rows)
+        return self._lib.bfir_engine_set_coeff_matrix_bank(self._h, self._bank_ints([en for r in rows for en in r]))
+
+    def set_coeff_bank_fade(self, rows, fade_blocks):
+        """bfir_engine_set_coeff_matrix_bank_fade: set_coeff_fade to the set rows names, over the next `fade_blocks`
+        blocks."""
+        assert len(rows) == self.n_out and all(len(r) == self.n_in for r in rows)
+        return self._lib.bfir_engine_set_coeff_matrix_bank_fade(self._h, self._bank_ints([en for r in rows for en in r]),
+                                                                int(fade_blocks))
+
+    def _pair_bank_args(self, pairs, entries):
+        assert len(pairs) == len(entries)
+        outs = (C.c_int * max(1, len(pairs)))(*[int(o) for o, _ in pairs])
+        ins = (C.c_int * max(1, len(pairs)))(*[int(i) for _, i in pairs])
+        return len(pairs), outs, ins, self._bank_ints(entries)
+
+    def set_coeff_pairs_bank(self, pairs, entries):
+        """bfir_engine_set_coeff_matrix_pairs_bank: bank entry entries[k] (or None = the path is removed) replaces h_{o,i}
+        for pairs[k] = (o, i); every other pair keeps its filter.  Returns 0 or an ERR_* code."""
+        return self._lib.bfir_engine_set_coeff_matrix_pairs_bank(self._h, *self._pair_bank_args(pairs, entries))
+
+    def set_coeff_pairs_bank_fade(self, pairs, entries, fade_blocks):
+        """bfir_engine_set_coeff_matrix_pairs_bank_fade: the same change, crossfaded over the next `fade_blocks` blocks."""
+        return self._lib.bfir_engine_set_coeff_matrix_pairs_bank_fade(self._h, *self._pair_bank_args(pairs, entries),
+                                                                      int(fade_blocks))
+
     def run(self, inbuf, outbuf=None):
         """inbuf: [n_blocks*L, n_in] frames in the input format.  Returns (rc, outbuf [n_blocks*L, n_out])."""
         x = np.ascontiguousarray(inbuf, dtype=_FMT_DTYPES[self.in_format])

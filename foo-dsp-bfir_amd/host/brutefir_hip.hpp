@@ -201,6 +201,36 @@ public:
                                                        coeff_blocks, scale, fade_blocks);
     }
 
+    // A mimo engine's coefficient bank: filters transformed once and kept on the device (bfir_engine_bank_create, _destroy,
+    // _entries, _blocks, _load, _read), then named by index.  coeffs[k] of bank_load: the `length` taps of entry first + k, or
+    // null (the entry becomes empty); an entry keeps the partition count min(coeff_blocks, filter_blocks) it was loaded with.
+    int bank_create(int n_entries) { return m_e ? bfir_engine_bank_create(m_e, n_entries) : -1; }
+    int bank_destroy() { return m_e ? bfir_engine_bank_destroy(m_e) : -1; }
+    int bank_entries() { return m_e ? bfir_engine_bank_entries(m_e) : -1; }
+    int bank_blocks(int entry) { return m_e ? bfir_engine_bank_blocks(m_e, entry) : -1; }
+    int bank_load(int first, int n, void **coeffs, int length, int coeff_blocks, double scale)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_bank_load(m_e, first, n, (const void *const *)coeffs, length, coeff_blocks, scale);
+    }
+    int bank_read(int entry, int block, void *dst) { return m_e ? bfir_engine_bank_read(m_e, entry, block, dst) : -1; }
+    // The four coefficient changes of a mimo engine with bank entries in place of taps: entries[o * n_inputs + i] (the whole
+    // matrix) or entries[k] for the pair (outputs[k], inputs[k]) is a bank index, or -1 = no path
+    // (bfir_engine_set_coeff_matrix_bank, _bank_fade, _pairs_bank, _pairs_bank_fade).
+    int set_coeff_matrix_bank(const int *entries) { return m_e ? bfir_engine_set_coeff_matrix_bank(m_e, entries) : -1; }
+    int set_coeff_matrix_bank_fade(const int *entries, int fade_blocks)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_bank_fade(m_e, entries, fade_blocks) : -1;
+    }
+    int set_coeff_matrix_pairs_bank(int n_pairs, const int *outputs, const int *inputs, const int *entries)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_pairs_bank(m_e, n_pairs, outputs, inputs, entries) : -1;
+    }
+    int set_coeff_matrix_pairs_bank_fade(int n_pairs, const int *outputs, const int *inputs, const int *entries, int fade_blocks)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_pairs_bank_fade(m_e, n_pairs, outputs, inputs, entries, fade_blocks) : -1;
+    }
+
     // A multi-level matrix engine's filters: coeffs[o * n_inputs + i] the taps of h_{o,i} or null (no path), lengths[o *
     // n_inputs + i] its tap count, each filter split between the levels (bfir_engine_set_coeff_matrix_levels).
     int set_coeff_matrix_levels(void **coeffs, const int *lengths, double scale)

@@ -380,6 +380,75 @@ int bfir_engine_set_coeff_matrix_pairs(bfir_engine *e, int n_pairs, const int *o
 int bfir_engine_set_coeff_matrix_pairs_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
                                             const void *const *coeffs, int length, int coeff_blocks, double scale,
                                             int fade_blocks);
+
+/* Coefficient banks (bfir_engine_create_matrix, bfir_engine_create_mimo; both precisions): filter sets that stay on the
+ * device, transformed once, and are switched by index -- BruteFIR's model of coefficient sets loaded at start and a filter
+ * pointed at another set at run time (the `cfc` command).  A bank is a store of n_entries filters in the form of the
+ * engine's own filter store ([n_entries][filter_blocks][2 filter_length] spectra in the engine's precision and spectrum
+ * layout) on the engine's device.  The four bfir_engine_set_coeff_matrix_*bank* calls below are the four calls with taps
+ * with a bank index in place of every filter: where those upload and transform, these copy rows on the device, all listed
+ * rows in ONE kernel launch (k_bank_gather), and take no host taps.  Every entry keeps the partition count it was loaded
+ * with, so the filters of one call may have different counts (which the calls with taps, with one coeff_blocks per call,
+ * cannot give).  The engine's sets are COPIES: loading over an entry, or destroying the bank, changes nothing in the engine.
+ * Multi-level kinds (bfir_engine_create_matrix_levels, _mimo_levels) have no banks: each of their levels would need a store
+ * of its own.  Every call of this group returns BFIR_ERR_UNSUPPORTED on an engine of any kind but the two above, and
+ * BFIR_ERR_ARG for a null e.
+ *
+ * bfir_engine_bank_create allocates the store; every entry is empty (partition count 0) and the store is not cleared.
+ * BFIR_ERR_ARG: n_entries < 1.  BFIR_ERR_STATE: the engine has a bank.  BFIR_ERR_HIP: the allocation failed; there is then
+ * no bank.
+ * bfir_engine_bank_destroy waits for queued work and frees the bank (no bank: BFIR_OK, nothing happens);
+ * bfir_engine_destroy does the same.  The engine's active filters and a running fade are untouched.
+ * bfir_engine_bank_entries: the entry count, 0 without a bank.  bfir_engine_bank_blocks: the partition count of an entry,
+ * 0 = empty; BFIR_ERR_ARG for an entry outside the bank (any entry, without one). */
+int bfir_engine_bank_create(bfir_engine *e, int n_entries);
+int bfir_engine_bank_destroy(bfir_engine *e);
+int bfir_engine_bank_entries(const bfir_engine *e);
+int bfir_engine_bank_blocks(const bfir_engine *e, int entry);
+/* Entries first .. first + n - 1 written: coeffs[k] is `length` taps in working precision, or NULL = the entry becomes empty;
+ * length / coeff_blocks / scale as bfir_engine_set_coeff_matrix, and the entry's partition count is min(coeff_blocks,
+ * filter_blocks).  All n filters go up in one upload and one transform launch, after queued work has finished.  Calls may
+ * differ in length, coeff_blocks and scale.  An entry's spectra are, byte for byte, those bfir_engine_set_coeff_matrix
+ * gives a filter of the same taps, coeff_blocks and scale.
+ * BFIR_ERR_ARG: a null coeffs, n < 1, first < 0, length < 0, coeff_blocks < 1, first + n past the bank.  BFIR_ERR_STATE: no
+ * bank (checked before the range).  BFIR_ERR_COEFF: a NaN/Inf tap in any filter, found before anything is uploaded -- the
+ * bank is unchanged. */
+int bfir_engine_bank_load(bfir_engine *e, int first, int n, const void *const *coeffs, int length, int coeff_blocks,
+                          double scale);
+/* Partition spectrum `block` of an entry (2 filter_length reals) in the form bfir_engine_read_coeff_matrix gives.  A block at
+ * or past the entry's partition count reads as zeros (every block of an empty entry): what a set call writes there.
+ * BFIR_ERR_ARG: a null dst, block outside 0 .. filter_blocks - 1, an entry outside the bank.  BFIR_ERR_STATE: no bank
+ * (checked before the entry). */
+int bfir_engine_bank_read(bfir_engine *e, int entry, int block, void *dst);
+/* bfir_engine_set_coeff_matrix, _matrix_fade, _matrix_pairs and _matrix_pairs_fade with bank entries: entries[o * n_inputs +
+ * i] (the whole matrix) or entries[k] for the pair (outputs[k], inputs[k]) is a bank index, or -1 = no path (the NULL of
+ * the calls with taps; in a pairs call the path is removed).  A row of the engine's store written from an entry of count c
+ * holds the entry's first c partitions and zeros up to filter_blocks, and its partition count is c: the row, the count
+ * and so every output byte are those of the call with taps for the same taps, coeff_blocks = c and scale.  One entry may be
+ * named for any number of pairs.  Everything else is the contract of the call with taps:
+ *   _bank        a fade in progress is cancelled, the delay line is kept, the engine becomes initialised;
+ *   _bank_fade   bfir_engine_set_coeff_matrix_fade, the new set gathered from the bank;
+ *   _pairs_bank  bfir_engine_set_coeff_matrix_pairs, merged-set semantics included: every pair not listed keeps its
+ *                spectra and its count; during a fade the fade is cancelled and the old set patched;
+ *   _pairs_bank_fade  bfir_engine_set_coeff_matrix_pairs_fade, merged-set semantics and the patched y_new (NOT bitwise
+ *                the whole-matrix fade's) included; nb_new of a listed pair is its entry's count.
+ * With entries of different counts in one call the result is that of the merged set with every filter at its own count: the
+ * plain calls give the bytes of one call with taps per distinct count.
+ * All refusals come before the device is touched and change nothing, in this order.  BFIR_ERR_UNSUPPORTED: the engine's
+ * kind; for the fade calls a batch or an engine that dithers its output.  BFIR_ERR_ARG: a null entries, outputs or inputs;
+ * n_pairs < 1.  BFIR_ERR_STATE: no bank.  BFIR_ERR_ARG: a pair outside the matrix; the same pair listed twice; an index
+ * outside -1 .. n_entries - 1.  BFIR_ERR_STATE: a named entry is empty.  For the fade calls BFIR_ERR_ARG: fade_blocks < 1 or
+ * K L > 2^24, then BFIR_ERR_STATE: an engine without coefficients, a fade pending or running.  For _pairs_bank
+ * BFIR_ERR_STATE: an engine without coefficients.
+ * The calls wait for queued work, upload the table of the listed rows and the counts, launch the gather once on the
+ * engine's stream and wait for it; they allocate nothing but the table when it grows (and, as every fade, the second set
+ * at the engine's first fade). */
+int bfir_engine_set_coeff_matrix_bank(bfir_engine *e, const int *entries);
+int bfir_engine_set_coeff_matrix_bank_fade(bfir_engine *e, const int *entries, int fade_blocks);
+int bfir_engine_set_coeff_matrix_pairs_bank(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                            const int *entries);
+int bfir_engine_set_coeff_matrix_pairs_bank_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                 const int *entries, int fade_blocks);
 /* Blocks of a pending or running fade still to be processed; 0 = none.  < 0: error. */
 int bfir_engine_fade_remaining(const bfir_engine *e);
 
