@@ -86,6 +86,17 @@ SIGNATURES = {
     "bfir_engine_set_coeff_matrix_bank_fade": (_ci, [_vp, _pi, _ci]),
     "bfir_engine_set_coeff_matrix_pairs_bank": (_ci, [_vp, _ci, _pi, _pi, _pi]),
     "bfir_engine_set_coeff_matrix_pairs_bank_fade": (_ci, [_vp, _ci, _pi, _pi, _pi, _ci]),
+    "bfir_engine_levels_bank_create": (_ci, [_vp, _ci]),
+    "bfir_engine_levels_bank_destroy": (_ci, [_vp]),
+    "bfir_engine_levels_bank_entries": (_ci, [_vp]),
+    "bfir_engine_levels_bank_length": (_ci, [_vp, _ci]),
+    "bfir_engine_levels_bank_blocks": (_ci, [_vp, _ci, _ci]),
+    "bfir_engine_levels_bank_load": (_ci, [_vp, _ci, _ci, C.POINTER(_vp), _pi, _cd]),
+    "bfir_engine_levels_bank_read": (_ci, [_vp, _ci, _ci, _ci, _vp]),
+    "bfir_engine_set_coeff_matrix_levels_bank": (_ci, [_vp, _pi]),
+    "bfir_engine_set_coeff_matrix_levels_bank_fade": (_ci, [_vp, _pi, _ci]),
+    "bfir_engine_set_coeff_matrix_levels_pairs_bank": (_ci, [_vp, _ci, _pi, _pi, _pi]),
+    "bfir_engine_set_coeff_matrix_levels_pairs_bank_fade": (_ci, [_vp, _ci, _pi, _pi, _pi, _ci]),
     "bfir_engine_fade_remaining": (_ci, [_vp]),
     "bfir_engine_create_nup": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_set_coeff_nup": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd]),

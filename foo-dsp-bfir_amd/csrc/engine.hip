@@ -193,6 +193,11 @@ struct bfir_engine {
     void *bank = nullptr;
     std::vector<int> bank_nb;
     int *d_gather = nullptr; size_t gather_ints = 0;   // [rows][3]: destination row, entry or -1, partitions (BankArgs)
+    // The bank of a multi-level matrix or mimo engine (bfir_engine_levels_bank_create): one such store per level, in `bank` of
+    // the head and of every tail, [entries][blocks[k]][2 L_k], loaded through the level split (bfir_engine_levels_bank_load).
+    // The head keeps every entry's tap count (0: empty) and its partitions on every level, [entry][BFIR_MAX_LEVELS]; its
+    // d_gather is k_lbank_gather's table (lbank.hip), [rows][2 + BFIR_MAX_LEVELS], for all levels of a call in one launch.
+    std::vector<int> lbank_len, lbank_nb;
     void *Yf[2] = {nullptr, nullptr};      // products with H2: [GCo][yf_blocks][N], one per chunk parity like Yb
     int yf_blocks = 0;
     void *ft[2] = {nullptr, nullptr};      // general back end: planar y_old / y_new, [GCo][ft_blocks][L] each
@@ -1215,26 +1220,101 @@ static int split_counts_set(bfir_engine *e, const LevelSplit &sp)
     return BFIR_OK;
 }
 
+// Where the rows of a set call on a split engine come from: host taps (rows, scale), which every level uploads and
+// transforms, or entries of the engine's bank (bfir_engine_levels_bank_create; ent[j]: the entry of row j, -1: none), which
+// every level holds transformed already.  set_coeff_split, set_coeff_split_fade and set_pairs_split ask the source for its
+// checks and its split and are otherwise the same for both: where taps are loaded level by level, entries are marked for ONE
+// gather behind the loop (lbank_gather).
+namespace {
+struct SplitSource {
+    const FilterRows *rows = nullptr; double scale = 1.0;
+    const std::vector<int> *ent = nullptr;
+};
+}
+
+static SplitSource taps_source(const FilterRows &rows, double scale) { SplitSource s; s.rows = &rows; s.scale = scale; return s; }
+static int source_check_lengths(const bfir_engine *e, const SplitSource &src) { return src.rows ? check_split_lengths(e, *src.rows) : BFIR_OK; }
+static int source_check_rows(const bfir_engine *e, const SplitSource &src) { return src.rows ? check_rows(e, *src.rows, SIZE_MAX, src.scale) : BFIR_OK; }
+
+// The split of a source.  Bank entries: counts only, what the host table holds since the entry was loaded; no FilterRows.
+static LevelSplit source_split(const bfir_engine *e, const SplitSource &src)
+{
+    if (src.rows) return split_rows(e, *src.rows);
+    LevelSplit sp;
+    for (int k = 0; k <= e->n_tail; k++) {
+        LevelSplit::Level &s = sp.lv[k];
+        s.nb.assign(src.ent->size(), 0);
+        for (size_t j = 0; j < src.ent->size(); j++) {
+            const int en = (*src.ent)[j];
+            s.nb[j] = en < 0 ? 0 : e->lbank_nb[(size_t)en * BFIR_MAX_LEVELS + k];
+            s.nb_max = std::max(s.nb_max, s.nb[j]);
+        }
+    }
+    return sp;
+}
+
+static_assert(BFIR_LBANK_LEVELS == BFIR_MAX_LEVELS, "k_lbank_gather takes one descriptor per level");
+
+// k_lbank_gather's level descriptors: level k of the bank into dst[k] (H or H2 of the level; null: not part of the launch)
+static LBankArgs lbank_args(const bfir_engine *e, void *const (&dst)[BFIR_MAX_LEVELS])
+{
+    LBankArgs a = {};
+    for (int k = 0; k <= e->n_tail; k++) {
+        const bfir_engine *l = level(e, k);
+        a.lv[k].bank = l->bank; a.lv[k].dst = dst[k];
+        a.lv[k].part_bytes = cbuf_bytes(l); a.lv[k].row_bytes = (unsigned long long)l->B * a.lv[k].part_bytes;
+    }
+    return a;
+}
+
+// Row j of the call (destination row (*list)[j], or j: the whole matrix) from bank entry ent[j], on every level with a
+// destination: the table goes up, ONE gather for all levels is queued on e->stream behind whatever the call has queued
+// there, and the host waits for it.  The device is idle; the counts are the caller's (the source's split).
+static int lbank_gather(bfir_engine *e, void *const (&dst)[BFIR_MAX_LEVELS], const std::vector<int> &ent, const std::vector<int> *list)
+{
+    const int W = 2 + BFIR_MAX_LEVELS;
+    std::vector<int> tab(W * ent.size(), 0);
+    for (size_t j = 0; j < ent.size(); j++) {
+        tab[W * j] = list ? (*list)[j] : (int)j; tab[W * j + 1] = ent[j];
+        for (int k = 0; k <= e->n_tail && ent[j] >= 0; k++) tab[W * j + 2 + k] = e->lbank_nb[(size_t)ent[j] * BFIR_MAX_LEVELS + k];
+    }
+    if (tab.size() > e->gather_ints) {
+        if (e->d_gather) (void)hipFree(e->d_gather);
+        e->d_gather = nullptr; e->gather_ints = 0;
+        HIP_TRY(hipMalloc((void **)&e->d_gather, sizeof(int) * tab.size()));
+        e->gather_ints = tab.size();
+    }
+    HIP_TRY(hipMemcpy(e->d_gather, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    LBankArgs a = lbank_args(e, dst);
+    a.tab = e->d_gather; a.n_rows = (int)ent.size();
+    if (launch_lbank_gather(a, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;   // checked by the entry point: not reached
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    return BFIR_OK;
+}
+
 // The filters of a two-level, multi-level or multi-level matrix engine, split at every D_k: taps [0, D_1) to the head,
 // [D_k, D_(k+1)) to level k.  Mid-stream every delay line is kept: the head takes the new filters from the next block,
 // level k from its next block that completes; what a level has already put into its time ring still plays.
-static int set_coeff_split(bfir_engine *e, const FilterRows &rows, double scale)
+static int set_coeff_split(bfir_engine *e, const SplitSource &src)
 {
-    int rc = check_split_lengths(e, rows);
+    int rc = source_check_lengths(e, src);
     if (rc != BFIR_OK) return rc;
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
     if (e->fade_len > 0) { e->fade_len = e->fade_pos = 0; e->fade_patch = false; lfade_finish(e, false); }   // a plain change during a fade cancels it: a hard cut
     e->eng_init[0] = 0;
-    rc = check_rows(e, rows, SIZE_MAX, scale);
+    rc = source_check_rows(e, src);
     if (rc != BFIR_OK) return rc;
-    const LevelSplit sp = split_rows(e, rows);
+    const LevelSplit sp = source_split(e, src);
+    void *gather[BFIR_MAX_LEVELS] = {};
     // the head, then level after level: the part of every filter that falls into the level and its partitions there
     for (int k = 0; k <= e->n_tail; k++) {
         bfir_engine *l = level(e, k);
         const LevelSplit::Level &s = sp.lv[k];
         if (s.nb_max > 0) {   // a level on which no filter has taps does no work at all (a matrix head: its MAC stores zeros)
-            rc = load_filters(l, l->H, 0, s.rows, s.nb_max, scale);
+            if (src.ent) gather[k] = l->H;
+            else rc = load_filters(l, l->H, 0, s.rows, s.nb_max, src.scale);
             if (rc != BFIR_OK) return rc;
         }
         l->nblk = s.nb;
@@ -1242,6 +1322,7 @@ static int set_coeff_split(bfir_engine *e, const FilterRows &rows, double scale)
         if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
         else if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->nblk.size(), hipMemcpyHostToDevice));
     }
+    if (src.ent) { rc = lbank_gather(e, gather, *src.ent, nullptr); if (rc != BFIR_OK) return rc; }
     return split_counts_set(e, sp);
 }
 
@@ -1250,7 +1331,8 @@ extern "C" int bfir_engine_set_coeff_nup(bfir_engine *e, const void *const *coef
     if (!e) return BFIR_ERR_ARG;
     if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
     if (!coeffs || n_coeffs < 0) return BFIR_ERR_ARG;
-    return set_coeff_split(e, diagonal_rows(e, coeffs, n_coeffs, length), scale);
+    const FilterRows rows = diagonal_rows(e, coeffs, n_coeffs, length);
+    return set_coeff_split(e, taps_source(rows, scale));
 }
 
 extern "C" int bfir_engine_set_coeff_levels(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale)
@@ -1258,7 +1340,8 @@ extern "C" int bfir_engine_set_coeff_levels(bfir_engine *e, const void *const *c
     if (!e) return BFIR_ERR_ARG;
     if (!e->levels) return BFIR_ERR_UNSUPPORTED;
     if (!coeffs || n_coeffs < 0) return BFIR_ERR_ARG;
-    return set_coeff_split(e, diagonal_rows(e, coeffs, n_coeffs, length), scale);
+    const FilterRows rows = diagonal_rows(e, coeffs, n_coeffs, length);
+    return set_coeff_split(e, taps_source(rows, scale));
 }
 
 // The n_out x n_in filters of a multi-level matrix engine, each of its own length: coeffs[o n_in + i], NULL = no path
@@ -1267,7 +1350,8 @@ extern "C" int bfir_engine_set_coeff_matrix_levels(bfir_engine *e, const void *c
     if (!e) return BFIR_ERR_ARG;
     if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
     if (!coeffs || !lengths) return BFIR_ERR_ARG;
-    return set_coeff_split(e, matrix_rows(e, coeffs, lengths, 0), scale);
+    const FilterRows rows = matrix_rows(e, coeffs, lengths, 0);
+    return set_coeff_split(e, taps_source(rows, scale));
 }
 
 // ---------------------------------------------------------------------------
@@ -1630,9 +1714,11 @@ struct BankList {
 }
 
 // What the four set calls ask of their list (outputs == nullptr: the whole matrix, entries[o C + i]); host arithmetic alone.
-static int bank_list(const bfir_engine *e, int n, const int *outputs, const int *inputs, const int *entries, BankList &bl)
+// filled: per entry of the bank, 0 = empty (bank_nb, or a multi-level engine's lbank_len).
+static int bank_list(const bfir_engine *e, const std::vector<int> &filled, int n, const int *outputs, const int *inputs,
+                     const int *entries, BankList &bl)
 {
-    const int n_ent = (int)e->bank_nb.size();
+    const int n_ent = (int)filled.size();
     std::vector<char> listed(outputs ? (size_t)e->Co * e->C : 0, 0);
     bl.row.resize((size_t)n); bl.ent.resize((size_t)n);
     for (int k = 0; k < n; k++) {
@@ -1646,7 +1732,7 @@ static int bank_list(const bfir_engine *e, int n, const int *outputs, const int 
         if (entries[k] < -1 || entries[k] >= n_ent) return BFIR_ERR_ARG;
         bl.row[k] = r; bl.ent[k] = entries[k];
     }
-    for (int en : bl.ent) if (en >= 0 && e->bank_nb[en] == 0) return BFIR_ERR_STATE;   // an empty entry
+    for (int en : bl.ent) if (en >= 0 && filled[en] == 0) return BFIR_ERR_STATE;       // an empty entry
     return BFIR_OK;
 }
 
@@ -1689,7 +1775,7 @@ static int set_coeff_bank(bfir_engine *e, bool pairs, int n, const int *outputs,
     if (!entries || (pairs && (!outputs || !inputs || n < 1))) return BFIR_ERR_ARG;
     if (!e->bank) return BFIR_ERR_STATE;
     BankList bl;
-    int rc = bank_list(e, pairs ? n : P, pairs ? outputs : nullptr, inputs, entries, bl);
+    int rc = bank_list(e, e->bank_nb, pairs ? n : P, pairs ? outputs : nullptr, inputs, entries, bl);
     if (rc == BFIR_OK && fade) rc = check_fade_args(e, fade_blocks);
     if (rc != BFIR_OK) return rc;
     if (pairs && !bfir_engine_is_initialized(e)) return BFIR_ERR_STATE;   // nothing to patch
@@ -2695,14 +2781,13 @@ static int patch_table_set(bfir_engine *l, const std::vector<int> &list)
 // list (bfir_engine_set_coeff_matrix_levels_pairs_fade): `rows` are the listed filters alone, row j the new filter list[j] =
 // o C + i, and the new set is the active one with those replaced.  Every level's H2 is its H copied and the listed rows'
 // part loaded, its table goes to its d_patch, and the launches that take both sets patch (fade_patch).
-static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double scale, int fade_blocks,
-                                const std::vector<int> *list = nullptr)
+static int set_coeff_split_fade(bfir_engine *e, const SplitSource &src, int fade_blocks, const std::vector<int> *list = nullptr)
 {
-    int rc = check_split_lengths(e, rows);
+    int rc = source_check_lengths(e, src);
     if (rc == BFIR_OK) rc = check_fade_args(e, fade_blocks);
     if (rc != BFIR_OK) return rc;
-    for (int n = 0; n < rows.n_required; n++) if (!rows.taps[n]) return BFIR_ERR_ARG;
-    const LevelSplit spl = split_rows(e, rows);
+    for (int n = 0; src.rows && n < src.rows->n_required; n++) if (!src.rows->taps[n]) return BFIR_ERR_ARG;
+    const LevelSplit spl = source_split(e, src);
     const LevelSplit sp = list ? merged_counts(e, spl, *list) : spl;
     for (int i = 0; i < e->n_tail; i++) {
         // a level the old set does not reach runs no forward transforms: it has no delay line to fade on (per level, not
@@ -2714,7 +2799,7 @@ static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double s
         }
     }
     // a NaN / Inf tap at any level is refused before anything is uploaded at any level: the engine keeps running the old set
-    rc = check_rows(e, rows, SIZE_MAX, scale);
+    rc = source_check_rows(e, src);
     if (rc != BFIR_OK) return rc;
     // the catch-up's launches (up to a tail's chunk) must fit the matrix MAC's grid: refused before anything changes
     for (int i = 0; i < e->n_tail; i++)
@@ -2727,23 +2812,31 @@ static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double s
     // queued work may still read what was H before the last fade's swap, and the catch-up below reads the delay lines: the
     // device is idle from here to the end of the call
     HIP_TRY(hipDeviceSynchronize());
-    const size_t n_rows = list ? (size_t)e->Co * e->C : rows.taps.size();
+    const size_t n_rows = list ? (size_t)e->Co * e->C : src.rows ? src.rows->taps.size() : src.ent->size();
     rc = fade_prepare(e, (int)n_rows);
     if (rc != BFIR_OK) return rc;
+    void *gather[BFIR_MAX_LEVELS] = {};   // bank entries: the levels of the one gather behind the loop; a skipped level is not among them
     for (int k = 0; k <= e->n_tail; k++) {
         bfir_engine *l = level(e, k);
         const LevelSplit::Level &s = sp.lv[k];
         if (k > 0 && !e->lv_active[k - 1]) continue;
         l->nblk2 = s.nb;
-        if (list) {
+        if (list && src.ent) {
+            // every level's copy is queued on the stream of the gather, which is so ordered behind all of them
+            HIP_TRY(hipMemcpyAsync(l->H2, l->H, n_rows * l->B * cbuf_bytes(l), hipMemcpyDeviceToDevice, e->stream));
+            gather[k] = l->H2;
+            rc = patch_table_set(l, *list);
+            if (rc != BFIR_OK) return rc;
+        } else if (list) {
             // the level's store copied on the stream its rows are loaded on, and complete before the first row is written
             HIP_TRY(hipMemcpyAsync(l->H2, l->H, n_rows * l->B * cbuf_bytes(l), hipMemcpyDeviceToDevice, l->stream));
             HIP_TRY(hipStreamSynchronize(l->stream));
-            rc = load_level_pairs(l, l->H2, spl.lv[k], *list, scale);
+            rc = load_level_pairs(l, l->H2, spl.lv[k], *list, src.scale);
             if (rc == BFIR_OK) rc = patch_table_set(l, *list);
             if (rc != BFIR_OK) return rc;
         } else if (s.nb_max > 0) {
-            rc = load_filters(l, l->H2, 0, s.rows, s.nb_max, scale);
+            if (src.ent) gather[k] = l->H2;
+            else rc = load_filters(l, l->H2, 0, s.rows, s.nb_max, src.scale);
             if (rc != BFIR_OK) return rc;
         } else {
             // The new set does not reach the level.  A matrix engine: every count 0, its products with the new set are stored
@@ -2755,6 +2848,7 @@ static int set_coeff_split_fade(bfir_engine *e, const FilterRows &rows, double s
         if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk2, l->nblk2.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
         else if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk2, l->nblk2.data(), sizeof(int) * l->nblk2.size(), hipMemcpyHostToDevice));
     }
+    if (src.ent) { rc = lbank_gather(e, gather, *src.ent, list); if (rc != BFIR_OK) return rc; }
     if (e->matrix) {
         // Front end: a level pairs channels only while every input is read under BOTH sets (an input is read if any filter of
         // its column has taps on any level); after the fade the new set decides (fade_swap_sets, lfade_finish).  The head of an
@@ -2797,7 +2891,8 @@ extern "C" int bfir_engine_set_coeff_nup_fade(bfir_engine *e, const void *const 
     if (!e) return BFIR_ERR_ARG;
     if (!e->nup || e->levels || e->mlevels) return BFIR_ERR_UNSUPPORTED;
     if (!coeffs || n_coeffs < 0) return BFIR_ERR_ARG;
-    return set_coeff_split_fade(e, diagonal_rows(e, coeffs, n_coeffs, length), scale, fade_blocks);
+    const FilterRows rows = diagonal_rows(e, coeffs, n_coeffs, length);
+    return set_coeff_split_fade(e, taps_source(rows, scale), fade_blocks);
 }
 
 extern "C" int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length, double scale,
@@ -2806,7 +2901,8 @@ extern "C" int bfir_engine_set_coeff_levels_fade(bfir_engine *e, const void *con
     if (!e) return BFIR_ERR_ARG;
     if (!e->levels) return BFIR_ERR_UNSUPPORTED;
     if (!coeffs || n_coeffs < 0) return BFIR_ERR_ARG;
-    return set_coeff_split_fade(e, diagonal_rows(e, coeffs, n_coeffs, length), scale, fade_blocks);
+    const FilterRows rows = diagonal_rows(e, coeffs, n_coeffs, length);
+    return set_coeff_split_fade(e, taps_source(rows, scale), fade_blocks);
 }
 
 // every filter of its own length, partition counts per filter and level, and the front-end rule of
@@ -2817,7 +2913,8 @@ extern "C" int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const vo
     if (!e) return BFIR_ERR_ARG;
     if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
     if (!coeffs || !lengths) return BFIR_ERR_ARG;
-    return set_coeff_split_fade(e, matrix_rows(e, coeffs, lengths, 0), scale, fade_blocks);
+    const FilterRows rows = matrix_rows(e, coeffs, lengths, 0);
+    return set_coeff_split_fade(e, taps_source(rows, scale), fade_blocks);
 }
 
 // ---------------------------------------------------------------------------
@@ -2843,22 +2940,18 @@ static int pairs_list_levels(const bfir_engine *e, int n_pairs, const int *outpu
     return check_split_lengths(e, pl.rows);
 }
 
-extern "C" int bfir_engine_set_coeff_matrix_levels_pairs(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
-                                                         const void *const *coeffs, const int *lengths, double scale)
+// The listed rows (row j of the source is filter list[j] = o C + i, the list checked) of the active set replaced on every level
+static int set_pairs_split(bfir_engine *e, const SplitSource &src, const std::vector<int> &list)
 {
-    if (!e) return BFIR_ERR_ARG;
-    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
-    PairList pl;
-    int rc = pairs_list_levels(e, n_pairs, outputs, inputs, coeffs, lengths, pl);
-    if (rc != BFIR_OK) return rc;
     // nothing to patch; or a fade: a tail past its last old block already runs the new set, there is no ONE active set
     if (!bfir_engine_is_initialized(e) || e->fade_len > 0) return BFIR_ERR_STATE;
-    rc = check_rows(e, pl.rows, SIZE_MAX, scale);               // a NaN / Inf tap: the engine keeps its filters and stays initialised
+    int rc = source_check_rows(e, src);                         // a NaN / Inf tap: the engine keeps its filters and stays initialised
     if (rc != BFIR_OK) return rc;
-    const LevelSplit spl = split_rows(e, pl.rows);
-    const LevelSplit sp = merged_counts(e, spl, pl.row);
+    const LevelSplit spl = source_split(e, src);
+    const LevelSplit sp = merged_counts(e, spl, list);
     HIP_TRY(hipSetDevice(e->device));
     HIP_TRY(hipDeviceSynchronize());
+    void *gather[BFIR_MAX_LEVELS] = {};
     for (int k = 0; k <= e->n_tail; k++) {
         bfir_engine *l = level(e, k);
         int nb_old = 0;
@@ -2866,12 +2959,25 @@ extern "C" int bfir_engine_set_coeff_matrix_levels_pairs(bfir_engine *e, int n_p
         // a level the active set does not reach was not loaded by the set call (set_coeff_split): its store reads as zeros
         // before the first listed row goes in, as load_filters leaves the rows of the whole matrix
         if (nb_old == 0 && sp.lv[k].nb_max > 0) HIP_TRY(hipMemset(l->H, 0, l->nblk.size() * l->B * cbuf_bytes(l)));
-        rc = load_level_pairs(l, l->H, spl.lv[k], pl.row, scale);
+        if (src.ent) gather[k] = l->H;                          // a listed entry that does not reach the level: its row cleared, as below
+        else rc = load_level_pairs(l, l->H, spl.lv[k], list, src.scale);
         if (rc != BFIR_OK) return rc;
         l->nblk = sp.lv[k].nb;
         if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->nblk.size(), hipMemcpyHostToDevice));
     }
+    if (src.ent) { rc = lbank_gather(e, gather, *src.ent, &list); if (rc != BFIR_OK) return rc; }
     return split_counts_set(e, sp);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_pairs(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                         const void *const *coeffs, const int *lengths, double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    PairList pl;
+    const int rc = pairs_list_levels(e, n_pairs, outputs, inputs, coeffs, lengths, pl);
+    if (rc != BFIR_OK) return rc;
+    return set_pairs_split(e, taps_source(pl.rows, scale), pl.row);
 }
 
 extern "C" int bfir_engine_set_coeff_matrix_levels_pairs_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
@@ -2883,7 +2989,168 @@ extern "C" int bfir_engine_set_coeff_matrix_levels_pairs_fade(bfir_engine *e, in
     PairList pl;
     const int rc = pairs_list_levels(e, n_pairs, outputs, inputs, coeffs, lengths, pl);
     if (rc != BFIR_OK) return rc;
-    return set_coeff_split_fade(e, pl.rows, scale, fade_blocks, &pl.row);
+    return set_coeff_split_fade(e, taps_source(pl.rows, scale), fade_blocks, &pl.row);
+}
+
+// ---------------------------------------------------------------------------
+// coefficient banks of a multi-level matrix or mimo engine: one store per level in the form of that level's H, loaded through
+// the level split (bfir_engine_levels_bank_create, _load), and the four set calls with bank entries in place of host taps
+// (bfir_engine_set_coeff_matrix_levels_bank, _bank_fade, _pairs_bank, _pairs_bank_fade): set_coeff_split, set_coeff_split_fade
+// and set_pairs_split with a SplitSource of entries, ONE k_lbank_gather launch (lbank.hip) for all levels where the calls
+// with taps upload and transform level by level
+// ---------------------------------------------------------------------------
+extern "C" int bfir_engine_levels_bank_create(bfir_engine *e, int n_entries)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (n_entries < 1) return BFIR_ERR_ARG;
+    if (e->bank) return BFIR_ERR_STATE;
+    HIP_TRY(hipSetDevice(e->device));
+    for (int k = 0; k <= e->n_tail; k++) {
+        bfir_engine *l = level(e, k);
+        if (hipMalloc(&l->bank, (size_t)n_entries * l->B * cbuf_bytes(l)) == hipSuccess) continue;
+        (void)hipGetLastError();
+        l->bank = nullptr;
+        for (int j = 0; j < k; j++) { (void)hipFree(level(e, j)->bank); level(e, j)->bank = nullptr; }   // no bank is left
+        return BFIR_ERR_HIP;
+    }
+    e->lbank_len.assign((size_t)n_entries, 0);                 // every entry empty; the stores themselves are not cleared
+    e->lbank_nb.assign((size_t)n_entries * BFIR_MAX_LEVELS, 0);
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_levels_bank_destroy(bfir_engine *e)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!e->bank) return BFIR_OK;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());
+    for (int k = 0; k <= e->n_tail; k++) { (void)hipFree(level(e, k)->bank); level(e, k)->bank = nullptr; }
+    e->lbank_len.clear(); e->lbank_nb.clear();
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_levels_bank_entries(const bfir_engine *e)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    return (int)e->lbank_len.size();
+}
+
+extern "C" int bfir_engine_levels_bank_length(const bfir_engine *e, int entry)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (entry < 0 || (size_t)entry >= e->lbank_len.size()) return BFIR_ERR_ARG;
+    return e->lbank_len[entry];
+}
+
+extern "C" int bfir_engine_levels_bank_blocks(const bfir_engine *e, int entry, int level)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (entry < 0 || (size_t)entry >= e->lbank_len.size() || level < 0 || level > e->n_tail) return BFIR_ERR_ARG;
+    return e->lbank_nb[(size_t)entry * BFIR_MAX_LEVELS + level];
+}
+
+extern "C" int bfir_engine_levels_bank_load(bfir_engine *e, int first, int n, const void *const *coeffs, const int *lengths,
+                                            double scale)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!coeffs || !lengths || n < 1 || first < 0) return BFIR_ERR_ARG;
+    FilterRows rows((size_t)n);
+    for (int k = 0; k < n; k++) { rows.taps[k] = coeffs[k]; rows.len[k] = coeffs[k] ? lengths[k] : 0; }
+    int rc = check_split_lengths(e, rows);
+    if (rc != BFIR_OK) return rc;
+    if (!e->bank) return BFIR_ERR_STATE;
+    if ((size_t)first + (size_t)n > e->lbank_len.size()) return BFIR_ERR_ARG;
+    // a NaN / Inf tap anywhere is refused before anything is uploaded: the bank is unchanged
+    rc = check_rows(e, rows, SIZE_MAX, scale);
+    if (rc != BFIR_OK) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipDeviceSynchronize());                            // the stores are written on an idle device
+    for (int k = 0; k < n; k++) {                               // a failed load leaves them empty
+        e->lbank_len[first + k] = 0;
+        for (int lv = 0; lv < BFIR_MAX_LEVELS; lv++) e->lbank_nb[(size_t)(first + k) * BFIR_MAX_LEVELS + lv] = 0;
+    }
+    // the split of set_coeff_split, and per level its one load: an entry is on every level the row that
+    // bfir_engine_set_coeff_matrix_levels writes for the same taps, length and scale
+    const LevelSplit sp = split_rows(e, rows);
+    for (int lv = 0; lv <= e->n_tail; lv++) {
+        bfir_engine *l = level(e, lv);
+        if (sp.lv[lv].nb_max == 0) continue;                    // none of the n filters reaches the level: nothing transformed, counts 0
+        rc = load_filters(l, l->bank, first, sp.lv[lv].rows, sp.lv[lv].nb_max, scale);
+        if (rc != BFIR_OK) return rc;
+    }
+    for (int k = 0; k < n; k++) {
+        e->lbank_len[first + k] = rows.len[k];
+        for (int lv = 0; lv <= e->n_tail; lv++) e->lbank_nb[(size_t)(first + k) * BFIR_MAX_LEVELS + lv] = sp.lv[lv].nb[k];
+    }
+    return BFIR_OK;
+}
+
+extern "C" int bfir_engine_levels_bank_read(bfir_engine *e, int entry, int level, int block, void *dst)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!dst || level < 0 || level > e->n_tail) return BFIR_ERR_ARG;
+    bfir_engine *l = level ? e->tail[level - 1] : e;
+    if (block < 0 || block >= l->B) return BFIR_ERR_ARG;
+    if (!e->bank) return BFIR_ERR_STATE;
+    if (entry < 0 || (size_t)entry >= e->lbank_len.size()) return BFIR_ERR_ARG;
+    if (block >= e->lbank_nb[(size_t)entry * BFIR_MAX_LEVELS + level]) {   // what a gather writes there: zeros at and past the count
+        memset(dst, 0, cbuf_bytes(l));
+        return BFIR_OK;
+    }
+    return read_store_spectrum(l, l->bank, entry, block, dst);
+}
+
+// The four calls.  pairs: a list (outputs, inputs, entries of n), else the whole matrix (entries[o C + i]); fade_blocks of a
+// fade.  The refusals of the list and of the bank come first, then those of the call with taps in its own order.
+static int set_coeff_lbank(bfir_engine *e, bool pairs, int n, const int *outputs, const int *inputs, const int *entries, bool fade,
+                           int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!entries || (pairs && (!outputs || !inputs || n < 1))) return BFIR_ERR_ARG;
+    if (!e->bank) return BFIR_ERR_STATE;
+    BankList bl;
+    const int rc = bank_list(e, e->lbank_len, pairs ? n : e->Co * e->C, pairs ? outputs : nullptr, inputs, entries, bl);
+    if (rc != BFIR_OK) return rc;
+    // the gather's own limits (alignment, a partition of whole 16 bytes, rows, grid), before anything is touched or launched
+    void *stores[BFIR_MAX_LEVELS] = {};
+    for (int k = 0; k <= e->n_tail; k++) stores[k] = level(e, k)->H;
+    LBankArgs ga = lbank_args(e, stores);
+    ga.n_rows = (int)bl.row.size();
+    if (!lbank_gather_supported(ga)) return BFIR_ERR_UNSUPPORTED;
+    SplitSource src;
+    src.ent = &bl.ent;
+    if (fade) return set_coeff_split_fade(e, src, fade_blocks, pairs ? &bl.row : nullptr);
+    return pairs ? set_pairs_split(e, src, bl.row) : set_coeff_split(e, src);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_bank(bfir_engine *e, const int *entries)
+{
+    return set_coeff_lbank(e, false, 0, nullptr, nullptr, entries, false, 0);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_bank_fade(bfir_engine *e, const int *entries, int fade_blocks)
+{
+    return set_coeff_lbank(e, false, 0, nullptr, nullptr, entries, true, fade_blocks);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_pairs_bank(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                              const int *entries)
+{
+    return set_coeff_lbank(e, true, n_pairs, outputs, inputs, entries, false, 0);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_pairs_bank_fade(bfir_engine *e, int n_pairs, const int *outputs,
+                                                                   const int *inputs, const int *entries, int fade_blocks)
+{
+    return set_coeff_lbank(e, true, n_pairs, outputs, inputs, entries, true, fade_blocks);
 }
 
 extern "C" int bfir_engine_fade_remaining_levels(const bfir_engine *e)

@@ -281,6 +281,23 @@ constexpr int BFIR_BANK_STEPS = 4;                          // steps per workgro
 bool bank_gather_supported(const BankArgs &a);              // alignment, and the grid of the launch fits
 int launch_bank_gather(const BankArgs &a, hipStream_t s);   // 0, or -1 if !bank_gather_supported(a) (nothing launched)
 
+// lbank.hip: k_lbank_gather, the same for ALL levels of a multi-level matrix or mimo engine in one launch
+// (bfir_engine_levels_bank_create: one store per level).  Row tab[W j] of every participating level's dst gets the first
+// tab[W j + 2 + k] partitions of that level's bank entry tab[W j + 1] and zeros behind them, W = 2 + BFIR_LBANK_LEVELS.
+constexpr int BFIR_LBANK_LEVELS = 4;                        // BFIR_MAX_LEVELS of the public header (engine.hip asserts it)
+struct LBankLevel {
+    const void *bank; void *dst;                              // 16-byte aligned; dst null: the level is not part of the launch
+    unsigned long long row_bytes, part_bytes;                 // blocks[k] N_k realsize and N_k realsize, multiples of 16
+};
+struct LBankArgs {
+    LBankLevel lv[BFIR_LBANK_LEVELS];
+    unsigned end[BFIR_LBANK_LEVELS];                          // workgroups of a row up to and with level k (launch_lbank_gather sets them)
+    const int *tab;                                           // device [n_rows][2 + BFIR_LBANK_LEVELS]: row, entry or -1, partitions per level
+    int n_rows;
+};
+bool lbank_gather_supported(const LBankArgs &a);            // alignment, and the grid of the launch fits
+int launch_lbank_gather(LBankArgs a, hipStream_t s);        // 0, or -1 if !lbank_gather_supported(a) (nothing launched)
+
 // a11 + a12: inverse real FFT of Y[gc][t] (grouped layout, times in_scale),
 // first L samples to dst + gc*dst_ch_stride + t*L.
 struct InvArgs {

@@ -364,8 +364,9 @@ class BrutefirMatrix(Brutefir):
 
     # A coefficient bank: filters transformed once and kept on the device, then named by index.  The calls below are
     # set_coeff / set_coeff_fade / set_coeff_pairs / set_coeff_pairs_fade with a bank index (or None = no path) in place
-    # of every filter; they take no taps and copy rows on the device in one kernel launch.  The multi-level classes have no
-    # banks: there the library answers every one of these with ERR_UNSUPPORTED.
+    # of every filter; they take no taps and copy rows on the device in one kernel launch.  On the multi-level classes the
+    # library answers every one of these with ERR_UNSUPPORTED: their banks, one store per level, are the lbank_* methods and
+    # set_bank / fade_to_rows_bank / set_pairs_bank / fade_to_pairs_bank of BrutefirMatrixLevels.
 
     def bank_create(self, n):
         """bfir_engine_bank_create: a bank of n empty entries on the engine's device.  Returns 0 or an ERR_* code
@@ -704,6 +705,76 @@ class BrutefirMatrixLevels(BrutefirMatrix):
         fade_to_rows fades to the merged set; the fading blocks agree with that fade within rounding, not bitwise."""
         args, _keep = self._level_pair_args(pairs, filters)
         return self._lib.bfir_engine_set_coeff_matrix_levels_pairs_fade(self._h, *args, float(scale), int(fade_blocks))
+
+    # The bank of a multi-level engine: one store per level, every filter transformed once through the level split and then
+    # named by index.  set_bank / fade_to_rows_bank / set_pairs_bank / fade_to_pairs_bank are set_coeff / fade_to_rows /
+    # set_pairs / fade_to_pairs with a bank index (or None = no path) in place of every filter; they take no taps and copy
+    # the rows of all levels on the device in one kernel launch.
+
+    def lbank_create(self, n):
+        """bfir_engine_levels_bank_create: a bank of n empty entries, a store on every level.  Returns 0 or an ERR_* code
+        (ERR_STATE: the engine has one)."""
+        return self._lib.bfir_engine_levels_bank_create(self._h, int(n))
+
+    def lbank_destroy(self):
+        """bfir_engine_levels_bank_destroy: frees the bank; the engine's active filters are copies and stay."""
+        return self._lib.bfir_engine_levels_bank_destroy(self._h)
+
+    def lbank_entries(self):
+        """bfir_engine_levels_bank_entries: the entry count, 0 without a bank (< 0: an ERR_* code)."""
+        return self._lib.bfir_engine_levels_bank_entries(self._h)
+
+    def lbank_length(self, entry):
+        """bfir_engine_levels_bank_length: the taps entry `entry` was loaded with, 0 = empty (< 0: an ERR_* code)."""
+        return self._lib.bfir_engine_levels_bank_length(self._h, int(entry))
+
+    def lbank_blocks(self, entry, level):
+        """bfir_engine_levels_bank_blocks: the entry's partition count on `level` (< 0: an ERR_* code)."""
+        return self._lib.bfir_engine_levels_bank_blocks(self._h, int(entry), int(level))
+
+    def lbank_load(self, first, filters, scale=1.0):
+        """bfir_engine_levels_bank_load: filters[k] (taps in working precision, each of its own length up to max_taps as
+        set_coeff takes them, or None = the entry becomes empty) into entry first + k, split between the levels, one upload
+        and one transform launch per level.  Returns 0 or an ERR_* code (ERR_COEFF: a NaN / Inf tap, the bank is unchanged)."""
+        rd = _real_dtype(self.s)
+        arrs = [None if h is None else np.ascontiguousarray(h, dtype=rd) for h in filters]
+        ptrs = (C.c_void_p * max(1, len(arrs)))(*[None if a is None else a.ctypes.data for a in arrs])
+        lens = (C.c_int * max(1, len(arrs)))(*[0 if a is None else a.size for a in arrs])
+        return self._lib.bfir_engine_levels_bank_load(self._h, int(first), len(arrs), ptrs, lens, float(scale))
+
+    def lbank_read(self, entry, level, block):
+        """bfir_engine_levels_bank_read: partition spectrum `block` of a bank entry on `level`, as coeff_block gives the
+        engine's; zeros at and past the entry's partition count there."""
+        n = 2 * self.lengths[level] if 0 <= level < len(self.lengths) else 2 * self.L
+        dst = np.zeros(n, dtype=_real_dtype(self.s))
+        rc = self._lib.bfir_engine_levels_bank_read(self._h, int(entry), int(level), int(block), dst.ctypes.data)
+        if rc != 0:
+            raise BfirError(rc, "bfir_engine_levels_bank_read")
+        return dst
+
+    def set_bank(self, rows):
+        """bfir_engine_set_coeff_matrix_levels_bank: rows[o][i] is the bank entry of h_{o,i}, or None = no path.  The engine
+        is left as set_coeff with the entries' taps leaves it.  Returns 0 or an ERR_* code (ERR_STATE: no bank, or an empty
+        entry)."""
+        assert len(rows) == self.n_out and all(len(r) == self.n_in for r in rows)
+        return self._lib.bfir_engine_set_coeff_matrix_levels_bank(self._h, self._bank_ints([en for r in rows for en in r]))
+
+    def fade_to_rows_bank(self, rows, fade_blocks):
+        """bfir_engine_set_coeff_matrix_levels_bank_fade: fade_to_rows to the set rows names."""
+        assert len(rows) == self.n_out and all(len(r) == self.n_in for r in rows)
+        return self._lib.bfir_engine_set_coeff_matrix_levels_bank_fade(
+            self._h, self._bank_ints([en for r in rows for en in r]), int(fade_blocks))
+
+    def set_pairs_bank(self, pairs, entries):
+        """bfir_engine_set_coeff_matrix_levels_pairs_bank: bank entry entries[k] (or None = the path is removed) replaces
+        h_{o,i} for pairs[k] = (o, i) on every level; every other pair keeps its filter.  Returns 0 or an ERR_* code
+        (ERR_STATE while a fade is pending or running)."""
+        return self._lib.bfir_engine_set_coeff_matrix_levels_pairs_bank(self._h, *self._pair_bank_args(pairs, entries))
+
+    def fade_to_pairs_bank(self, pairs, entries, fade_blocks):
+        """bfir_engine_set_coeff_matrix_levels_pairs_bank_fade: the same change, crossfaded as fade_to_pairs."""
+        return self._lib.bfir_engine_set_coeff_matrix_levels_pairs_bank_fade(self._h, *self._pair_bank_args(pairs, entries),
+                                                                             int(fade_blocks))
 
     def fade_remaining(self):
         """Head blocks of a pending or running fade_to_rows / fade_to_pairs still to be processed; 0 = none."""

@@ -281,6 +281,40 @@ public:
         return bfir_engine_set_coeff_matrix_levels_pairs_fade(m_e, n_pairs, outputs, inputs, (const void *const *)coeffs, lengths,
                                                               scale, fade_blocks);
     }
+    // A multi-level matrix or mimo engine's coefficient bank, one store per level: filters split between the levels and
+    // transformed once (bfir_engine_levels_bank_create, _destroy, _entries, _length, _blocks, _load, _read), then named by
+    // index.  coeffs[k] of levels_bank_load: the lengths[k] taps of entry first + k, or null (the entry becomes empty).
+    int levels_bank_create(int n_entries) { return m_e ? bfir_engine_levels_bank_create(m_e, n_entries) : -1; }
+    int levels_bank_destroy() { return m_e ? bfir_engine_levels_bank_destroy(m_e) : -1; }
+    int levels_bank_entries() { return m_e ? bfir_engine_levels_bank_entries(m_e) : -1; }
+    int levels_bank_length(int entry) { return m_e ? bfir_engine_levels_bank_length(m_e, entry) : -1; }
+    int levels_bank_blocks(int entry, int level) { return m_e ? bfir_engine_levels_bank_blocks(m_e, entry, level) : -1; }
+    int levels_bank_load(int first, int n, void **coeffs, const int *lengths, double scale)
+    {
+        if (!m_e) return -1;
+        return bfir_engine_levels_bank_load(m_e, first, n, (const void *const *)coeffs, lengths, scale);
+    }
+    int levels_bank_read(int entry, int level, int block, void *dst)
+    {
+        return m_e ? bfir_engine_levels_bank_read(m_e, entry, level, block, dst) : -1;
+    }
+    // The four coefficient changes of such an engine with bank entries in place of taps: entries[o * n_inputs + i] (the whole
+    // matrix) or entries[k] for the pair (outputs[k], inputs[k]) is a bank index, or -1 = no path
+    // (bfir_engine_set_coeff_matrix_levels_bank, _bank_fade, _pairs_bank, _pairs_bank_fade).
+    int set_coeff_matrix_levels_bank(const int *entries) { return m_e ? bfir_engine_set_coeff_matrix_levels_bank(m_e, entries) : -1; }
+    int set_coeff_matrix_levels_bank_fade(const int *entries, int fade_blocks)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_levels_bank_fade(m_e, entries, fade_blocks) : -1;
+    }
+    int set_coeff_matrix_levels_pairs_bank(int n_pairs, const int *outputs, const int *inputs, const int *entries)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_levels_pairs_bank(m_e, n_pairs, outputs, inputs, entries) : -1;
+    }
+    int set_coeff_matrix_levels_pairs_bank_fade(int n_pairs, const int *outputs, const int *inputs, const int *entries,
+                                                int fade_blocks)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_levels_pairs_bank_fade(m_e, n_pairs, outputs, inputs, entries, fade_blocks) : -1;
+    }
     // head blocks of such a fade still to be processed; 0 = none
     int fade_remaining_levels() { return m_e ? bfir_engine_fade_remaining_levels(m_e) : -1; }
 

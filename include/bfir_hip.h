@@ -390,8 +390,8 @@ int bfir_engine_set_coeff_matrix_pairs_fade(bfir_engine *e, int n_pairs, const i
  * rows in ONE kernel launch (k_bank_gather), and take no host taps.  Every entry keeps the partition count it was loaded
  * with, so the filters of one call may have different counts (which the calls with taps, with one coeff_blocks per call,
  * cannot give).  The engine's sets are COPIES: loading over an entry, or destroying the bank, changes nothing in the engine.
- * Multi-level kinds (bfir_engine_create_matrix_levels, _mimo_levels) have no banks: each of their levels would need a store
- * of its own.  Every call of this group returns BFIR_ERR_UNSUPPORTED on an engine of any kind but the two above, and
+ * Multi-level kinds (bfir_engine_create_matrix_levels, _mimo_levels) have no banks of this group: theirs, one store per
+ * level, are the bfir_engine_levels_bank_* calls further below.  Every call of this group returns BFIR_ERR_UNSUPPORTED on an engine of any kind but the two above, and
  * BFIR_ERR_ARG for a null e.
  *
  * bfir_engine_bank_create allocates the store; every entry is empty (partition count 0) and the store is not cleared.
@@ -561,6 +561,76 @@ int bfir_engine_set_coeff_matrix_levels_pairs(bfir_engine *e, int n_pairs, const
 int bfir_engine_set_coeff_matrix_levels_pairs_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
                                                    const void *const *coeffs, const int *lengths, double scale,
                                                    int fade_blocks);
+
+/* Coefficient banks of the multi-level matrix kinds (bfir_engine_create_matrix_levels, bfir_engine_create_mimo_levels; both
+ * precisions): the banks of bfir_engine_bank_create for engines whose filters are split between levels.  The bank is one
+ * store per level on the engine's device: level k holds [n_entries][blocks[k]][2 L_k] spectra in that level's precision and
+ * spectrum layout, an entry being a row of that level's filter store that lives elsewhere.  The bank takes n_entries * 2 *
+ * realsize * D_(n_levels) bytes (D_(n_levels) = the sum of blocks[k] L_k, the taps the engine holds per filter).  The four
+ * bfir_engine_set_coeff_matrix_levels_*bank* calls are bfir_engine_set_coeff_matrix_levels, _levels_fade, _levels_pairs and
+ * _levels_pairs_fade with a bank index in place of every filter: where those upload and transform level by level and row by
+ * row, these copy rows on the device, all listed rows of ALL levels in ONE kernel launch (k_lbank_gather), and take no host
+ * taps.  The engine's sets are COPIES: loading over an entry, or destroying the bank, changes nothing in the engine.  Every
+ * call of this group returns BFIR_ERR_UNSUPPORTED on an engine of any kind but the two above (the ten bfir_engine_bank_* /
+ * _set_coeff_matrix_*bank* calls above keep refusing these two), and BFIR_ERR_ARG for a null e.
+ *
+ * bfir_engine_levels_bank_create allocates the stores of all levels; every entry is empty (length 0) and the stores are not
+ * cleared.  BFIR_ERR_ARG: n_entries < 1.  BFIR_ERR_STATE: the engine has a bank.  BFIR_ERR_HIP: an allocation failed; what
+ * was allocated is freed and there is then no bank.
+ * bfir_engine_levels_bank_destroy waits for queued work and frees the bank (no bank: BFIR_OK, nothing happens);
+ * bfir_engine_destroy does the same.  The engine's active filters and a running fade are untouched.
+ * bfir_engine_levels_bank_entries: the entry count, 0 without a bank.  bfir_engine_levels_bank_length: the taps an entry was
+ * loaded with, 0 = empty.  bfir_engine_levels_bank_blocks: its partition count on `level` (0 .. n_levels - 1), 0 = the entry
+ * does not reach that level.  Both: BFIR_ERR_ARG for an entry outside the bank (any entry, without one) or a level outside the
+ * engine. */
+int bfir_engine_levels_bank_create(bfir_engine *e, int n_entries);
+int bfir_engine_levels_bank_destroy(bfir_engine *e);
+int bfir_engine_levels_bank_entries(const bfir_engine *e);
+int bfir_engine_levels_bank_length(const bfir_engine *e, int entry);
+int bfir_engine_levels_bank_blocks(const bfir_engine *e, int entry, int level);
+/* Entries first .. first + n - 1 written: coeffs[k] is lengths[k] taps in working precision, 0 .. D_(n_levels) as
+ * bfir_engine_set_coeff_matrix_levels takes them; NULL or 0 taps = the entry becomes empty.  The n filters are split at every
+ * D_k as that call splits them and every level they reach gets ONE upload and ONE transform launch for all n, after queued
+ * work has finished; a level none of them reaches is not transformed into.  An entry holds, on every level, byte for byte the
+ * partitions bfir_engine_set_coeff_matrix_levels gives a filter of the same taps, length and scale, and the host keeps its
+ * length and its partition count on every level.  Calls may differ in scale.
+ * BFIR_ERR_ARG: a null coeffs or lengths, n < 1, first < 0, a length outside 0 .. D_(n_levels), first + n past the bank.
+ * BFIR_ERR_STATE: no bank (checked before the range).  BFIR_ERR_COEFF: a NaN/Inf tap in any filter, found before anything is
+ * uploaded -- the bank is unchanged. */
+int bfir_engine_levels_bank_load(bfir_engine *e, int first, int n, const void *const *coeffs, const int *lengths, double scale);
+/* Partition spectrum `block` of an entry on `level` (2 L_level reals) in the form bfir_engine_read_coeff_matrix_levels gives.
+ * A block at or past the entry's partition count on that level reads as zeros: what a set call writes there.
+ * BFIR_ERR_ARG: a null dst, a level outside the engine, block outside 0 .. blocks[level] - 1, an entry outside the bank.
+ * BFIR_ERR_STATE: no bank (checked before the entry). */
+int bfir_engine_levels_bank_read(bfir_engine *e, int entry, int level, int block, void *dst);
+/* bfir_engine_set_coeff_matrix_levels, _levels_fade, _levels_pairs and _levels_pairs_fade with bank entries: entries[o *
+ * n_inputs + i] (the whole matrix) or entries[k] for the pair (outputs[k], inputs[k]) is a bank index, or -1 = no path (in a
+ * pairs call the path is removed).  A row written from an entry holds, on level k, the entry's first count_k partitions and
+ * zeros up to blocks[k], and its partition count there is count_k: the row, the counts and so every output byte are those of
+ * the call with taps for the same taps, length and scale.  One entry may be named for any number of pairs.  Everything else
+ * is the contract of the call with taps: the plain whole-matrix call cuts a fade; the plain pairs call returns
+ * BFIR_ERR_STATE while a fade is pending or running; the fades refuse, per level, a new set that reaches a level the active
+ * set does not; a newly reached level starts and a left one stops; the pairs fade keeps the merged-set semantics and the
+ * patched y_new; bfir_engine_fade_remaining_levels and bfir_engine_reset behave as with taps.
+ * All refusals come before the device is touched and change nothing, in this order.  BFIR_ERR_UNSUPPORTED: the engine's
+ * kind.  BFIR_ERR_ARG: a null entries, outputs or inputs; n_pairs < 1.  BFIR_ERR_STATE: no bank.  BFIR_ERR_ARG: a pair outside
+ * the matrix; the same pair listed twice; an index outside -1 .. n_entries - 1.  BFIR_ERR_STATE: a named entry is empty.
+ * BFIR_ERR_UNSUPPORTED: a gather the kernel cannot make (a misaligned store, a partition that is not whole 16 bytes, more
+ * than 65535 rows, a grid past the launch limits) -- never a skipped launch.  For the fade calls BFIR_ERR_ARG: fade_blocks < 1
+ * or K L > 2^24, then BFIR_ERR_STATE: an engine without coefficients, a fade pending or running; for _pairs_bank
+ * BFIR_ERR_STATE likewise.  For the fade calls then BFIR_ERR_UNSUPPORTED: the new set reaches a level the active one does
+ * not, or a launch of the fade on an active level that does not fit its kernel's grid.
+ * The calls wait for queued work, upload ONE table of the listed rows (row, entry, the count on every level) and the counts,
+ * launch the gather once on the engine's stream for all levels and wait for it once; a pairs fade queues every active
+ * level's copy of its store in front of the gather, and a level the fade with taps skips is skipped by the gather too.  They
+ * transform nothing and allocate nothing but the table when it grows (and, as every fade, the second set at the engine's
+ * first fade). */
+int bfir_engine_set_coeff_matrix_levels_bank(bfir_engine *e, const int *entries);
+int bfir_engine_set_coeff_matrix_levels_bank_fade(bfir_engine *e, const int *entries, int fade_blocks);
+int bfir_engine_set_coeff_matrix_levels_pairs_bank(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                   const int *entries);
+int bfir_engine_set_coeff_matrix_levels_pairs_bank_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                        const int *entries, int fade_blocks);
 /* Head blocks of a pending or running fade (fftw_convolver.cpp:275-321 over fade_blocks blocks) of an engine from
  * bfir_engine_create_nup, _levels or _matrix_levels still to be processed; 0 = none.  BFIR_ERR_UNSUPPORTED on every other kind
  * of engine. */
