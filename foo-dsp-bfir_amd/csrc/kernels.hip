@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "fft_lds.h"
+#include "pair_io.h"
 
 namespace bfir {
 
@@ -1607,71 +1608,166 @@ template <int D> static void launch_mac_lds_d(const MacArgs &a, hipStream_t s)
 
 // ACC (partition batches after the first, B > PB): the sums continue from the partial results the
 // previous batch left in Y; those are fetched D blocks ahead like the spectra (yq, ty_next).
-__device__ __forceinline__ float2 mac_ld_x(const float2 *p)
+//
+// Addressing (MacIo).  A wave walks three sequences, each one spectrum down per step: the delay-line slots it loads
+// (wrapping at slot 0), the outputs it stores, and -- ACC -- the partial sums it reads back D outputs ahead.  MacIo<true>
+// reaches all three through buffer descriptors: the lane keeps ONE constant 32-bit byte offset (8 k), the position in
+// the sequence is a scalar byte offset that takes a subtract per step (the delay line's: and an unsigned minimum with
+// the top slot, for the wrap), so no step holds a 64-bit multiply, a vector address add, a compare of lanes or an
+// exec-mask branch.
+// What must not be written or read is left to the buffer range check instead:
+//   * an output t >= n_t (the last range of a launch is rounded up to whole groups): the descriptor of Y ends with
+//     the launch's n_t spectra, and on gfx950 the range check takes lane offset + scalar offset + access size against
+//     that (measured, profiles/mac_stream_addr.txt: a scalar offset at or beyond the size drops the store, as does a
+//     sum that crosses it), so the store is dropped;
+//   * a filter partition p >= nblk (the batch is rounded up to PB): the descriptor of H ends with nblk spectra, and the
+//     load returns the zeros the code used to substitute, without a compare and a branch per partition;
+//   * a read-back (ACC) at t < 0 or t >= n_t: "below zero" the scalar offset has wrapped to just under 4 GiB, where
+//     nothing is measured; the descriptor of such a load has ZERO bytes instead (a scalar compare and select on its
+//     third word, the zero-byte descriptors of pair.hip) and the load returns the zeros the sums start from;
+//   * the lane of bin 0 (DC | Nyquist belongs to the first workgroups) carries a lane offset of 2 GiB, beyond every
+//     buffer this form is launched for and low enough that no scalar offset carries it past 32 bits (k_mac_sys does
+//     the same for its stores): it loads zeros and stores nothing, and one register serves loads and stores.
+// launch_mac_stream checks that the byte offsets fit (a ring, and n_t + PB spectra, within 2 GiB per channel);
+// an engine beyond that runs MacIo<false>, the 64-bit pointer arithmetic and the tests this kernel had before.
+__device__ __forceinline__ float2 mac_ld_x(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff)   // buf_load2, nontemporal
 {
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    const f2v v = __builtin_nontemporal_load((const f2v *)p);
-    float2 r; r.x = v.x; r.y = v.y; return r;
+    const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, 2);
+    float2 f; f.x = __uint_as_float(v.x); f.y = __uint_as_float(v.y);
+    return f;
 }
-__device__ __forceinline__ void mac_st_y(float2 *p, float2 v)
+__device__ __forceinline__ void mac_st_y(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff, float2 f)   // buf_store2, nontemporal
 {
-    typedef float f2v __attribute__((ext_vector_type(2)));
-    f2v w; w.x = v.x; w.y = v.y;
-    __builtin_nontemporal_store(w, (f2v *)p);
+    u32x2 v; v.x = __float_as_uint(f.x); v.y = __float_as_uint(f.y);
+    __builtin_amdgcn_raw_buffer_store_b64(v, r, voff, soff, 2);
 }
 
-// `a` is not read, but without it hipcc emits different code for k_mac_stream (it loads nblk through the scalar cache)
-template <int PB, int D, int MODE, bool ACC>
-__device__ __forceinline__ void mac_stream_group(float (&ar)[PB], float (&ai)[PB], const float (&hr)[PB],
+template <bool BUF> struct MacIo;
+template <> struct MacIo<true> {
+    __amdgpu_buffer_rsrc_t rx, ry, rh;  // the channel's delay line, ring spectra; its product spectra, n_t; its filter, nblk
+    const float *yb;                    // (ACC) the product spectra again, for the descriptor of a read-back
+    unsigned kv;                        // lane: byte offset of bin k in a spectrum; 2 GiB (nowhere) in the lane of bin 0
+    unsigned step, xtop, ybytes;        // bytes per spectrum, in ring - 1 spectra, in n_t spectra
+    unsigned sx, sy, sn;                // scalar: byte offset of the next slot to load, output to store, output to read back
+    __device__ __forceinline__ MacIo(const MacArgs &a, int gc, unsigned k, int slot, int ty)
+    {
+        step = (unsigned)a.N * 4u; xtop = (unsigned)(a.ring - 1) * step; ybytes = (unsigned)a.n_t * step;
+        rx = make_rsrc((const float *)a.x + (long)gc * a.x_ch_stride, (unsigned)a.ring * step);
+        yb = (const float *)a.y + (long)gc * a.y_ch_stride;
+        ry = make_rsrc(yb, ybytes);
+        rh = make_rsrc((const float *)a.h + (long)gc * a.h_ch_stride, (unsigned)a.nblk[gc] * step);
+        kv = k != 0 ? k * 8u : 0x80000000u;
+        sx = (unsigned)slot * step; sy = sn = (unsigned)ty * step;
+    }
+    __device__ __forceinline__ float2 ld_h(int p) const  // partitions from nblk on are beyond the descriptor: zeros
+    {
+        return buf_load2(rh, kv, (unsigned)p * step);
+    }
+    __device__ __forceinline__ float2 ld_x()             // nontemporal, 8 bytes per lane; then one slot back in time
+    {
+        const float2 v = mac_ld_x(rx, kv, sx);
+        sx = min(sx - step, xtop);                       // below slot 0 the difference wraps to just under 4 GiB: the top slot
+        return v;
+    }
+    __device__ __forceinline__ void st_y(float2 v)       // nontemporal; then one output down
+    {
+        mac_st_y(ry, kv, sy, v);
+        sy -= step;
+        asm volatile("" : "+s"(sy));                     // ONE running offset: no table of 32 offsets per group to set up
+    }
+    __device__ __forceinline__ float2 ld_y()
+    {
+        const float2 v = buf_load2(make_rsrc(yb, sn < ybytes ? ybytes : 0u), kv, sn);
+        sn -= step;
+        return v;
+    }
+};
+template <> struct MacIo<false> {
+    const float2 *__restrict__ Xc, *__restrict__ Hc; float2 *__restrict__ Yc;
+    unsigned k; int N2, ring, n_t, nb, sq, ty, tn;
+    __device__ __forceinline__ MacIo(const MacArgs &a, int gc, unsigned k_, int slot, int ty_)
+    {
+        Xc = (const float2 *)((const float *)a.x + (long)gc * a.x_ch_stride);
+        Hc = (const float2 *)((const float *)a.h + (long)gc * a.h_ch_stride);
+        Yc = (float2 *)((float *)a.y + (long)gc * a.y_ch_stride);
+        k = k_; N2 = a.N / 2; ring = a.ring; n_t = a.n_t; nb = a.nblk[gc]; sq = slot; ty = tn = ty_;
+    }
+    __device__ __forceinline__ float2 ld_h(int p) const
+    {
+        float2 h; h.x = 0.f; h.y = 0.f;
+        if (p < nb) h = (Hc + (long)p * N2)[k];
+        return h;
+    }
+    __device__ __forceinline__ float2 ld_x()
+    {
+        typedef float f2v __attribute__((ext_vector_type(2)));
+        const f2v v = __builtin_nontemporal_load((const f2v *)(Xc + (long)sq * N2 + k));
+        sq -= 1; if (sq < 0) sq += ring;
+        float2 r; r.x = v.x; r.y = v.y; return r;
+    }
+    __device__ __forceinline__ void st_y(float2 v)
+    {
+        typedef float f2v __attribute__((ext_vector_type(2)));
+        f2v w; w.x = v.x; w.y = v.y;
+        if (ty < n_t && k != 0) __builtin_nontemporal_store(w, (f2v *)(Yc + (long)ty * N2 + k));
+        ty -= 1;
+    }
+    __device__ __forceinline__ float2 ld_y()
+    {
+        float2 v; v.x = 0.f; v.y = 0.f;
+        if (tn >= 0 && tn < n_t) v = (Yc + (long)tn * N2)[k];
+        tn -= 1;
+        return v;
+    }
+};
+
+// A running sum is a (re, im) REGISTER PAIR from its first FMA on (mac_sum_t; the pin names the pair): its store takes
+// the pair as it stands.  As two floats that only meet at the store, every sum was moved into a free aligned pair on
+// the way, and the pairs in flight were what the 168 registers of <32, 8> did not hold (20 bytes of scratch).
+typedef float mac_sum_t __attribute__((ext_vector_type(2)));
+
+template <int PB, int D, int MODE, bool ACC, bool BUF>
+__device__ __forceinline__ void mac_stream_group(mac_sum_t (&acc)[PB], const float (&hr)[PB],
                                                  const float (&hi)[PB], float2 (&q)[D], float2 (&yq)[ACC ? D : 1],
-                                                 const float2 *__restrict__ Xc, float2 *__restrict__ Yc, unsigned k,
-                                                 int N2, int ring, int &sq, int &ty_next, int tg, int n_t,
-                                                 bool store_lane, const MacArgs &a)
+                                                 MacIo<BUF> &io)
 {
     static_assert(PB % D == 0, "queue depth must divide the group");
     constexpr int NU = MODE == 2 ? PB - 1 : PB;          // the block PB before the range feeds nothing
     static_for<0, NU>([&](auto U) {                      // spectrum of block t = tg + PB-1-u
         constexpr int u = decltype(U)::value;
         const float xr = q[u % D].x, xi = q[u % D].y;
-        q[u % D] = mac_ld_x(Xc + (long)sq * N2 + k);     // uniform base + 32-bit lane offset, 8 bytes per lane
-        sq -= 1; if (sq < 0) sq += ring;
+        q[u % D] = io.ld_x();
         const float nxi = -xi;
         constexpr int plo = MODE == 2 ? u + 1 : 0, phi = MODE == 0 ? u : PB - 1;
         float y0r = 0.f, y0i = 0.f;                      // what the sums of y[t] start from
         if constexpr (ACC && plo == 0) {
             y0r = yq[u % D].x; y0i = yq[u % D].y;
-            float2 v; v.x = 0.f; v.y = 0.f;
-            if (ty_next >= 0 && ty_next < n_t) v = (Yc + (long)ty_next * N2)[k];
-            yq[u % D] = v;
-            ty_next -= 1;
+            yq[u % D] = io.ld_y();
         }
         static_for<plo, phi + 1>([&](auto P) {
             constexpr int p = decltype(P)::value;
             constexpr int sl = (PB - 1 - u + p) % PB;    // accumulator of y[t + p]
             if constexpr (p == 0) {
-                ar[sl] = fmaf(xr, hr[0], y0r); ar[sl] = fmaf(nxi, hi[0], ar[sl]);
-                ai[sl] = fmaf(xr, hi[0], y0i); ai[sl] = fmaf(xi, hr[0], ai[sl]);
+                acc[sl].x = fmaf(xr, hr[0], y0r); acc[sl].x = fmaf(nxi, hi[0], acc[sl].x);
+                acc[sl].y = fmaf(xr, hi[0], y0i); acc[sl].y = fmaf(xi, hr[0], acc[sl].y);
             } else {
-                ar[sl] = fmaf(xr, hr[p], ar[sl]); ar[sl] = fmaf(nxi, hi[p], ar[sl]);
-                ai[sl] = fmaf(xr, hi[p], ai[sl]); ai[sl] = fmaf(xi, hr[p], ai[sl]);
+                acc[sl].x = fmaf(xr, hr[p], acc[sl].x); acc[sl].x = fmaf(nxi, hi[p], acc[sl].x);
+                acc[sl].y = fmaf(xr, hi[p], acc[sl].y); acc[sl].y = fmaf(xi, hr[p], acc[sl].y);
             }
-            // pin the sums here: otherwise the compiler sinks every chain down to its (conditional)
+            // pin the sums here: otherwise the compiler sinks every chain down to its
             // store, which keeps a whole group of spectra live and serialises each chain
-            asm volatile("" : "+v"(ar[sl]), "+v"(ai[sl]));
+            asm volatile("" : "+v"(acc[sl]));
         });
-        if constexpr (phi == PB - 1) {                   // y[t + PB-1] is complete
+        if constexpr (phi == PB - 1) {                   // y[t + PB-1] is complete: output tg + 2 PB-2-u, one down per store
             constexpr int sl = (2 * PB - 2 - u) % PB;
-            const int ty = tg + 2 * PB - 2 - u;
-            if (ty < n_t && store_lane) {
-                float2 v; v.x = ar[sl]; v.y = ai[sl];
-                mac_st_y(Yc + (long)ty * N2 + k, v);
-            }
+            float2 v; v.x = acc[sl].x; v.y = acc[sl].y;
+            io.st_y(v);
         }
     });
 }
 
-template <int PB, int D, bool ACC>
-__global__ __launch_bounds__(256, ACC ? 2 : 3) void k_mac_stream(MacArgs a, int ncol, int nR, int ngrp, int n_dc, int p0)
+template <int PB, int D, bool ACC, bool BUF>
+__device__ __forceinline__ void mac_stream_body(const MacArgs &a, int ncol, int nR, int ngrp, int n_dc, int p0)
 {
     const int N = a.N, ring = a.ring;
     if ((int)blockIdx.x < n_dc) {
@@ -1716,11 +1812,6 @@ __global__ __launch_bounds__(256, ACC ? 2 : 3) void k_mac_stream(MacArgs a, int 
     const int s = w / nR, r = w - s * nR;
     const int gc = s / ncol, col = s - gc * ncol;
     const unsigned k = col * 256 + threadIdx.x;          // bin: (re, im) pair k of every spectrum
-    const int N2 = N / 2;
-    const float2 *__restrict__ Xc = (const float2 *)((const float *)a.x + (long)gc * a.x_ch_stride);
-    const float2 *__restrict__ Hc = (const float2 *)((const float *)a.h + (long)gc * a.h_ch_stride);
-    float2 *__restrict__ Yc = (float2 *)((float *)a.y + (long)gc * a.y_ch_stride);
-    const int nb = a.nblk[gc];
     // this range: blocks ta .. ta+R-1; the last range of a launch only runs the groups it has blocks for
     const int ta = r * ngrp * PB;
     const int my_grp = min(ngrp, (a.n_t - ta + PB - 1) / PB);
@@ -1728,45 +1819,40 @@ __global__ __launch_bounds__(256, ACC ? 2 : 3) void k_mac_stream(MacArgs a, int 
 
     float2 q[D];
     // newest block of the range first; batch p0 pairs output t with spectrum t - p0 - p
-    int sq = ((a.base_slot + ta + R - 1 - p0) % ring + ring) % ring;
+    int slot = (a.base_slot + ta + R - 1 - p0) % ring; if (slot < 0) slot += ring;
+    MacIo<BUF> io(a, gc, k, slot, ta + R - 1);
 #pragma unroll
-    for (int d = 0; d < D; d++) {
-        q[d] = mac_ld_x(Xc + (long)sq * N2 + k);
-        sq -= 1; if (sq < 0) sq += ring;
-    }
+    for (int d = 0; d < D; d++) q[d] = io.ld_x();
     float hr[PB], hi[PB];
 #pragma unroll
-    for (int p = 0; p < PB; p++) {
-        if (p0 + p < nb) { const float2 h = (Hc + (long)(p0 + p) * N2)[k]; hr[p] = h.x; hi[p] = h.y; }
-        else { hr[p] = 0.f; hi[p] = 0.f; }
-    }
+    for (int p = 0; p < PB; p++) { const float2 h = io.ld_h(p0 + p); hr[p] = h.x; hi[p] = h.y; }
     float2 yq[ACC ? D : 1];
-    int ty_next = ta + R - 1;
     if constexpr (ACC) {
 #pragma unroll
-        for (int d = 0; d < D; d++) {
-            float2 v; v.x = 0.f; v.y = 0.f;
-            if (ty_next >= 0 && ty_next < a.n_t) v = (Yc + (long)ty_next * N2)[k];
-            yq[d] = v;
-            ty_next -= 1;
-        }
+        for (int d = 0; d < D; d++) yq[d] = io.ld_y();
     }
-    float ar[PB], ai[PB];
+    mac_sum_t acc[PB];
 #pragma unroll
-    for (int p = 0; p < PB; p++) { ar[p] = 0.f; ai[p] = 0.f; }
-    const bool store_lane = k != 0;
-    int tg = ta + R - PB;
-    mac_stream_group<PB, D, 0, ACC>(ar, ai, hr, hi, q, yq, Xc, Yc, k, N2, ring, sq, ty_next, tg, a.n_t, store_lane, a);
-    for (int g = my_grp - 2; g >= 0; g--) {
-        tg -= PB;
-        mac_stream_group<PB, D, 1, ACC>(ar, ai, hr, hi, q, yq, Xc, Yc, k, N2, ring, sq, ty_next, tg, a.n_t, store_lane, a);
-    }
-    tg -= PB;
-    mac_stream_group<PB, D, 2, ACC>(ar, ai, hr, hi, q, yq, Xc, Yc, k, N2, ring, sq, ty_next, tg, a.n_t, store_lane, a);
+    for (int p = 0; p < PB; p++) { acc[p].x = 0.f; acc[p].y = 0.f; }
+    mac_stream_group<PB, D, 0, ACC, BUF>(acc, hr, hi, q, yq, io);           // group tg = ta + R - PB
+    for (int g = my_grp - 2; g >= 0; g--) mac_stream_group<PB, D, 1, ACC, BUF>(acc, hr, hi, q, yq, io);
+    mac_stream_group<PB, D, 2, ACC, BUF>(acc, hr, hi, q, yq, io);           // the PB - 1 blocks before the range
+}
+
+// the two entry points of the one body: descriptor addressing, and pointers for engines beyond its 32-bit offsets
+template <int PB, int D, bool ACC>
+__global__ __launch_bounds__(256, ACC ? 2 : 3) void k_mac_stream(MacArgs a, int ncol, int nR, int ngrp, int n_dc, int p0)
+{
+    mac_stream_body<PB, D, ACC, true>(a, ncol, nR, ngrp, n_dc, p0);
+}
+template <int PB, int D, bool ACC>
+__global__ __launch_bounds__(256, ACC ? 2 : 3) void k_mac_stream_far(MacArgs a, int ncol, int nR, int ngrp, int n_dc, int p0)
+{
+    mac_stream_body<PB, D, ACC, false>(a, ncol, nR, ngrp, n_dc, p0);
 }
 
 // ngrp: groups of PB blocks per wave (BFIR_MAC_RANGE overrides, in blocks)
-template <int PB, int D> static void launch_mac_stream(const MacArgs &a, hipStream_t s)
+template <int PB, int D, bool BUF> static void launch_mac_stream_as(const MacArgs &a, hipStream_t s)
 {
     // read per launch (a getenv is nanoseconds next to a launch) so tests can switch it in-process
     const char *re_ = getenv("BFIR_MAC_RANGE");
@@ -1783,13 +1869,26 @@ template <int PB, int D> static void launch_mac_stream(const MacArgs &a, hipStre
     }
     const int R = ngrp * PB, nR = (a.n_t + R - 1) / R;
     const int n_dc = a.n_ch * ((a.n_t + 255) / 256);
-    hipLaunchKernelGGL((k_mac_stream<PB, D, false>), dim3(n_dc + nR * ncol * a.n_ch), dim3(256), 0, s, a, ncol, nR, ngrp,
-                       n_dc, 0);
+    auto first = k_mac_stream<PB, D, false>, more = k_mac_stream<PB, D, true>;
+    if constexpr (!BUF) { first = k_mac_stream_far<PB, D, false>; more = k_mac_stream_far<PB, D, true>; }
+    hipLaunchKernelGGL(first, dim3(n_dc + nR * ncol * a.n_ch), dim3(256), 0, s, a, ncol, nR, ngrp, n_dc, 0);
     // more partitions than fit the registers: further batches of PB continue the sums left in Y
     // (same stream, so batch b sees batch b-1's stores; DC/Nyquist were finished by the first launch)
     for (int p0 = PB; p0 < a.B; p0 += PB)
-        hipLaunchKernelGGL((k_mac_stream<PB, D, true>), dim3(nR * ncol * a.n_ch), dim3(256), 0, s, a, ncol, nR, ngrp, 0,
-                           p0);
+        hipLaunchKernelGGL(more, dim3(nR * ncol * a.n_ch), dim3(256), 0, s, a, ncol, nR, ngrp, 0, p0);
+}
+
+// Descriptor addressing (MacIo<true>) wherever its 32-bit byte offsets hold: one channel's delay line, and the product
+// spectra of a launch rounded up to whole groups, each within the 2 GiB below the "nowhere" offset of bin 0's lane (the
+// headline: 269 MB and 134 MB).  An engine beyond that keeps the pointer arithmetic, in the batch of 32 alone
+// (partitions past nblk are zeros there too: the same sums).
+template <int PB, int D> static void launch_mac_stream(const MacArgs &a, hipStream_t s)
+{
+    const unsigned long long spec = (unsigned long long)a.N * 4u;
+    if (spec * (unsigned)a.ring <= (1ull << 31) && spec * ((unsigned)a.n_t + PB) <= (1ull << 31) &&
+        spec * ((unsigned)a.B + PB) <= (1ull << 31))   // ... and the filter's partitions, rounded up to whole batches
+        launch_mac_stream_as<PB, D, true>(a, s);
+    else launch_mac_stream_as<32, 8, false>(a, s);
 }
 
 template <int D> static void launch_mac_lds(const MacArgs &a, hipStream_t s)
