@@ -86,6 +86,10 @@ SIGNATURES = {
     "bfir_engine_set_coeff_matrix_bank_fade": (_ci, [_vp, _pi, _ci]),
     "bfir_engine_set_coeff_matrix_pairs_bank": (_ci, [_vp, _ci, _pi, _pi, _pi]),
     "bfir_engine_set_coeff_matrix_pairs_bank_fade": (_ci, [_vp, _ci, _pi, _pi, _pi, _ci]),
+    "bfir_engine_set_coeff_matrix_bank_mix": (_ci, [_vp, _ci, _pi, C.POINTER(_cd)]),
+    "bfir_engine_set_coeff_matrix_bank_mix_fade": (_ci, [_vp, _ci, _pi, C.POINTER(_cd), _ci]),
+    "bfir_engine_set_coeff_matrix_pairs_bank_mix": (_ci, [_vp, _ci, _pi, _pi, _ci, _pi, C.POINTER(_cd)]),
+    "bfir_engine_set_coeff_matrix_pairs_bank_mix_fade": (_ci, [_vp, _ci, _pi, _pi, _ci, _pi, C.POINTER(_cd), _ci]),
     "bfir_engine_levels_bank_create": (_ci, [_vp, _ci]),
     "bfir_engine_levels_bank_destroy": (_ci, [_vp]),
     "bfir_engine_levels_bank_entries": (_ci, [_vp]),

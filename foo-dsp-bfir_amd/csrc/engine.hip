@@ -192,7 +192,8 @@ struct bfir_engine {
     // the table of the listed rows; the engine's sets are copies and never point into the bank.
     void *bank = nullptr;
     std::vector<int> bank_nb;
-    int *d_gather = nullptr; size_t gather_ints = 0;   // [rows][3]: destination row, entry or -1, partitions (BankArgs)
+    int *d_gather = nullptr; size_t gather_ints = 0;   // [rows][3]: destination row, entry or -1, partitions (BankArgs);
+                                                       // a mix call: [rows][BFIR_BANK_MIX_REC], k_bank_mix's records (BankMixArgs)
     // The bank of a multi-level matrix or mimo engine (bfir_engine_levels_bank_create): one such store per level, in `bank` of
     // the head and of every tail, [entries][blocks[k]][2 L_k], loaded through the level split (bfir_engine_levels_bank_load).
     // The head keeps every entry's tap count (0: empty) and its partitions on every level, [entry][BFIR_MAX_LEVELS]; its
@@ -1620,7 +1621,8 @@ extern "C" int bfir_engine_set_coeff_matrix_pairs_fade(bfir_engine *e, int n_pai
 // coefficient banks of a uniform matrix or mimo engine: filters transformed once into a store of the engine's own row form
 // (bfir_engine_bank_create, _bank_load), and the four set calls with bank entries in place of host taps
 // (bfir_engine_set_coeff_matrix_bank, _bank_fade, _pairs_bank, _pairs_bank_fade): one k_bank_gather launch (bank.hip) where
-// the calls with taps upload and transform
+// the calls with taps upload and transform; and the same four with a weighted sum of up to BFIR_BANK_MIX_TERMS entries in
+// place of one (bfir_engine_set_coeff_matrix_bank_mix, ...): one k_bank_mix launch (bankmix.hip)
 // ---------------------------------------------------------------------------
 static bool bank_kind(const bfir_engine *e) { return e->matrix && !e->mlevels; }
 static int read_store_spectrum(bfir_engine *e, const void *store, int f, int block, void *dst);
@@ -1710,6 +1712,7 @@ namespace {
 struct BankList {
     std::vector<int> row;        // the rows of the store that are written: filter o C + i
     std::vector<int> ent;        // the bank entry of each, or -1: no path
+    std::vector<int> mix;        // a mix call: k_bank_mix's records, [rows][BFIR_BANK_MIX_REC] (ent is not used)
 };
 }
 
@@ -1736,16 +1739,72 @@ static int bank_list(const bfir_engine *e, const std::vector<int> &filled, int n
     return BFIR_OK;
 }
 
+// The same for the four mix calls: listed row k has the n_terms terms (entries[k n_terms + j], weights[k n_terms + j]).  Every
+// weight is converted once to the working precision; a term is live iff its entry is >= 0 and the converted weight is not
+// zero.  bl.mix gets k_bank_mix's records: the live terms compacted to the front in listed order, each with its entry's count,
+// and the row's count, the largest of them (no live term: 0, no path).  Every index and count the kernel uses is checked here.
+static int bank_mix_list(const bfir_engine *e, int n, const int *outputs, const int *inputs, int n_terms, const int *entries,
+                         const double *weights, BankList &bl)
+{
+    const int n_ent = (int)e->bank_nb.size(), W = BFIR_BANK_MIX_REC;
+    std::vector<char> listed(outputs ? (size_t)e->Co * e->C : 0, 0);
+    bl.row.resize((size_t)n);
+    bl.mix.assign((size_t)n * W, 0);
+    for (int k = 0; k < n; k++) {
+        int r = k;
+        if (outputs) {
+            if (outputs[k] < 0 || outputs[k] >= e->Co || inputs[k] < 0 || inputs[k] >= e->C) return BFIR_ERR_ARG;
+            r = outputs[k] * e->C + inputs[k];
+            if (listed[r]) return BFIR_ERR_ARG;                 // the same pair twice
+            listed[r] = 1;
+        }
+        int *rec = &bl.mix[(size_t)k * W];
+        bl.row[k] = rec[0] = r;
+        for (int j = 0; j < n_terms; j++) {
+            const int en = entries[(size_t)k * n_terms + j];
+            const double w = weights[(size_t)k * n_terms + j];
+            if (en < -1 || en >= n_ent) return BFIR_ERR_ARG;    // live or not
+            if (!std::isfinite(w)) return BFIR_ERR_ARG;
+            unsigned long long bits;
+            bool zero;
+            if (e->s == 4) {
+                const float wf = (float)w;
+                if (!std::isfinite(wf)) return BFIR_ERR_ARG;    // infinite in the working precision
+                unsigned u; memcpy(&u, &wf, sizeof u);
+                bits = u; zero = wf == 0.0f;
+            } else {
+                memcpy(&bits, &w, sizeof bits); zero = w == 0.0;
+            }
+            if (en < 0 || zero) continue;
+            int *t = rec + 3 + 4 * rec[2]++;
+            t[0] = en; t[1] = e->bank_nb[en]; t[2] = (int)(unsigned)bits; t[3] = (int)(unsigned)(bits >> 32);
+            rec[1] = std::max(rec[1], t[1]);
+        }
+    }
+    for (int k = 0; k < n; k++) {
+        const int *rec = &bl.mix[(size_t)k * W];
+        for (int j = 0; j < rec[2]; j++) if (rec[4 + 4 * j] == 0) return BFIR_ERR_STATE;   // a live term names an empty entry
+    }
+    return BFIR_OK;
+}
+
 // The listed rows of Hdst (H, or H2) from the bank and their partition counts into cnt (nblk, or nblk2): the table goes up,
-// ONE gather is queued on the stream that owns every write to the store, and the host waits for it.  The device is idle.
+// ONE gather (k_bank_gather, or a mix call's k_bank_mix) is queued on the stream that owns every write to the store, and the
+// host waits for it.  The device is idle.
 static int bank_gather(bfir_engine *e, void *Hdst, std::vector<int> &cnt, const BankList &bl)
 {
+    const bool mix = !bl.mix.empty();
     std::vector<int> tab;
-    tab.reserve(3 * bl.row.size());
-    for (size_t k = 0; k < bl.row.size(); k++) {
-        const int nb = bl.ent[k] < 0 ? 0 : e->bank_nb[bl.ent[k]];
-        tab.push_back(bl.row[k]); tab.push_back(bl.ent[k]); tab.push_back(nb);
-        cnt[bl.row[k]] = nb;
+    if (mix) {
+        tab = bl.mix;
+        for (size_t k = 0; k < bl.row.size(); k++) cnt[bl.row[k]] = tab[k * BFIR_BANK_MIX_REC + 1];
+    } else {
+        tab.reserve(3 * bl.row.size());
+        for (size_t k = 0; k < bl.row.size(); k++) {
+            const int nb = bl.ent[k] < 0 ? 0 : e->bank_nb[bl.ent[k]];
+            tab.push_back(bl.row[k]); tab.push_back(bl.ent[k]); tab.push_back(nb);
+            cnt[bl.row[k]] = nb;
+        }
     }
     if (tab.size() > e->gather_ints) {
         if (e->d_gather) (void)hipFree(e->d_gather);
@@ -1754,10 +1813,17 @@ static int bank_gather(bfir_engine *e, void *Hdst, std::vector<int> &cnt, const 
         e->gather_ints = tab.size();
     }
     HIP_TRY(hipMemcpy(e->d_gather, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-    BankArgs a;
-    a.bank = e->bank; a.dst = Hdst; a.tab = e->d_gather; a.n_rows = (int)bl.row.size();
-    a.part_bytes = cbuf_bytes(e); a.row_bytes = (unsigned long long)e->B * a.part_bytes;
-    if (launch_bank_gather(a, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;
+    if (mix) {
+        BankMixArgs a;
+        a.bank = e->bank; a.dst = Hdst; a.tab = e->d_gather; a.n_rows = (int)bl.row.size();
+        a.part_bytes = cbuf_bytes(e); a.row_bytes = (unsigned long long)e->B * a.part_bytes;
+        if (launch_bank_mix(a, e->s, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;
+    } else {
+        BankArgs a;
+        a.bank = e->bank; a.dst = Hdst; a.tab = e->d_gather; a.n_rows = (int)bl.row.size();
+        a.part_bytes = cbuf_bytes(e); a.row_bytes = (unsigned long long)e->B * a.part_bytes;
+        if (launch_bank_gather(a, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;
+    }
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipGetLastError());
     return BFIR_OK;
@@ -1765,17 +1831,21 @@ static int bank_gather(bfir_engine *e, void *Hdst, std::vector<int> &cnt, const 
 
 // The four calls.  pairs: a list (outputs, inputs, entries of n), else the whole matrix (entries[o C + i]); fade_blocks < 0:
 // the plain call.  The order of the refusals is that of the calls with taps, with the bank's own behind the arguments.
+// mix: the four mix calls, n_terms (entry, weight) terms per listed row in place of one entry; only the list and the kernel
+// of the gather differ, the fade, the patch table and the swap are the same code.
 static int set_coeff_bank(bfir_engine *e, bool pairs, int n, const int *outputs, const int *inputs, const int *entries,
-                          bool fade, int fade_blocks)
+                          bool fade, int fade_blocks, bool mix = false, int n_terms = 0, const double *weights = nullptr)
 {
     if (!e) return BFIR_ERR_ARG;
     if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
     if (fade && (e->n_eng > 1 || e->d_dither_tab)) return BFIR_ERR_UNSUPPORTED;   // as every fade
     const int P = e->Co * e->C;
     if (!entries || (pairs && (!outputs || !inputs || n < 1))) return BFIR_ERR_ARG;
+    if (mix && (!weights || n_terms < 1 || n_terms > BFIR_BANK_MIX_TERMS)) return BFIR_ERR_ARG;
     if (!e->bank) return BFIR_ERR_STATE;
     BankList bl;
-    int rc = bank_list(e, e->bank_nb, pairs ? n : P, pairs ? outputs : nullptr, inputs, entries, bl);
+    int rc = mix ? bank_mix_list(e, pairs ? n : P, pairs ? outputs : nullptr, inputs, n_terms, entries, weights, bl)
+                 : bank_list(e, e->bank_nb, pairs ? n : P, pairs ? outputs : nullptr, inputs, entries, bl);
     if (rc == BFIR_OK && fade) rc = check_fade_args(e, fade_blocks);
     if (rc != BFIR_OK) return rc;
     if (pairs && !bfir_engine_is_initialized(e)) return BFIR_ERR_STATE;   // nothing to patch
@@ -1852,6 +1922,30 @@ extern "C" int bfir_engine_set_coeff_matrix_pairs_bank_fade(bfir_engine *e, int 
                                                             const int *entries, int fade_blocks)
 {
     return set_coeff_bank(e, true, n_pairs, outputs, inputs, entries, true, fade_blocks);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_bank_mix(bfir_engine *e, int n_terms, const int *entries, const double *weights)
+{
+    return set_coeff_bank(e, false, 0, nullptr, nullptr, entries, false, 0, true, n_terms, weights);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_bank_mix_fade(bfir_engine *e, int n_terms, const int *entries, const double *weights,
+                                                          int fade_blocks)
+{
+    return set_coeff_bank(e, false, 0, nullptr, nullptr, entries, true, fade_blocks, true, n_terms, weights);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_pairs_bank_mix(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                           int n_terms, const int *entries, const double *weights)
+{
+    return set_coeff_bank(e, true, n_pairs, outputs, inputs, entries, false, 0, true, n_terms, weights);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_pairs_bank_mix_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                                int n_terms, const int *entries, const double *weights,
+                                                                int fade_blocks)
+{
+    return set_coeff_bank(e, true, n_pairs, outputs, inputs, entries, true, fade_blocks, true, n_terms, weights);
 }
 
 extern "C" int bfir_engine_fade_remaining(const bfir_engine *e)

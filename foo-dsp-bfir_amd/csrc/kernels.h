@@ -281,6 +281,27 @@ constexpr int BFIR_BANK_STEPS = 4;                          // steps per workgro
 bool bank_gather_supported(const BankArgs &a);              // alignment, and the grid of the launch fits
 int launch_bank_gather(const BankArgs &a, hipStream_t s);   // 0, or -1 if !bank_gather_supported(a) (nothing launched)
 
+// bankmix.hip: k_bank_mix<R>, the gather that multiplies and adds while it copies (bfir_engine_set_coeff_matrix_bank_mix,
+// _bank_mix_fade, _pairs_bank_mix, _pairs_bank_mix_fade).  Row rec[0] of dst gets, in its first rec[1] partitions, the sum of
+// rec[2] <= BFIR_BANK_MIX_TERMS bank entries, each times a weight in R, every product and every add rounded on its own and
+// the first product starting the sum; a term takes part in the partitions below its own count alone; zeros behind rec[1].
+// The host lists live terms only (entry >= 0, weight != 0, count >= 1), in the caller's order; rec[1] is their largest count.
+#ifndef BFIR_BANK_MIX_TERMS
+#define BFIR_BANK_MIX_TERMS 4                               // the terms of a mix; the public header's constant of this name
+#endif
+static_assert(BFIR_BANK_MIX_TERMS == 4, "k_bank_mix's records and its register budget are laid out for four terms");
+constexpr int BFIR_BANK_MIX_REC = 3 + 4 * BFIR_BANK_MIX_TERMS;   // words of a record: row, count, live terms, then per term
+                                                            // entry, count, the weight's bits in R (low word, high word; float: high 0)
+struct BankMixArgs {
+    const void *bank; void *dst;                              // 16-byte aligned
+    const int *tab;                                           // device [n_rows][BFIR_BANK_MIX_REC]
+    int n_rows;
+    unsigned long long row_bytes, part_bytes;                 // B N realsize and N realsize, multiples of 16
+};
+constexpr int BFIR_BANK_MIX_STEPS = 2;                      // steps of BFIR_BANK_SPAN bytes per workgroup
+bool bank_mix_supported(const BankMixArgs &a);              // alignment, and the grid of the launch fits
+int launch_bank_mix(const BankMixArgs &a, int realsize, hipStream_t s);   // 0, or -1 if unsupported (nothing launched)
+
 // lbank.hip: k_lbank_gather, the same for ALL levels of a multi-level matrix or mimo engine in one launch
 // (bfir_engine_levels_bank_create: one store per level).  Row tab[W j] of every participating level's dst gets the first
 // tab[W j + 2 + k] partitions of that level's bank entry tab[W j + 1] and zeros behind them, W = 2 + BFIR_LBANK_LEVELS.

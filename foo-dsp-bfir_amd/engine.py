@@ -442,6 +442,50 @@ class BrutefirMatrix(Brutefir):
         return self._lib.bfir_engine_set_coeff_matrix_pairs_bank_fade(self._h, *self._pair_bank_args(pairs, entries),
                                                                       int(fade_blocks))
 
+    # Bank mixes: a filter as a weighted sum of up to four bank entries, formed on the device while the rows are copied
+    # (k_bank_mix).  `terms` holds, per listed row, a list of up to four (entry, weight) tuples, or None / [] = no path;
+    # shorter lists are padded with (-1, 0.0) up to the call's longest.  One term of weight 1.0 is the bank call above.
+
+    @staticmethod
+    def _mix_args(terms):
+        """(n_terms, entries, weights) of the C calls from per-row lists of (entry, weight)."""
+        rows = [list(t) if t else [] for t in terms]
+        n_terms = max([1] + [len(r) for r in rows])
+        flat = [t for r in rows for t in r + [(-1, 0.0)] * (n_terms - len(r))]
+        ents = (C.c_int * max(1, len(flat)))(*[-1 if en is None else int(en) for en, _ in flat])
+        wts = (C.c_double * max(1, len(flat)))(*[float(w) for _, w in flat])
+        return n_terms, ents, wts
+
+    def set_coeff_bank_mix(self, terms):
+        """bfir_engine_set_coeff_matrix_bank_mix: terms[o][i] is the list of (entry, weight) of h_{o,i}.  Every stored real is
+        fl(w_1 h_1), then fl(. + fl(w_m h_m)) in listed order over the live terms (entry >= 0, weight != 0 in the working
+        precision) whose entry reaches the partition; the filter's partition count is the largest among its live terms.
+        Returns 0 or an ERR_* code."""
+        assert len(terms) == self.n_out and all(len(r) == self.n_in for r in terms)
+        return self._lib.bfir_engine_set_coeff_matrix_bank_mix(self._h, *self._mix_args([t for r in terms for t in r]))
+
+    def set_coeff_bank_mix_fade(self, terms, fade_blocks):
+        """bfir_engine_set_coeff_matrix_bank_mix_fade: set_coeff_fade to the mixed set, over the next `fade_blocks` blocks."""
+        assert len(terms) == self.n_out and all(len(r) == self.n_in for r in terms)
+        return self._lib.bfir_engine_set_coeff_matrix_bank_mix_fade(self._h, *self._mix_args([t for r in terms for t in r]),
+                                                                    int(fade_blocks))
+
+    def _pair_mix_args(self, pairs, terms):
+        assert len(pairs) == len(terms)
+        outs = (C.c_int * max(1, len(pairs)))(*[int(o) for o, _ in pairs])
+        ins = (C.c_int * max(1, len(pairs)))(*[int(i) for _, i in pairs])
+        return (len(pairs), outs, ins) + self._mix_args(terms)
+
+    def set_coeff_pairs_bank_mix(self, pairs, terms):
+        """bfir_engine_set_coeff_matrix_pairs_bank_mix: the mix terms[k] (None / [] = the path is removed) replaces h_{o,i}
+        for pairs[k] = (o, i); every other pair keeps its filter.  Returns 0 or an ERR_* code."""
+        return self._lib.bfir_engine_set_coeff_matrix_pairs_bank_mix(self._h, *self._pair_mix_args(pairs, terms))
+
+    def set_coeff_pairs_bank_mix_fade(self, pairs, terms, fade_blocks):
+        """bfir_engine_set_coeff_matrix_pairs_bank_mix_fade: the same change, crossfaded over the next `fade_blocks` blocks."""
+        return self._lib.bfir_engine_set_coeff_matrix_pairs_bank_mix_fade(self._h, *self._pair_mix_args(pairs, terms),
+                                                                          int(fade_blocks))
+
     def run(self, inbuf, outbuf=None):
         """inbuf: [n_blocks*L, n_in] frames in the input format.  Returns (rc, outbuf [n_blocks*L, n_out])."""
         x = np.ascontiguousarray(inbuf, dtype=_FMT_DTYPES[self.in_format])

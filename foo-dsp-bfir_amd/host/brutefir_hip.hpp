@@ -230,6 +230,29 @@ public:
     {
         return m_e ? bfir_engine_set_coeff_matrix_pairs_bank_fade(m_e, n_pairs, outputs, inputs, entries, fade_blocks) : -1;
     }
+    // The same four with a weighted sum of up to BFIR_BANK_MIX_TERMS entries in place of one: listed row k has the terms
+    // (entries[k * n_terms + j], weights[k * n_terms + j]), j < n_terms; entry -1 or weight 0: the term takes no part
+    // (bfir_engine_set_coeff_matrix_bank_mix, _bank_mix_fade, _pairs_bank_mix, _pairs_bank_mix_fade).
+    int set_coeff_matrix_bank_mix(int n_terms, const int *entries, const double *weights)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_bank_mix(m_e, n_terms, entries, weights) : -1;
+    }
+    int set_coeff_matrix_bank_mix_fade(int n_terms, const int *entries, const double *weights, int fade_blocks)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_bank_mix_fade(m_e, n_terms, entries, weights, fade_blocks) : -1;
+    }
+    int set_coeff_matrix_pairs_bank_mix(int n_pairs, const int *outputs, const int *inputs, int n_terms, const int *entries,
+                                        const double *weights)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_pairs_bank_mix(m_e, n_pairs, outputs, inputs, n_terms, entries, weights) : -1;
+    }
+    int set_coeff_matrix_pairs_bank_mix_fade(int n_pairs, const int *outputs, const int *inputs, int n_terms, const int *entries,
+                                             const double *weights, int fade_blocks)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_pairs_bank_mix_fade(m_e, n_pairs, outputs, inputs, n_terms, entries, weights,
+                                                                      fade_blocks)
+                   : -1;
+    }
 
     // A multi-level matrix engine's filters: coeffs[o * n_inputs + i] the taps of h_{o,i} or null (no path), lengths[o *
     // n_inputs + i] its tap count, each filter split between the levels (bfir_engine_set_coeff_matrix_levels).

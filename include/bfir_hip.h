@@ -449,6 +449,53 @@ int bfir_engine_set_coeff_matrix_pairs_bank(bfir_engine *e, int n_pairs, const i
                                             const int *entries);
 int bfir_engine_set_coeff_matrix_pairs_bank_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
                                                  const int *entries, int fade_blocks);
+/* Bank mixes: the four calls above with up to BFIR_BANK_MIX_TERMS terms (entry, weight) in place of one entry, so that a
+ * filter BETWEEN measured entries (two neighbours on an arc, three on a triangle, four on a bilinear grid) or an entry AT A
+ * LEVEL (distance attenuation, a volume, a polarity flip, a mute: a "sum" of one term) is still named by index.  The
+ * transform is linear: the weighted sum of entry spectra is the spectrum of the same weighted sum of the taps, and no
+ * transform runs.  One kernel launch (k_bank_mix) writes all listed rows; the MAC, the fades and the swap are untouched, and
+ * after the call the store is a store like any other.
+ * entries[k * n_terms + j] and weights[k * n_terms + j], j < n_terms <= BFIR_BANK_MIX_TERMS, belong to listed row k: k = o *
+ * n_inputs + i in the whole-matrix calls, the pair (outputs[k], inputs[k]) in the pairs calls.  Every weight is converted
+ * once to the working precision R (float or double; 1e-60 on a float engine converts to 0 and is handled like 0).  A term
+ * is LIVE iff its entry is >= 0 and its converted weight is not zero; c_j is the partition count of a live term's entry.
+ *   The row's partition count is c = max c_j over its live terms.  Without a live term the pair has no path: count 0, a
+ *   row of zeros, the -1 of the calls above (in a pairs call the path is removed).  A mute is a removed path, nothing is
+ *   multiplied by zero.
+ *   With j_1 < j_2 < ... the live terms with c_j > p, in listed order, every stored real of partition p < c is
+ *       r = fl(w_j1 * h_j1);  r = fl(r + fl(w_jm * h_jm)), m = 2, 3, ...
+ *   every multiply and every add rounded on its own in R (no fma), the first product starting the sum (no 0 + ..., a
+ *   product of -0 stays -0).  A term whose entry is shorter than p takes no part in partition p, and what that entry's
+ *   store holds past its count is never read.  Partitions c .. filter_blocks - 1 are written as zeros.  Real and imaginary
+ *   parts, DC and Nyquist and both spectrum layouts are all stored reals: the operation is elementwise.
+ * So n_terms = 1 with weight 1 writes every byte of the call above for the same entry, and a restatement in IEEE single or
+ * double arithmetic from bfir_engine_bank_read is exact to the bit wherever no product or sum is subnormal.
+ * Everything not said here is the contract of the corresponding call above, word for word: the merged-set semantics of
+ * the pairs calls; the plain call cancels a fade and keeps the delay line; the whole-matrix plain call initialises the
+ * engine; the fades are bfir_engine_set_coeff_matrix_fade / _pairs_fade with the mixed set as the new set (the patched
+ * y_new of a pairs fade with nb_new = the row's count c); bfir_engine_fade_remaining, bfir_engine_reset and the pair-path
+ * rule behave as there.
+ * All refusals come before the device is touched and change nothing, in this order.  BFIR_ERR_ARG: a null e.
+ * BFIR_ERR_UNSUPPORTED: the engine's kind (the kinds of the calls above); for the fade calls a batch or an engine that
+ * dithers its output.  BFIR_ERR_ARG: a null entries, weights, outputs or inputs; n_pairs < 1; n_terms outside 1 ..
+ * BFIR_BANK_MIX_TERMS.  BFIR_ERR_STATE: no bank.  BFIR_ERR_ARG: a pair outside the matrix; the same pair listed twice; an
+ * index outside -1 .. n_entries - 1, live or not; a weight that is NaN or infinite, or becomes infinite in the working
+ * precision.  BFIR_ERR_STATE: a live term names an empty entry (a term of weight 0 may name one).  For the fade calls
+ * BFIR_ERR_ARG: fade_blocks < 1 or K L > 2^24, then BFIR_ERR_STATE: an engine without coefficients, a fade pending or
+ * running.  For _pairs_bank_mix BFIR_ERR_STATE: an engine without coefficients.
+ * The calls wait for queued work, upload one table, launch k_bank_mix once on the engine's stream and wait for it; they
+ * allocate nothing but that table when it grows (and, as every fade, the second set at the engine's first fade).
+ * Out of scope: mixes on the multi-level kinds (BFIR_ERR_UNSUPPORTED there); a gain change that keeps a pair's current
+ * entry without naming it; more than BFIR_BANK_MIX_TERMS terms; complex weights (phase or delay interpolation). */
+#define BFIR_BANK_MIX_TERMS 4
+int bfir_engine_set_coeff_matrix_bank_mix(bfir_engine *e, int n_terms, const int *entries, const double *weights);
+int bfir_engine_set_coeff_matrix_bank_mix_fade(bfir_engine *e, int n_terms, const int *entries, const double *weights,
+                                               int fade_blocks);
+int bfir_engine_set_coeff_matrix_pairs_bank_mix(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                int n_terms, const int *entries, const double *weights);
+int bfir_engine_set_coeff_matrix_pairs_bank_mix_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                     int n_terms, const int *entries, const double *weights,
+                                                     int fade_blocks);
 /* Blocks of a pending or running fade still to be processed; 0 = none.  < 0: error. */
 int bfir_engine_fade_remaining(const bfir_engine *e);
 
