@@ -36,6 +36,7 @@
 
 #include "../../include/bfir_hip.h"
 #include "kernels.h"
+#include "coeff_tables.h"
 
 using namespace bfir;
 
@@ -1039,6 +1040,32 @@ static int load_filters(bfir_engine *e, void *Hdst, int row0, const FilterRows &
     return BFIR_OK;
 }
 
+// A host table into the device table a kernel reads it from (d_gather, d_patch of any level), which grows where it is too
+// small.  The device is idle.
+static int upload_table(int *&d, size_t &cap, const std::vector<int> &tab)
+{
+    if (tab.size() > cap) {
+        if (d) (void)hipFree(d);
+        d = nullptr; cap = 0;
+        HIP_TRY(hipMalloc((void **)&d, sizeof(int) * tab.size()));
+        cap = tab.size();
+    }
+    HIP_TRY(hipMemcpy(d, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    return BFIR_OK;
+}
+
+// The partition counts of a level (a uniform engine: itself), new on the host in nblk or (second: a fade's new set) nblk2, to
+// where a kernel reads them: the C channels from row0 on of a diagonal engine, the whole table of a mimo engine (k_mac_mimo,
+// k_wduo); the MAC of any other matrix engine takes them by value (MatArgs.nblk).  The device is idle.
+static int upload_counts(bfir_engine *l, bool second, int row0 = 0)
+{
+    const std::vector<int> &nb = second ? l->nblk2 : l->nblk;
+    int *d = second ? l->d_nblk2 : l->d_nblk;
+    if (!l->matrix) HIP_TRY(hipMemcpy(d + row0, nb.data() + row0, sizeof(int) * l->C, hipMemcpyHostToDevice));
+    else if (l->mimo) HIP_TRY(hipMemcpy(d, nb.data(), sizeof(int) * nb.size(), hipMemcpyHostToDevice));
+    return BFIR_OK;
+}
+
 // the C channels of one engine
 extern "C" int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const void *const *coeffs,
                                         int n_coeffs, int length, int coeff_blocks, double scale)
@@ -1058,7 +1085,8 @@ extern "C" int bfir_engine_set_coeff_at(bfir_engine *e, int engine_index, const 
     if (rc == BFIR_OK) rc = load_filters(e, e->H, gc0, rows, nb, scale);
     if (rc != BFIR_OK) return rc;
     for (int n = 0; n < e->C; n++) e->nblk[gc0 + n] = nb;
-    HIP_TRY(hipMemcpy(e->d_nblk + gc0, e->nblk.data() + gc0, sizeof(int) * e->C, hipMemcpyHostToDevice));
+    rc = upload_counts(e, false, gc0);
+    if (rc != BFIR_OK) return rc;
     e->eng_init[engine_index] = 1;
     return BFIR_OK;
 }
@@ -1114,15 +1142,36 @@ static void matrix_take_path(bfir_engine *e, bool pair)
     e->pair = pair; e->direct = !pair;
 }
 
-// The partition counts of a uniform matrix engine's active set are new in e->nblk (the device is idle): k_mac_mimo's table,
-// the path, and the engine has its coefficients.
+// The partition counts of a uniform matrix engine's active set are new in e->nblk and where its MAC reads them (the device is
+// idle): the path, and the engine has its coefficients.
 static int matrix_counts_set(bfir_engine *e)
 {
-    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk, e->nblk.data(), sizeof(int) * e->nblk.size(), hipMemcpyHostToDevice));
     if (e->pair_cap) matrix_take_path(e, every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
     e->eng_init[0] = 1;
     return BFIR_OK;
 }
+
+// Where the rows of a set call on a uniform engine come from (the SplitSource of the uniform kinds): host taps, all loaded with
+// nb partitions; entries of the engine's bank (ent[j]: the entry of row j of the call, -1: none); or weighted sums of entries
+// (k_bank_mix's records, coeff_tables::mix_records).  set_coeff_uniform asks the source for its finite check, the partition
+// count of every row and to write its rows, and is otherwise the same for all three.
+namespace {
+struct UniformSource {
+    const FilterRows *rows = nullptr; double scale = 1.0; int nb = 0;
+    const std::vector<int> *ent = nullptr;
+    const std::vector<int> *mix = nullptr;
+};
+}
+
+static UniformSource uniform_taps(const bfir_engine *e, const FilterRows &rows, double scale, int coeff_blocks)
+{
+    UniformSource s;
+    s.rows = &rows; s.scale = scale; s.nb = std::min(coeff_blocks, e->B);   // run() never looks past B blocks
+    return s;
+}
+
+static int set_coeff_uniform(bfir_engine *e, const UniformSource &src, const std::vector<int> *list, int fade_blocks,
+                             bool check_first = true);
 
 // the n_out x n_in filters of a matrix engine: coeffs[o n_in + i], NULL = no path from input i to output o
 extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *coeffs, int length, int coeff_blocks,
@@ -1131,18 +1180,9 @@ extern "C" int bfir_engine_set_coeff_matrix(bfir_engine *e, const void *const *c
     if (!e) return BFIR_ERR_ARG;
     if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;   // bfir_engine_set_coeff_matrix_levels
     if (!coeffs || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    e->fade_len = e->fade_pos = 0;                              // a plain change during a fade cancels it
-    e->fade_patch = false;
-    e->eng_init[0] = 0;
-    const int nb = std::min(coeff_blocks, e->B);
     const FilterRows rows = matrix_rows(e, coeffs, nullptr, length);
-    int rc = check_rows(e, rows, (size_t)nb * e->L, scale);
-    if (rc == BFIR_OK) rc = load_filters(e, e->H, 0, rows, nb, scale);
-    if (rc != BFIR_OK) return rc;
-    for (size_t n = 0; n < rows.taps.size(); n++) e->nblk[n] = coeffs[n] ? nb : 0;   // the MAC takes them by value (MatArgs.nblk)
-    return matrix_counts_set(e);
+    // as bfir_engine_set_coeff_at: a NaN / Inf tap is refused on the idle device, behind free_coeff()
+    return set_coeff_uniform(e, uniform_taps(e, rows, scale, coeff_blocks), nullptr, -1, false);
 }
 
 // The rows of a set call on a split engine, cut at every D_k: level k (0: the head) gets taps [D_k, D_(k+1)) of every row
@@ -1273,19 +1313,8 @@ static LBankArgs lbank_args(const bfir_engine *e, void *const (&dst)[BFIR_MAX_LE
 // there, and the host waits for it.  The device is idle; the counts are the caller's (the source's split).
 static int lbank_gather(bfir_engine *e, void *const (&dst)[BFIR_MAX_LEVELS], const std::vector<int> &ent, const std::vector<int> *list)
 {
-    const int W = 2 + BFIR_MAX_LEVELS;
-    std::vector<int> tab(W * ent.size(), 0);
-    for (size_t j = 0; j < ent.size(); j++) {
-        tab[W * j] = list ? (*list)[j] : (int)j; tab[W * j + 1] = ent[j];
-        for (int k = 0; k <= e->n_tail && ent[j] >= 0; k++) tab[W * j + 2 + k] = e->lbank_nb[(size_t)ent[j] * BFIR_MAX_LEVELS + k];
-    }
-    if (tab.size() > e->gather_ints) {
-        if (e->d_gather) (void)hipFree(e->d_gather);
-        e->d_gather = nullptr; e->gather_ints = 0;
-        HIP_TRY(hipMalloc((void **)&e->d_gather, sizeof(int) * tab.size()));
-        e->gather_ints = tab.size();
-    }
-    HIP_TRY(hipMemcpy(e->d_gather, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+    const int rc = upload_table(e->d_gather, e->gather_ints, coeff_tables::level_gather_table(list, ent, e->lbank_nb, e->n_tail + 1));
+    if (rc != BFIR_OK) return rc;
     LBankArgs a = lbank_args(e, dst);
     a.tab = e->d_gather; a.n_rows = (int)ent.size();
     if (launch_lbank_gather(a, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;   // checked by the entry point: not reached
@@ -1319,9 +1348,8 @@ static int set_coeff_split(bfir_engine *e, const SplitSource &src)
             if (rc != BFIR_OK) return rc;
         }
         l->nblk = s.nb;
-        // the matrix MAC takes the counts by value (MatArgs.nblk), k_mac_mimo from the level's table (the device is idle)
-        if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
-        else if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->nblk.size(), hipMemcpyHostToDevice));
+        rc = upload_counts(l, false);
+        if (rc != BFIR_OK) return rc;
     }
     if (src.ent) { rc = lbank_gather(e, gather, *src.ent, nullptr); if (rc != BFIR_OK) return rc; }
     return split_counts_set(e, sp);
@@ -1443,31 +1471,10 @@ static int set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_coeff
     if (e->n_eng > 1 || e->d_dither_tab) return BFIR_ERR_UNSUPPORTED;   // batches; HP-TPDF dither (a recursion over the output samples)
     if (e->nup) return BFIR_ERR_UNSUPPORTED;                            // two-level engines do not fade
     if (!coeffs || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
-    int rc = check_fade_args(e, fade_blocks);
+    const int rc = check_fade_args(e, fade_blocks);
     if (rc != BFIR_OK) return rc;
-    const int nb = std::min(coeff_blocks, e->B);
     const FilterRows rows = e->matrix ? matrix_rows(e, coeffs, nullptr, length) : diagonal_rows(e, coeffs, n_coeffs, length);
-    // a NaN / Inf tap is refused before anything is uploaded: the engine keeps running the old set
-    rc = check_rows(e, rows, (size_t)nb * e->L, scale);
-    if (rc != BFIR_OK) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    // queued work may still read what was H before the last fade's swap: H2 is written only when the device is idle
-    HIP_TRY(hipDeviceSynchronize());
-    rc = fade_prepare(e, (int)rows.taps.size());
-    if (rc == BFIR_OK) rc = load_filters(e, e->H2, 0, rows, nb, scale);
-    if (rc != BFIR_OK) return rc;
-    e->nblk2.assign(e->nblk.size(), 0);
-    for (size_t n = 0; n < rows.taps.size(); n++) e->nblk2[n] = (e->matrix && !coeffs[n]) ? 0 : nb;
-    if (!e->matrix) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->C, hipMemcpyHostToDevice));
-    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->nblk2.size(), hipMemcpyHostToDevice));
-    if (e->matrix && e->pair_cap) {
-        // no channel pairs around an unread input, per set: the fade's forward transforms take the pair path only if every
-        // input is read under BOTH sets; after the fade the new set decides
-        e->pair_new = every_input_read(e, [&](int, int n) { return e->nblk2[n]; });
-        matrix_take_path(e, e->pair_new && every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
-    }
-    fade_begin(e, fade_blocks);
-    return BFIR_OK;
+    return set_coeff_uniform(e, uniform_taps(e, rows, scale, coeff_blocks), nullptr, fade_blocks);
 }
 
 extern "C" int bfir_engine_set_coeff_fade(bfir_engine *e, const void *const *coeffs, int n_coeffs, int length,
@@ -1497,42 +1504,42 @@ struct PairList {
 };
 }
 
-// What both pairs calls ask of their list; host arithmetic alone.
-static int pairs_list(const bfir_engine *e, int n_pairs, const int *outputs, const int *inputs, const void *const *coeffs, int length,
-                      int coeff_blocks, PairList &pl)
+// What every pairs call with taps asks of its list; host arithmetic alone.  Every listed filter has its own lengths[k] taps,
+// or (lengths == nullptr) all have `length`; a NULL has none.
+static int pairs_list(const bfir_engine *e, int n_pairs, const int *outputs, const int *inputs, const void *const *coeffs,
+                      const int *lengths, int length, PairList &pl)
 {
-    if (!outputs || !inputs || !coeffs || n_pairs < 1 || length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
-    std::vector<char> listed((size_t)e->Co * e->C, 0);
+    if (!outputs || !inputs || !coeffs || n_pairs < 1) return BFIR_ERR_ARG;
+    const int rc = coeff_tables::list_rows(e->Co, e->C, n_pairs, outputs, inputs, pl.row);
+    if (rc != BFIR_OK) return rc;
     pl.rows = FilterRows((size_t)n_pairs);
-    pl.row.resize((size_t)n_pairs);
     for (int k = 0; k < n_pairs; k++) {
-        if (outputs[k] < 0 || outputs[k] >= e->Co || inputs[k] < 0 || inputs[k] >= e->C) return BFIR_ERR_ARG;
-        const int n = outputs[k] * e->C + inputs[k];
-        if (listed[n]) return BFIR_ERR_ARG;                     // the same pair twice
-        listed[n] = 1;
-        pl.row[k] = n; pl.rows.taps[k] = coeffs[k]; pl.rows.len[k] = coeffs[k] ? length : 0;
+        pl.rows.taps[k] = coeffs[k];
+        pl.rows.len[k] = !coeffs[k] ? 0 : lengths ? lengths[k] : length;
     }
     return BFIR_OK;
 }
 
-// The listed filters into Hdst (H, or H2 holding a copy of H), nb partitions each as load_filters gives them; the row of a
-// removed path reads as zeros, as bfir_engine_set_coeff_matrix leaves the row of a NULL.  The spectrum of a row does not
-// depend on the rows transformed with it (one workgroup per row and partition, k_fwd's planar form), so row by row gives
-// the bytes of the whole matrix in one call.
-static int load_pairs(bfir_engine *e, void *Hdst, const PairList &pl, int nb, double scale)
+// The listed rows of a level (a uniform engine: itself) into Hdst (H, or H2 holding a copy of H): row j of `rows` with nb[j]
+// partitions, as load_filters gives them, to row list[j], on the stream that owns every write to the level's store.  A row
+// without partitions (a removed path; a filter that does not reach the level) is cleared, as a whole-matrix call leaves the
+// row of a NULL.  The spectrum of a row does not depend on the rows transformed with it (one workgroup per row and
+// partition, k_fwd's planar form), so row by row gives the bytes of the whole matrix in one call.
+static int load_listed_rows(bfir_engine *l, void *Hdst, const FilterRows &rows, const std::vector<int> &nb,
+                            const std::vector<int> &list, double scale)
 {
-    const size_t row_bytes = (size_t)e->B * cbuf_bytes(e);
-    for (size_t k = 0; k < pl.row.size(); k++) {
-        if (!pl.rows.taps[k]) {   // on the stream that owns every write to the store
-            HIP_TRY(hipMemsetAsync((char *)Hdst + (size_t)pl.row[k] * row_bytes, 0, row_bytes, e->stream));
+    const size_t row_bytes = (size_t)l->B * cbuf_bytes(l);
+    for (size_t j = 0; j < list.size(); j++) {
+        if (nb[j] == 0) {
+            HIP_TRY(hipMemsetAsync((char *)Hdst + (size_t)list[j] * row_bytes, 0, row_bytes, l->stream));
             continue;
         }
         FilterRows one(1);
-        one.taps[0] = pl.rows.taps[k]; one.len[0] = pl.rows.len[k];
-        const int rc = load_filters(e, Hdst, pl.row[k], one, nb, scale);
+        one.taps[0] = rows.taps[j]; one.len[0] = rows.len[j];
+        const int rc = load_filters(l, Hdst, list[j], one, nb[j], scale);
         if (rc != BFIR_OK) return rc;
     }
-    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipStreamSynchronize(l->stream));
     return BFIR_OK;
 }
 
@@ -1541,22 +1548,12 @@ extern "C" int bfir_engine_set_coeff_matrix_pairs(bfir_engine *e, int n_pairs, c
 {
     if (!e) return BFIR_ERR_ARG;
     if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
     PairList pl;
-    int rc = pairs_list(e, n_pairs, outputs, inputs, coeffs, length, coeff_blocks, pl);
+    const int rc = pairs_list(e, n_pairs, outputs, inputs, coeffs, nullptr, length, pl);
     if (rc != BFIR_OK) return rc;
     if (!bfir_engine_is_initialized(e)) return BFIR_ERR_STATE;   // nothing to patch
-    const int nb = std::min(coeff_blocks, e->B);
-    // a NaN / Inf tap is refused before anything is uploaded: the engine keeps its filters, and a fade goes on
-    rc = check_rows(e, pl.rows, (size_t)nb * e->L, scale);
-    if (rc != BFIR_OK) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    HIP_TRY(hipDeviceSynchronize());
-    e->fade_len = e->fade_pos = 0;                              // during a fade: a hard cut, the old set stays and is patched
-    e->fade_patch = false;
-    rc = load_pairs(e, e->H, pl, nb, scale);
-    if (rc != BFIR_OK) return rc;
-    for (size_t k = 0; k < pl.row.size(); k++) e->nblk[pl.row[k]] = coeffs[k] ? nb : 0;
-    return matrix_counts_set(e);
+    return set_coeff_uniform(e, uniform_taps(e, pl.rows, scale, coeff_blocks), &pl.row, -1);
 }
 
 extern "C" int bfir_engine_set_coeff_matrix_pairs_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
@@ -1566,56 +1563,14 @@ extern "C" int bfir_engine_set_coeff_matrix_pairs_fade(bfir_engine *e, int n_pai
     if (!e) return BFIR_ERR_ARG;
     if (!e->matrix || e->mlevels) return BFIR_ERR_UNSUPPORTED;
     if (e->n_eng > 1 || e->d_dither_tab) return BFIR_ERR_UNSUPPORTED;   // as every fade: HP-TPDF dither is a recursion over the output
+    if (length < 0 || coeff_blocks < 1) return BFIR_ERR_ARG;
     PairList pl;
-    int rc = pairs_list(e, n_pairs, outputs, inputs, coeffs, length, coeff_blocks, pl);
+    int rc = pairs_list(e, n_pairs, outputs, inputs, coeffs, nullptr, length, pl);
     if (rc == BFIR_OK) rc = check_fade_args(e, fade_blocks);
     if (rc != BFIR_OK) return rc;
-    const int nb = std::min(coeff_blocks, e->B);
-    rc = check_rows(e, pl.rows, (size_t)nb * e->L, scale);
-    if (rc != BFIR_OK) return rc;
-    HIP_TRY(hipSetDevice(e->device));
-    // queued work may still read what was H before the last fade's swap, or the table: both are written on an idle device
-    HIP_TRY(hipDeviceSynchronize());
-    const size_t P = (size_t)e->Co * e->C;
-    rc = fade_prepare(e, (int)P);
-    if (rc != BFIR_OK) return rc;
-    // the merged set: the whole store copied, then the listed rows -- the copy on the stream the rows are loaded on (a
-    // non-blocking stream: a copy on the null stream would not be ordered before them, nor waited for by the host), and
-    // complete before the first row is written
-    HIP_TRY(hipMemcpyAsync(e->H2, e->H, P * e->B * cbuf_bytes(e), hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    rc = load_pairs(e, e->H2, pl, nb, scale);
-    if (rc != BFIR_OK) return rc;
-    e->nblk2 = e->nblk;
-    for (size_t k = 0; k < pl.row.size(); k++) e->nblk2[pl.row[k]] = coeffs[k] ? nb : 0;
-    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->nblk2.size(), hipMemcpyHostToDevice));
-    // k_patch_pairs' table: per output its listed pairs in input order
-    std::vector<char> listed(P, 0);
-    for (int n : pl.row) listed[n] = 1;
-    std::vector<int> tab((size_t)e->Co + 1);
-    for (int o = 0; o < e->Co; o++) {
-        tab[o] = (int)(tab.size() - (e->Co + 1)) / 3;
-        for (int i = 0; i < e->C; i++) {
-            const int n = o * e->C + i;
-            if (listed[n]) { tab.push_back(i); tab.push_back(e->nblk2[n]); tab.push_back(e->nblk[n]); }
-        }
-    }
-    tab[e->Co] = (int)pl.row.size();
-    if (tab.size() > e->patch_ints) {
-        if (e->d_patch) (void)hipFree(e->d_patch);
-        e->d_patch = nullptr; e->patch_ints = 0;
-        HIP_TRY(hipMalloc((void **)&e->d_patch, sizeof(int) * tab.size()));
-        e->patch_ints = tab.size();
-    }
-    HIP_TRY(hipMemcpy(e->d_patch, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-    if (e->pair_cap) {   // set_coeff_fade's rule: channel pairs only while every input is read under BOTH sets
-        e->pair_new = every_input_read(e, [&](int, int n) { return e->nblk2[n]; });
-        matrix_take_path(e, e->pair_new && every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
-    }
-    fade_begin(e, fade_blocks);
-    e->fade_patch = true;
-    return BFIR_OK;
+    return set_coeff_uniform(e, uniform_taps(e, pl.rows, scale, coeff_blocks), &pl.row, fade_blocks);
 }
+
 
 // ---------------------------------------------------------------------------
 // coefficient banks of a uniform matrix or mimo engine: filters transformed once into a store of the engine's own row form
@@ -1710,117 +1665,29 @@ extern "C" int bfir_engine_bank_read(bfir_engine *e, int entry, int block, void 
 
 namespace {
 struct BankList {
-    std::vector<int> row;        // the rows of the store that are written: filter o C + i
+    std::vector<int> row;        // a pairs call: the rows of the store that are written, filter o C + i (else the whole store)
     std::vector<int> ent;        // the bank entry of each, or -1: no path
     std::vector<int> mix;        // a mix call: k_bank_mix's records, [rows][BFIR_BANK_MIX_REC] (ent is not used)
 };
 }
 
-// What the four set calls ask of their list (outputs == nullptr: the whole matrix, entries[o C + i]); host arithmetic alone.
-// filled: per entry of the bank, 0 = empty (bank_nb, or a multi-level engine's lbank_len).
-static int bank_list(const bfir_engine *e, const std::vector<int> &filled, int n, const int *outputs, const int *inputs,
-                     const int *entries, BankList &bl)
-{
-    const int n_ent = (int)filled.size();
-    std::vector<char> listed(outputs ? (size_t)e->Co * e->C : 0, 0);
-    bl.row.resize((size_t)n); bl.ent.resize((size_t)n);
-    for (int k = 0; k < n; k++) {
-        int r = k;
-        if (outputs) {
-            if (outputs[k] < 0 || outputs[k] >= e->Co || inputs[k] < 0 || inputs[k] >= e->C) return BFIR_ERR_ARG;
-            r = outputs[k] * e->C + inputs[k];
-            if (listed[r]) return BFIR_ERR_ARG;                 // the same pair twice
-            listed[r] = 1;
-        }
-        if (entries[k] < -1 || entries[k] >= n_ent) return BFIR_ERR_ARG;
-        bl.row[k] = r; bl.ent[k] = entries[k];
-    }
-    for (int en : bl.ent) if (en >= 0 && filled[en] == 0) return BFIR_ERR_STATE;       // an empty entry
-    return BFIR_OK;
-}
+static_assert(coeff_tables::kMixRec == BFIR_BANK_MIX_REC, "coeff_tables::mix_records writes k_bank_mix's records");
 
-// The same for the four mix calls: listed row k has the n_terms terms (entries[k n_terms + j], weights[k n_terms + j]).  Every
-// weight is converted once to the working precision; a term is live iff its entry is >= 0 and the converted weight is not
-// zero.  bl.mix gets k_bank_mix's records: the live terms compacted to the front in listed order, each with its entry's count,
-// and the row's count, the largest of them (no live term: 0, no path).  Every index and count the kernel uses is checked here.
-static int bank_mix_list(const bfir_engine *e, int n, const int *outputs, const int *inputs, int n_terms, const int *entries,
-                         const double *weights, BankList &bl)
+// The source's rows of Hdst (H, or H2) from the bank: the table goes up, ONE gather (k_bank_gather, or a mix call's
+// k_bank_mix) is queued on the stream that owns every write to the store, and the host waits for it.  The device is idle.
+static int bank_gather(bfir_engine *e, void *Hdst, const UniformSource &src, const std::vector<int> *list)
 {
-    const int n_ent = (int)e->bank_nb.size(), W = BFIR_BANK_MIX_REC;
-    std::vector<char> listed(outputs ? (size_t)e->Co * e->C : 0, 0);
-    bl.row.resize((size_t)n);
-    bl.mix.assign((size_t)n * W, 0);
-    for (int k = 0; k < n; k++) {
-        int r = k;
-        if (outputs) {
-            if (outputs[k] < 0 || outputs[k] >= e->Co || inputs[k] < 0 || inputs[k] >= e->C) return BFIR_ERR_ARG;
-            r = outputs[k] * e->C + inputs[k];
-            if (listed[r]) return BFIR_ERR_ARG;                 // the same pair twice
-            listed[r] = 1;
-        }
-        int *rec = &bl.mix[(size_t)k * W];
-        bl.row[k] = rec[0] = r;
-        for (int j = 0; j < n_terms; j++) {
-            const int en = entries[(size_t)k * n_terms + j];
-            const double w = weights[(size_t)k * n_terms + j];
-            if (en < -1 || en >= n_ent) return BFIR_ERR_ARG;    // live or not
-            if (!std::isfinite(w)) return BFIR_ERR_ARG;
-            unsigned long long bits;
-            bool zero;
-            if (e->s == 4) {
-                const float wf = (float)w;
-                if (!std::isfinite(wf)) return BFIR_ERR_ARG;    // infinite in the working precision
-                unsigned u; memcpy(&u, &wf, sizeof u);
-                bits = u; zero = wf == 0.0f;
-            } else {
-                memcpy(&bits, &w, sizeof bits); zero = w == 0.0;
-            }
-            if (en < 0 || zero) continue;
-            int *t = rec + 3 + 4 * rec[2]++;
-            t[0] = en; t[1] = e->bank_nb[en]; t[2] = (int)(unsigned)bits; t[3] = (int)(unsigned)(bits >> 32);
-            rec[1] = std::max(rec[1], t[1]);
-        }
-    }
-    for (int k = 0; k < n; k++) {
-        const int *rec = &bl.mix[(size_t)k * W];
-        for (int j = 0; j < rec[2]; j++) if (rec[4 + 4 * j] == 0) return BFIR_ERR_STATE;   // a live term names an empty entry
-    }
-    return BFIR_OK;
-}
-
-// The listed rows of Hdst (H, or H2) from the bank and their partition counts into cnt (nblk, or nblk2): the table goes up,
-// ONE gather (k_bank_gather, or a mix call's k_bank_mix) is queued on the stream that owns every write to the store, and the
-// host waits for it.  The device is idle.
-static int bank_gather(bfir_engine *e, void *Hdst, std::vector<int> &cnt, const BankList &bl)
-{
-    const bool mix = !bl.mix.empty();
-    std::vector<int> tab;
-    if (mix) {
-        tab = bl.mix;
-        for (size_t k = 0; k < bl.row.size(); k++) cnt[bl.row[k]] = tab[k * BFIR_BANK_MIX_REC + 1];
-    } else {
-        tab.reserve(3 * bl.row.size());
-        for (size_t k = 0; k < bl.row.size(); k++) {
-            const int nb = bl.ent[k] < 0 ? 0 : e->bank_nb[bl.ent[k]];
-            tab.push_back(bl.row[k]); tab.push_back(bl.ent[k]); tab.push_back(nb);
-            cnt[bl.row[k]] = nb;
-        }
-    }
-    if (tab.size() > e->gather_ints) {
-        if (e->d_gather) (void)hipFree(e->d_gather);
-        e->d_gather = nullptr; e->gather_ints = 0;
-        HIP_TRY(hipMalloc((void **)&e->d_gather, sizeof(int) * tab.size()));
-        e->gather_ints = tab.size();
-    }
-    HIP_TRY(hipMemcpy(e->d_gather, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-    if (mix) {
+    const std::vector<int> tab = src.mix ? *src.mix : coeff_tables::gather_table(list, *src.ent, e->bank_nb);
+    const int rc = upload_table(e->d_gather, e->gather_ints, tab);
+    if (rc != BFIR_OK) return rc;
+    if (src.mix) {
         BankMixArgs a;
-        a.bank = e->bank; a.dst = Hdst; a.tab = e->d_gather; a.n_rows = (int)bl.row.size();
+        a.bank = e->bank; a.dst = Hdst; a.tab = e->d_gather; a.n_rows = (int)(tab.size() / BFIR_BANK_MIX_REC);
         a.part_bytes = cbuf_bytes(e); a.row_bytes = (unsigned long long)e->B * a.part_bytes;
         if (launch_bank_mix(a, e->s, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;
     } else {
         BankArgs a;
-        a.bank = e->bank; a.dst = Hdst; a.tab = e->d_gather; a.n_rows = (int)bl.row.size();
+        a.bank = e->bank; a.dst = Hdst; a.tab = e->d_gather; a.n_rows = (int)src.ent->size();
         a.part_bytes = cbuf_bytes(e); a.row_bytes = (unsigned long long)e->B * a.part_bytes;
         if (launch_bank_gather(a, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;
     }
@@ -1829,77 +1696,115 @@ static int bank_gather(bfir_engine *e, void *Hdst, std::vector<int> &cnt, const 
     return BFIR_OK;
 }
 
-// The four calls.  pairs: a list (outputs, inputs, entries of n), else the whole matrix (entries[o C + i]); fade_blocks < 0:
-// the plain call.  The order of the refusals is that of the calls with taps, with the bank's own behind the arguments.
-// mix: the four mix calls, n_terms (entry, weight) terms per listed row in place of one entry; only the list and the kernel
-// of the gather differ, the fade, the patch table and the swap are the same code.
+// k_patch_pairs' table of one level (a uniform engine: itself) in its d_patch, for the listed rows and the counts of its two sets
+static int patch_table_set(bfir_engine *l, const std::vector<int> &list)
+{
+    return upload_table(l->d_patch, l->patch_ints, coeff_tables::patch_table(l->Co, l->C, list, l->nblk2, l->nblk));
+}
+
+// The front end of a uniform matrix engine's fade, its two sets' counts in nblk and nblk2: no channel pairs around an unread
+// input, per set.  The fade's forward transforms take the pair path only if every input is read under BOTH sets; after the
+// fade the new set decides (pair_new, fade_swap_sets).
+static void fade_front_end(bfir_engine *e)
+{
+    if (!e->matrix || !e->pair_cap) return;
+    e->pair_new = every_input_read(e, [&](int, int n) { return e->nblk2[n]; });
+    matrix_take_path(e, e->pair_new && every_input_read(e, [&](int, int n) { return e->nblk[n]; }));
+}
+
+// the three operations of a UniformSource: the finite check (taps alone), ...
+static int source_check(const bfir_engine *e, const UniformSource &src)
+{
+    return src.rows ? check_rows(e, *src.rows, (size_t)src.nb * e->L, src.scale) : BFIR_OK;
+}
+
+// ... the partition count of every row of the call (a diagonal engine: its zero rows past n_coeffs too, which are still
+// multiplied; a matrix NULL and a -1 entry: 0, no path; a mix: the largest live term's), ...
+static std::vector<int> source_counts(const bfir_engine *e, const UniformSource &src)
+{
+    std::vector<int> nb(src.rows ? src.rows->taps.size() : src.ent ? src.ent->size() : src.mix->size() / BFIR_BANK_MIX_REC);
+    for (size_t j = 0; j < nb.size(); j++)
+        nb[j] = src.rows ? (e->matrix && !src.rows->taps[j] ? 0 : src.nb)
+              : src.ent  ? coeff_tables::entry_count(e->bank_nb, (*src.ent)[j]) : (*src.mix)[j * BFIR_BANK_MIX_REC + 1];
+    return nb;
+}
+
+// ... and its rows (nb: their counts) written to Hdst, row j of the call to row list[j], or all of them (list == nullptr) to
+// the whole store: taps in one load_filters or row by row, entries and mixes in one gather.  Every write is queued on
+// e->stream, and the host has waited for the last of them.
+static int source_write(bfir_engine *e, const UniformSource &src, const std::vector<int> &nb, void *Hdst, const std::vector<int> *list)
+{
+    if (!src.rows) return bank_gather(e, Hdst, src, list);
+    if (!list) return load_filters(e, Hdst, 0, *src.rows, src.nb, src.scale);
+    return load_listed_rows(e, Hdst, *src.rows, nb, *list, src.scale);
+}
+
+// Every coefficient change of a uniform engine but the batch form (bfir_engine_set_coeff_at), its arguments checked by the
+// entry point: the rows of `src` replace the rows `list` of the filter store (nullptr: the whole store), at once
+// (fade_blocks < 0; the active set H is written) or over the next fade_blocks blocks (the second set H2 is).  A NaN / Inf tap
+// is refused before anything changes -- or (check_first = false: bfir_engine_set_coeff_matrix) on the idle device behind
+// free_coeff(), which leaves the engine without coefficients.
+static int set_coeff_uniform(bfir_engine *e, const UniformSource &src, const std::vector<int> *list, int fade_blocks, bool check_first)
+{
+    const bool fade = fade_blocks >= 0;
+    int rc = check_first ? source_check(e, src) : BFIR_OK;
+    if (rc != BFIR_OK) return rc;
+    HIP_TRY(hipSetDevice(e->device));
+    // queued work may still read the bank, what was H before the last fade's swap, or a table: all written on an idle device
+    HIP_TRY(hipDeviceSynchronize());
+    if (!fade) {
+        e->fade_len = e->fade_pos = 0;                          // a plain change during a fade cancels it: a hard cut, the old set
+        e->fade_patch = false;                                  // stays and (a list) is patched
+        if (!list) e->eng_init[0] = 0;                          // free_coeff(), brutefir.cpp:188
+        if (!check_first) rc = source_check(e, src);
+    } else {
+        rc = fade_prepare(e, (int)e->nblk.size());
+        // a list: the merged set is the whole store copied, then the listed rows, both on e->stream and so in order
+        if (rc == BFIR_OK && list)
+            HIP_TRY(hipMemcpyAsync(e->H2, e->H, e->nblk.size() * e->B * cbuf_bytes(e), hipMemcpyDeviceToDevice, e->stream));
+    }
+    if (rc != BFIR_OK) return rc;
+    const std::vector<int> nb = source_counts(e, src);
+    rc = source_write(e, src, nb, fade ? e->H2 : e->H, list);
+    if (rc != BFIR_OK) return rc;
+    std::vector<int> &cnt = fade ? e->nblk2 : e->nblk;
+    if (fade) { if (list) e->nblk2 = e->nblk; else e->nblk2.assign(e->nblk.size(), 0); }
+    for (size_t j = 0; j < nb.size(); j++) cnt[coeff_tables::dest_row(list, j)] = nb[j];
+    rc = upload_counts(e, fade);
+    if (rc != BFIR_OK) return rc;
+    if (!fade) return matrix_counts_set(e);
+    if (list) { rc = patch_table_set(e, *list); if (rc != BFIR_OK) return rc; }
+    fade_front_end(e);
+    fade_begin(e, fade_blocks);
+    e->fade_patch = list != nullptr;                            // behind fade_begin, which clears it
+    return BFIR_OK;
+}
+
+// The eight calls with bank entries.  pairs: a list (outputs, inputs, entries of n), else the whole matrix (entries[o C + i]);
+// fade_blocks < 0: the plain call; n_terms > 0: a mix call, n_terms (entry, weight) terms per row in place of one entry.  The
+// order of the refusals is that of the calls with taps, with the bank's own behind the arguments.
 static int set_coeff_bank(bfir_engine *e, bool pairs, int n, const int *outputs, const int *inputs, const int *entries,
                           bool fade, int fade_blocks, bool mix = false, int n_terms = 0, const double *weights = nullptr)
 {
     if (!e) return BFIR_ERR_ARG;
     if (!bank_kind(e)) return BFIR_ERR_UNSUPPORTED;
     if (fade && (e->n_eng > 1 || e->d_dither_tab)) return BFIR_ERR_UNSUPPORTED;   // as every fade
-    const int P = e->Co * e->C;
     if (!entries || (pairs && (!outputs || !inputs || n < 1))) return BFIR_ERR_ARG;
     if (mix && (!weights || n_terms < 1 || n_terms > BFIR_BANK_MIX_TERMS)) return BFIR_ERR_ARG;
     if (!e->bank) return BFIR_ERR_STATE;
     BankList bl;
-    int rc = mix ? bank_mix_list(e, pairs ? n : P, pairs ? outputs : nullptr, inputs, n_terms, entries, weights, bl)
-                 : bank_list(e, e->bank_nb, pairs ? n : P, pairs ? outputs : nullptr, inputs, entries, bl);
+    const std::vector<int> *list = pairs ? &bl.row : nullptr;
+    const int n_rows = pairs ? n : e->Co * e->C;
+    int rc = pairs ? coeff_tables::list_rows(e->Co, e->C, n, outputs, inputs, bl.row) : BFIR_OK;
+    if (rc == BFIR_OK) rc = mix ? coeff_tables::mix_records(e->bank_nb, e->s, list, n_rows, n_terms, entries, weights, bl.mix)
+                                : coeff_tables::check_entries(e->bank_nb, n_rows, entries, bl.ent);
     if (rc == BFIR_OK && fade) rc = check_fade_args(e, fade_blocks);
     if (rc != BFIR_OK) return rc;
     if (pairs && !bfir_engine_is_initialized(e)) return BFIR_ERR_STATE;   // nothing to patch
-    if (bl.row.size() > 65535) return BFIR_ERR_UNSUPPORTED;      // the gather's grid; a matrix has 64 x 64 rows at most
-    HIP_TRY(hipSetDevice(e->device));
-    // queued work may still read the store, what was H before the last fade's swap, or a table: all written on an idle device
-    HIP_TRY(hipDeviceSynchronize());
-    if (!fade) {
-        e->fade_len = e->fade_pos = 0;                          // a plain change during a fade cancels it: the old set stays
-        e->fade_patch = false;
-        if (!pairs) e->eng_init[0] = 0;                         // as bfir_engine_set_coeff_matrix
-        rc = bank_gather(e, e->H, e->nblk, bl);
-        if (rc != BFIR_OK) return rc;
-        return matrix_counts_set(e);
-    }
-    rc = fade_prepare(e, P);
-    if (rc != BFIR_OK) return rc;
-    if (pairs) {
-        // the merged set: the whole store copied, then the listed rows, both on e->stream and so in order
-        HIP_TRY(hipMemcpyAsync(e->H2, e->H, (size_t)P * e->B * cbuf_bytes(e), hipMemcpyDeviceToDevice, e->stream));
-        e->nblk2 = e->nblk;
-    } else {
-        e->nblk2.assign(e->nblk.size(), 0);
-    }
-    rc = bank_gather(e, e->H2, e->nblk2, bl);
-    if (rc != BFIR_OK) return rc;
-    if (e->mimo) HIP_TRY(hipMemcpy(e->d_nblk2, e->nblk2.data(), sizeof(int) * e->nblk2.size(), hipMemcpyHostToDevice));
-    if (pairs) {   // k_patch_pairs' table: per output its listed pairs in input order
-        std::vector<char> listed((size_t)P, 0);
-        for (int r : bl.row) listed[r] = 1;
-        std::vector<int> tab((size_t)e->Co + 1);
-        for (int o = 0; o < e->Co; o++) {
-            tab[o] = (int)(tab.size() - (e->Co + 1)) / 3;
-            for (int i = 0; i < e->C; i++) {
-                const int r = o * e->C + i;
-                if (listed[r]) { tab.push_back(i); tab.push_back(e->nblk2[r]); tab.push_back(e->nblk[r]); }
-            }
-        }
-        tab[e->Co] = (int)bl.row.size();
-        if (tab.size() > e->patch_ints) {
-            if (e->d_patch) (void)hipFree(e->d_patch);
-            e->d_patch = nullptr; e->patch_ints = 0;
-            HIP_TRY(hipMalloc((void **)&e->d_patch, sizeof(int) * tab.size()));
-            e->patch_ints = tab.size();
-        }
-        HIP_TRY(hipMemcpy(e->d_patch, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-    }
-    if (e->pair_cap) {   // set_coeff_fade's rule: channel pairs only while every input is read under BOTH sets
-        e->pair_new = every_input_read(e, [&](int, int r) { return e->nblk2[r]; });
-        matrix_take_path(e, e->pair_new && every_input_read(e, [&](int, int r) { return e->nblk[r]; }));
-    }
-    fade_begin(e, fade_blocks);
-    e->fade_patch = pairs;
-    return BFIR_OK;
+    if (n_rows > 65535) return BFIR_ERR_UNSUPPORTED;            // the gather's grid; a matrix has 64 x 64 rows at most
+    UniformSource src;
+    if (mix) src.mix = &bl.mix; else src.ent = &bl.ent;
+    return set_coeff_uniform(e, src, list, fade ? fade_blocks : -1);
 }
 
 extern "C" int bfir_engine_set_coeff_matrix_bank(bfir_engine *e, const int *entries)
@@ -2826,50 +2731,6 @@ static LevelSplit merged_counts(const bfir_engine *e, const LevelSplit &spl, con
     return sp;
 }
 
-// The listed rows' part of level l into Hdst (H, or H2 holding a copy of H), row by row on the stream that owns every write
-// to the level's store: the spectrum of a row does not depend on the rows transformed with it (load_pairs).  A listed
-// filter that does not reach the level gets its row cleared.
-static int load_level_pairs(bfir_engine *l, void *Hdst, const LevelSplit::Level &sl, const std::vector<int> &list, double scale)
-{
-    const size_t row_bytes = (size_t)l->B * cbuf_bytes(l);
-    for (size_t j = 0; j < list.size(); j++) {
-        if (sl.nb[j] == 0) {
-            HIP_TRY(hipMemsetAsync((char *)Hdst + (size_t)list[j] * row_bytes, 0, row_bytes, l->stream));
-            continue;
-        }
-        FilterRows one(1);
-        one.taps[0] = sl.rows.taps[j]; one.len[0] = sl.rows.len[j];
-        const int rc = load_filters(l, Hdst, list[j], one, sl.nb[j], scale);
-        if (rc != BFIR_OK) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(l->stream));
-    return BFIR_OK;
-}
-
-// k_patch_pairs' table of one level in its d_patch: per output its listed pairs in input order, (input, nb_new, nb_old)
-static int patch_table_set(bfir_engine *l, const std::vector<int> &list)
-{
-    std::vector<char> listed((size_t)l->Co * l->C, 0);
-    for (int n : list) listed[n] = 1;
-    std::vector<int> tab((size_t)l->Co + 1);
-    for (int o = 0; o < l->Co; o++) {
-        tab[o] = (int)(tab.size() - (l->Co + 1)) / 3;
-        for (int i = 0; i < l->C; i++) {
-            const int n = o * l->C + i;
-            if (listed[n]) { tab.push_back(i); tab.push_back(l->nblk2[n]); tab.push_back(l->nblk[n]); }
-        }
-    }
-    tab[l->Co] = (int)list.size();
-    if (tab.size() > l->patch_ints) {
-        if (l->d_patch) (void)hipFree(l->d_patch);
-        l->d_patch = nullptr; l->patch_ints = 0;
-        HIP_TRY(hipMalloc((void **)&l->d_patch, sizeof(int) * tab.size()));
-        l->patch_ints = tab.size();
-    }
-    HIP_TRY(hipMemcpy(l->d_patch, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-    return BFIR_OK;
-}
-
 // The crossfade of a two-level, multi-level or multi-level matrix engine: the split of set_coeff_split into H2 of every
 // level, the catch-up, and the head's fade as a uniform engine's.
 // list (bfir_engine_set_coeff_matrix_levels_pairs_fade): `rows` are the listed filters alone, row j the new filter list[j] =
@@ -2915,17 +2776,12 @@ static int set_coeff_split_fade(bfir_engine *e, const SplitSource &src, int fade
         const LevelSplit::Level &s = sp.lv[k];
         if (k > 0 && !e->lv_active[k - 1]) continue;
         l->nblk2 = s.nb;
-        if (list && src.ent) {
-            // every level's copy is queued on the stream of the gather, which is so ordered behind all of them
-            HIP_TRY(hipMemcpyAsync(l->H2, l->H, n_rows * l->B * cbuf_bytes(l), hipMemcpyDeviceToDevice, e->stream));
-            gather[k] = l->H2;
-            rc = patch_table_set(l, *list);
-            if (rc != BFIR_OK) return rc;
-        } else if (list) {
-            // the level's store copied on the stream its rows are loaded on, and complete before the first row is written
-            HIP_TRY(hipMemcpyAsync(l->H2, l->H, n_rows * l->B * cbuf_bytes(l), hipMemcpyDeviceToDevice, l->stream));
-            HIP_TRY(hipStreamSynchronize(l->stream));
-            rc = load_level_pairs(l, l->H2, spl.lv[k], *list, src.scale);
+        if (list) {
+            // the level's store copied on the stream that writes the listed rows and so ordered before them: the level's own
+            // where they are loaded, the head's where the one gather behind the loop copies them
+            HIP_TRY(hipMemcpyAsync(l->H2, l->H, n_rows * l->B * cbuf_bytes(l), hipMemcpyDeviceToDevice, src.ent ? e->stream : l->stream));
+            if (src.ent) gather[k] = l->H2;
+            else rc = load_listed_rows(l, l->H2, spl.lv[k].rows, spl.lv[k].nb, *list, src.scale);
             if (rc == BFIR_OK) rc = patch_table_set(l, *list);
             if (rc != BFIR_OK) return rc;
         } else if (s.nb_max > 0) {
@@ -2938,9 +2794,8 @@ static int set_coeff_split_fade(bfir_engine *e, const SplitSource &src, int fade
             HIP_TRY(hipMemset(l->H2, 0, n_rows * l->B * cbuf_bytes(l)));
             if (!e->matrix) l->nblk2.assign(n_rows, 1);
         }
-        // the matrix MAC takes the counts by value (MatArgs.nblk), k_mac_mimo and k_wduo from the level's second table
-        if (!e->matrix) HIP_TRY(hipMemcpy(l->d_nblk2, l->nblk2.data(), sizeof(int) * l->C, hipMemcpyHostToDevice));
-        else if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk2, l->nblk2.data(), sizeof(int) * l->nblk2.size(), hipMemcpyHostToDevice));
+        rc = upload_counts(l, true);
+        if (rc != BFIR_OK) return rc;
     }
     if (src.ent) { rc = lbank_gather(e, gather, *src.ent, list); if (rc != BFIR_OK) return rc; }
     if (e->matrix) {
@@ -3019,19 +2874,9 @@ extern "C" int bfir_engine_set_coeff_matrix_levels_fade(bfir_engine *e, const vo
 static int pairs_list_levels(const bfir_engine *e, int n_pairs, const int *outputs, const int *inputs, const void *const *coeffs,
                              const int *lengths, PairList &pl)
 {
-    if (!outputs || !inputs || !coeffs || !lengths || n_pairs < 1) return BFIR_ERR_ARG;
-    std::vector<char> listed((size_t)e->Co * e->C, 0);
-    pl.rows = FilterRows((size_t)n_pairs);
-    pl.row.resize((size_t)n_pairs);
-    for (int k = 0; k < n_pairs; k++) {
-        if (outputs[k] < 0 || outputs[k] >= e->Co || inputs[k] < 0 || inputs[k] >= e->C) return BFIR_ERR_ARG;
-        const int n = outputs[k] * e->C + inputs[k];
-        if (listed[n]) return BFIR_ERR_ARG;                     // the same pair twice
-        listed[n] = 1;
-        if (coeffs[k] && lengths[k] < 0) return BFIR_ERR_ARG;
-        pl.row[k] = n; pl.rows.taps[k] = coeffs[k]; pl.rows.len[k] = coeffs[k] ? lengths[k] : 0;
-    }
-    return check_split_lengths(e, pl.rows);
+    if (!lengths) return BFIR_ERR_ARG;
+    const int rc = pairs_list(e, n_pairs, outputs, inputs, coeffs, lengths, 0, pl);
+    return rc != BFIR_OK ? rc : check_split_lengths(e, pl.rows);   // no length negative, none past the taps the levels hold
 }
 
 // The listed rows (row j of the source is filter list[j] = o C + i, the list checked) of the active set replaced on every level
@@ -3054,10 +2899,11 @@ static int set_pairs_split(bfir_engine *e, const SplitSource &src, const std::ve
         // before the first listed row goes in, as load_filters leaves the rows of the whole matrix
         if (nb_old == 0 && sp.lv[k].nb_max > 0) HIP_TRY(hipMemset(l->H, 0, l->nblk.size() * l->B * cbuf_bytes(l)));
         if (src.ent) gather[k] = l->H;                          // a listed entry that does not reach the level: its row cleared, as below
-        else rc = load_level_pairs(l, l->H, spl.lv[k], list, src.scale);
+        else rc = load_listed_rows(l, l->H, spl.lv[k].rows, spl.lv[k].nb, list, src.scale);
         if (rc != BFIR_OK) return rc;
         l->nblk = sp.lv[k].nb;
-        if (l->mimo) HIP_TRY(hipMemcpy(l->d_nblk, l->nblk.data(), sizeof(int) * l->nblk.size(), hipMemcpyHostToDevice));
+        rc = upload_counts(l, false);
+        if (rc != BFIR_OK) return rc;
     }
     if (src.ent) { rc = lbank_gather(e, gather, *src.ent, &list); if (rc != BFIR_OK) return rc; }
     return split_counts_set(e, sp);
@@ -3211,13 +3057,14 @@ static int set_coeff_lbank(bfir_engine *e, bool pairs, int n, const int *outputs
     if (!entries || (pairs && (!outputs || !inputs || n < 1))) return BFIR_ERR_ARG;
     if (!e->bank) return BFIR_ERR_STATE;
     BankList bl;
-    const int rc = bank_list(e, e->lbank_len, pairs ? n : e->Co * e->C, pairs ? outputs : nullptr, inputs, entries, bl);
+    int rc = pairs ? coeff_tables::list_rows(e->Co, e->C, n, outputs, inputs, bl.row) : BFIR_OK;
+    if (rc == BFIR_OK) rc = coeff_tables::check_entries(e->lbank_len, pairs ? n : e->Co * e->C, entries, bl.ent);   // 0 = empty
     if (rc != BFIR_OK) return rc;
     // the gather's own limits (alignment, a partition of whole 16 bytes, rows, grid), before anything is touched or launched
     void *stores[BFIR_MAX_LEVELS] = {};
     for (int k = 0; k <= e->n_tail; k++) stores[k] = level(e, k)->H;
     LBankArgs ga = lbank_args(e, stores);
-    ga.n_rows = (int)bl.row.size();
+    ga.n_rows = (int)bl.ent.size();
     if (!lbank_gather_supported(ga)) return BFIR_ERR_UNSUPPORTED;
     SplitSource src;
     src.ent = &bl.ent;
