@@ -9,8 +9,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libbfir_hip.so")
-SOURCES = ["kernels.hip", "engine.hip", "stage.hip", "bigfft.hip", "bigconv.hip", "pair.hip", "quad.hip", "wide.hip", "dither.hip", "mac_sys.hip", "matrix.hip", "mimo.hip", "fade.hip", "nup.hip", "levels.hip", "lfade.hip", "mlevels.hip", "mfade.hip", "wduo.hip", "patch.hip", "wpatch.hip", "bank.hip", "bankmix.hip", "lbank.hip", "delay.hip", "resample.hip"]
-HEADERS = ["kernels.h", "fft_lds.h", "pair_io.h", "inv_back.h", "fade_blend.h", "mat_ops.h", "coeff_tables.h", os.path.join("..", "..", "include", "bfir_hip.h")]
+SOURCES = ["kernels.hip", "engine.hip", "stage.hip", "bigfft.hip", "bigconv.hip", "pair.hip", "quad.hip", "wide.hip", "dither.hip", "mac_sys.hip", "matrix.hip", "mimo.hip", "fade.hip", "nup.hip", "levels.hip", "lfade.hip", "mlevels.hip", "mfade.hip", "wduo.hip", "patch.hip", "wpatch.hip", "bank.hip", "bankmix.hip", "lbank.hip", "lbankmix.hip", "delay.hip", "resample.hip"]
+HEADERS = ["kernels.h", "fft_lds.h", "pair_io.h", "inv_back.h", "fade_blend.h", "mat_ops.h", "mix_ops.h", "coeff_tables.h", os.path.join("..", "..", "include", "bfir_hip.h")]
 # -ffp-contract=on: fuse only inside one source expression (the stage kernels rely on it);
 # -fno-slp-vectorize: packing the FFT butterflies into v_pk_* costs more moves than it saves
 # (the MAC kernel asks for v_pk_fma_f32 explicitly).

@@ -101,6 +101,10 @@ SIGNATURES = {
     "bfir_engine_set_coeff_matrix_levels_bank_fade": (_ci, [_vp, _pi, _ci]),
     "bfir_engine_set_coeff_matrix_levels_pairs_bank": (_ci, [_vp, _ci, _pi, _pi, _pi]),
     "bfir_engine_set_coeff_matrix_levels_pairs_bank_fade": (_ci, [_vp, _ci, _pi, _pi, _pi, _ci]),
+    "bfir_engine_set_coeff_matrix_levels_bank_mix": (_ci, [_vp, _ci, _pi, C.POINTER(_cd)]),
+    "bfir_engine_set_coeff_matrix_levels_bank_mix_fade": (_ci, [_vp, _ci, _pi, C.POINTER(_cd), _ci]),
+    "bfir_engine_set_coeff_matrix_levels_pairs_bank_mix": (_ci, [_vp, _ci, _pi, _pi, _ci, _pi, C.POINTER(_cd)]),
+    "bfir_engine_set_coeff_matrix_levels_pairs_bank_mix_fade": (_ci, [_vp, _ci, _pi, _pi, _ci, _pi, C.POINTER(_cd), _ci]),
     "bfir_engine_fade_remaining": (_ci, [_vp]),
     "bfir_engine_create_nup": (_vp, [_ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _ci, _pi]),
     "bfir_engine_set_coeff_nup": (_ci, [_vp, C.POINTER(_vp), _ci, _ci, _cd]),

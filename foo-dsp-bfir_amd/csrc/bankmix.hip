@@ -23,6 +23,7 @@
 // loads of every term that covers its offset, up to 2 x 4 x 16 bytes = 32 registers, before it forms its sums and makes one
 // 16-byte store per step.  Offsets are 64-bit.  No LDS, no scratch.
 #include "kernels.h"
+#include "mix_ops.h"
 
 #include <climits>
 
@@ -30,15 +31,6 @@ namespace bfir {
 
 constexpr int kMixLanes = BFIR_BANK_SPAN / 16;
 constexpr int kMixT = BFIR_BANK_MIX_TERMS;
-
-template <typename R> struct alignas(16) MixVec { R x[16 / sizeof(R)]; };
-
-__device__ inline float mix_weight(int lo, int, float) { return __int_as_float(lo); }
-__device__ inline double mix_weight(int lo, int hi, double) { return __hiloint2double(hi, lo); }
-__device__ inline float mix_mul(float a, float b) { return __fmul_rn(a, b); }
-__device__ inline double mix_mul(double a, double b) { return __dmul_rn(a, b); }
-__device__ inline float mix_add(float a, float b) { return __fadd_rn(a, b); }
-__device__ inline double mix_add(double a, double b) { return __dadd_rn(a, b); }
 
 template <typename R>
 __global__ __launch_bounds__(kMixLanes) void k_bank_mix(BankMixArgs a)

@@ -1,6 +1,7 @@
 // coeff_tables.h -- the host arithmetic that turns the integers a caller hands to a set call (pairs, bank entries, mix terms)
-// into the tables the kernels read: k_patch_pairs' table (patch.hip), k_bank_gather's (bank.hip), k_lbank_gather's (lbank.hip)
-// and k_bank_mix's records (bankmix.hip).  Every index and count a kernel takes from a table is checked here.
+// into the tables the kernels read: k_patch_pairs' table (patch.hip), k_bank_gather's (bank.hip), k_lbank_gather's (lbank.hip),
+// k_bank_mix's records (bankmix.hip) and k_lbank_mix's (lbankmix.hip).  Every index and count a kernel takes from a table is
+// checked here.
 //
 // Host only: no HIP header, no engine; plain ints and vectors in, vectors and BFIR_* codes out, so that a stand-alone program
 // can run it under the host sanitizers (tests/cpp/test_coeff_tables.cpp).  engine.hip is its one user in the library.
@@ -94,20 +95,17 @@ inline std::vector<int> level_gather_table(const std::vector<int> *list, const s
     return tab;
 }
 
-// k_bank_mix's records for the n rows of a mix call: row j has the n_terms terms (entries[j n_terms + t], weights[j n_terms +
-// t]).  Every weight is converted once to the working precision (s = 4: float, 8: double); a term is live iff its entry is >= 0
-// and the converted weight is not zero.  rec gets [n][kMixRec]: destination row, the row's count (the largest of its live
-// terms'; none live: 0, no path), the live terms, then the live terms compacted to the front in listed order, each (entry, its
-// count, the weight's bits low, high).  BFIR_ERR_ARG: an entry outside the bank, live or not, a weight that is not finite or
-// not finite in the working precision; then BFIR_ERR_STATE: a live term names an empty entry.
-inline int mix_records(const std::vector<int> &bank_nb, int s, const std::vector<int> *list, int n, int n_terms,
-                       const int *entries, const double *weights, std::vector<int> &rec)
+// The live terms of the n rows of a mix call: row j has the n_terms terms (entries[j n_terms + t], weights[j n_terms + t]) on a
+// bank of n_ent entries.  Every weight is converted once to the working precision (s = 4: float, 8: double); a term is live
+// iff its entry is >= 0 and the converted weight is not zero.  live gets [n][kLiveRec]: the live terms, then those terms
+// compacted to the front in listed order, each (entry, the weight's bits low, high).  BFIR_ERR_ARG: an entry outside the
+// bank, live or not, a weight that is not finite or not finite in the working precision.
+constexpr int kLiveRec = 1 + 3 * BFIR_BANK_MIX_TERMS;
+inline int live_terms(int n_ent, int s, int n, int n_terms, const int *entries, const double *weights, std::vector<int> &live)
 {
-    const int n_ent = (int)bank_nb.size();
-    rec.assign((size_t)std::max(n, 0) * kMixRec, 0);
+    live.assign((size_t)std::max(n, 0) * kLiveRec, 0);
     for (int j = 0; j < n; j++) {
-        int *r = &rec[(size_t)j * kMixRec];
-        r[0] = dest_row(list, (size_t)j);
+        int *r = &live[(size_t)j * kLiveRec];
         for (int t = 0; t < n_terms; t++) {
             const int en = entries[(size_t)j * n_terms + t];
             const double w = weights[(size_t)j * n_terms + t];
@@ -124,14 +122,76 @@ inline int mix_records(const std::vector<int> &bank_nb, int s, const std::vector
                 memcpy(&bits, &w, sizeof bits); zero = w == 0.0;
             }
             if (en < 0 || zero) continue;
-            int *term = r + 3 + 4 * r[2]++;
-            term[0] = en; term[1] = bank_nb[en]; term[2] = (int)(unsigned)bits; term[3] = (int)(unsigned)(bits >> 32);
+            int *term = r + 1 + 3 * r[0]++;
+            term[0] = en; term[1] = (int)(unsigned)bits; term[2] = (int)(unsigned)(bits >> 32);
+        }
+    }
+    return BFIR_OK;
+}
+
+// k_bank_mix's records for the n rows of a mix call (live_terms: the terms, the conversion, liveness).  rec gets [n][kMixRec]:
+// destination row, the row's count (the largest of its live terms'; none live: 0, no path), the live terms, then the live
+// terms compacted to the front in listed order, each (entry, its count, the weight's bits low, high).  BFIR_ERR_ARG: as
+// live_terms; then BFIR_ERR_STATE: a live term names an empty entry.
+inline int mix_records(const std::vector<int> &bank_nb, int s, const std::vector<int> *list, int n, int n_terms,
+                       const int *entries, const double *weights, std::vector<int> &rec)
+{
+    std::vector<int> live;
+    rec.assign((size_t)std::max(n, 0) * kMixRec, 0);
+    const int rc = live_terms((int)bank_nb.size(), s, n, n_terms, entries, weights, live);
+    if (rc != BFIR_OK) return rc;
+    for (int j = 0; j < n; j++) {
+        const int *lt = &live[(size_t)j * kLiveRec];
+        int *r = &rec[(size_t)j * kMixRec];
+        r[0] = dest_row(list, (size_t)j); r[2] = lt[0];
+        for (int t = 0; t < lt[0]; t++) {
+            int *term = r + 3 + 4 * t;
+            term[0] = lt[1 + 3 * t]; term[1] = bank_nb[term[0]]; term[2] = lt[2 + 3 * t]; term[3] = lt[3 + 3 * t];
             r[1] = std::max(r[1], term[1]);
         }
     }
     for (int j = 0; j < n; j++) {
         const int *r = &rec[(size_t)j * kMixRec];
         for (int t = 0; t < r[2]; t++) if (r[4 + 4 * t] == 0) return BFIR_ERR_STATE;   // a live term names an empty entry
+    }
+    return BFIR_OK;
+}
+
+// k_lbank_mix's records, the multi-level form of mix_records: the bank is one store per level (lbank_len: the taps of every
+// entry, 0 = empty; lbank_nb: [entry][BFIR_MAX_LEVELS] its partitions per level).  rec gets [n][kLevelMixRec]: destination
+// row, the live terms, then per live term (entry, the weight's bits low, high, its count on each of BFIR_MAX_LEVELS levels;
+// the levels the engine does not have: 0); the rest of a record is zeros.  nb gets [n][BFIR_MAX_LEVELS], the row's count on
+// every level: the largest of its live terms' there (none live: 0 everywhere, no path).  A live term may have count 0 on a
+// level its entry does not reach.  The refusals are mix_records', "empty" being lbank_len == 0.
+constexpr int kLevelMixTerm = 3 + BFIR_MAX_LEVELS;
+constexpr int kLevelMixRec = 32;
+static_assert(2 + BFIR_BANK_MIX_TERMS * kLevelMixTerm <= kLevelMixRec, "a record holds its terms");
+inline int level_mix_records(const std::vector<int> &lbank_len, const std::vector<int> &lbank_nb, int n_levels, int s,
+                             const std::vector<int> *list, int n, int n_terms, const int *entries, const double *weights,
+                             std::vector<int> &rec, std::vector<int> &nb)
+{
+    std::vector<int> live;
+    rec.assign((size_t)std::max(n, 0) * kLevelMixRec, 0);
+    nb.assign((size_t)std::max(n, 0) * BFIR_MAX_LEVELS, 0);
+    const int rc = live_terms((int)lbank_len.size(), s, n, n_terms, entries, weights, live);
+    if (rc != BFIR_OK) return rc;
+    for (int j = 0; j < n; j++) {
+        const int *lt = &live[(size_t)j * kLiveRec];
+        int *r = &rec[(size_t)j * kLevelMixRec];
+        r[0] = dest_row(list, (size_t)j); r[1] = lt[0];
+        for (int t = 0; t < lt[0]; t++) {
+            int *term = r + 2 + kLevelMixTerm * t;
+            term[0] = lt[1 + 3 * t]; term[1] = lt[2 + 3 * t]; term[2] = lt[3 + 3 * t];
+            for (int k = 0; k < n_levels && k < BFIR_MAX_LEVELS; k++) {
+                term[3 + k] = lbank_nb[(size_t)term[0] * BFIR_MAX_LEVELS + k];
+                int &c = nb[(size_t)j * BFIR_MAX_LEVELS + k];
+                c = std::max(c, term[3 + k]);
+            }
+        }
+    }
+    for (int j = 0; j < n; j++) {
+        const int *r = &rec[(size_t)j * kLevelMixRec];
+        for (int t = 0; t < r[1]; t++) if (lbank_len[r[2 + kLevelMixTerm * t]] == 0) return BFIR_ERR_STATE;   // a live term names an empty entry
     }
     return BFIR_OK;
 }

@@ -198,7 +198,8 @@ struct bfir_engine {
     // The bank of a multi-level matrix or mimo engine (bfir_engine_levels_bank_create): one such store per level, in `bank` of
     // the head and of every tail, [entries][blocks[k]][2 L_k], loaded through the level split (bfir_engine_levels_bank_load).
     // The head keeps every entry's tap count (0: empty) and its partitions on every level, [entry][BFIR_MAX_LEVELS]; its
-    // d_gather is k_lbank_gather's table (lbank.hip), [rows][2 + BFIR_MAX_LEVELS], for all levels of a call in one launch.
+    // d_gather is k_lbank_gather's table (lbank.hip), [rows][2 + BFIR_MAX_LEVELS], for all levels of a call in one launch
+    // (a mix call: k_lbank_mix's records, [rows][BFIR_LBANK_MIX_REC], lbankmix.hip).
     std::vector<int> lbank_len, lbank_nb;
     void *Yf[2] = {nullptr, nullptr};      // products with H2: [GCo][yf_blocks][N], one per chunk parity like Yb
     int yf_blocks = 0;
@@ -1262,14 +1263,16 @@ static int split_counts_set(bfir_engine *e, const LevelSplit &sp)
 }
 
 // Where the rows of a set call on a split engine come from: host taps (rows, scale), which every level uploads and
-// transforms, or entries of the engine's bank (bfir_engine_levels_bank_create; ent[j]: the entry of row j, -1: none), which
-// every level holds transformed already.  set_coeff_split, set_coeff_split_fade and set_pairs_split ask the source for its
-// checks and its split and are otherwise the same for both: where taps are loaded level by level, entries are marked for ONE
-// gather behind the loop (lbank_gather).
+// transforms; entries of the engine's bank (bfir_engine_levels_bank_create; ent[j]: the entry of row j, -1: none), which
+// every level holds transformed already; or weighted sums of entries (mix: k_lbank_mix's records, mix_nb: the rows' counts,
+// [row][BFIR_MAX_LEVELS], both of coeff_tables::level_mix_records).  set_coeff_split, set_coeff_split_fade and set_pairs_split
+// ask the source for its checks and its split and are otherwise the same for all three: where taps are loaded level by
+// level, entries and mixes are marked for ONE launch behind the loop (lbank_gather, lbank_mix_gather).
 namespace {
 struct SplitSource {
     const FilterRows *rows = nullptr; double scale = 1.0;
     const std::vector<int> *ent = nullptr;
+    const std::vector<int> *mix = nullptr, *mix_nb = nullptr;
 };
 }
 
@@ -1277,17 +1280,25 @@ static SplitSource taps_source(const FilterRows &rows, double scale) { SplitSour
 static int source_check_lengths(const bfir_engine *e, const SplitSource &src) { return src.rows ? check_split_lengths(e, *src.rows) : BFIR_OK; }
 static int source_check_rows(const bfir_engine *e, const SplitSource &src) { return src.rows ? check_rows(e, *src.rows, SIZE_MAX, src.scale) : BFIR_OK; }
 
+// the rows of the call
+static size_t source_size(const SplitSource &src)
+{
+    return src.rows ? src.rows->taps.size() : src.ent ? src.ent->size() : src.mix_nb->size() / BFIR_MAX_LEVELS;
+}
+
 // The split of a source.  Bank entries: counts only, what the host table holds since the entry was loaded; no FilterRows.
+// Mixes: the counts level_mix_records found, the largest of every row's live terms per level.
 static LevelSplit source_split(const bfir_engine *e, const SplitSource &src)
 {
     if (src.rows) return split_rows(e, *src.rows);
     LevelSplit sp;
+    const size_t n = source_size(src);
     for (int k = 0; k <= e->n_tail; k++) {
         LevelSplit::Level &s = sp.lv[k];
-        s.nb.assign(src.ent->size(), 0);
-        for (size_t j = 0; j < src.ent->size(); j++) {
-            const int en = (*src.ent)[j];
-            s.nb[j] = en < 0 ? 0 : e->lbank_nb[(size_t)en * BFIR_MAX_LEVELS + k];
+        s.nb.assign(n, 0);
+        for (size_t j = 0; j < n; j++) {
+            const int en = src.ent ? (*src.ent)[j] : -1;
+            s.nb[j] = src.mix_nb ? (*src.mix_nb)[j * BFIR_MAX_LEVELS + k] : en < 0 ? 0 : e->lbank_nb[(size_t)en * BFIR_MAX_LEVELS + k];
             s.nb_max = std::max(s.nb_max, s.nb[j]);
         }
     }
@@ -1323,6 +1334,38 @@ static int lbank_gather(bfir_engine *e, void *const (&dst)[BFIR_MAX_LEVELS], con
     return BFIR_OK;
 }
 
+static_assert(coeff_tables::kLevelMixRec == BFIR_LBANK_MIX_REC && coeff_tables::kLevelMixTerm == BFIR_LBANK_MIX_TERM,
+              "coeff_tables::level_mix_records writes k_lbank_mix's records");
+
+// k_lbank_mix's arguments: lbank_args' descriptors
+static LBankMixArgs lbank_mix_args(const bfir_engine *e, void *const (&dst)[BFIR_MAX_LEVELS])
+{
+    const LBankArgs g = lbank_args(e, dst);
+    LBankMixArgs a = {};
+    for (int k = 0; k < BFIR_LBANK_LEVELS; k++) a.lv[k] = g.lv[k];
+    return a;
+}
+
+// The same for a mix call: the records (their destination rows are in them) go up, ONE k_lbank_mix launch for all levels is
+// queued on e->stream, and the host waits for it.
+static int lbank_mix_gather(bfir_engine *e, void *const (&dst)[BFIR_MAX_LEVELS], const std::vector<int> &rec)
+{
+    const int rc = upload_table(e->d_gather, e->gather_ints, rec);
+    if (rc != BFIR_OK) return rc;
+    LBankMixArgs a = lbank_mix_args(e, dst);
+    a.tab = e->d_gather; a.n_rows = (int)(rec.size() / BFIR_LBANK_MIX_REC);
+    if (launch_lbank_mix(a, e->s, e->stream) != 0) return BFIR_ERR_UNSUPPORTED;   // checked by the entry point: not reached
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    HIP_TRY(hipGetLastError());
+    return BFIR_OK;
+}
+
+// the one launch of a source without taps
+static int source_gather(bfir_engine *e, void *const (&dst)[BFIR_MAX_LEVELS], const SplitSource &src, const std::vector<int> *list)
+{
+    return src.mix ? lbank_mix_gather(e, dst, *src.mix) : lbank_gather(e, dst, *src.ent, list);
+}
+
 // The filters of a two-level, multi-level or multi-level matrix engine, split at every D_k: taps [0, D_1) to the head,
 // [D_k, D_(k+1)) to level k.  Mid-stream every delay line is kept: the head takes the new filters from the next block,
 // level k from its next block that completes; what a level has already put into its time ring still plays.
@@ -1343,7 +1386,7 @@ static int set_coeff_split(bfir_engine *e, const SplitSource &src)
         bfir_engine *l = level(e, k);
         const LevelSplit::Level &s = sp.lv[k];
         if (s.nb_max > 0) {   // a level on which no filter has taps does no work at all (a matrix head: its MAC stores zeros)
-            if (src.ent) gather[k] = l->H;
+            if (!src.rows) gather[k] = l->H;
             else rc = load_filters(l, l->H, 0, s.rows, s.nb_max, src.scale);
             if (rc != BFIR_OK) return rc;
         }
@@ -1351,7 +1394,7 @@ static int set_coeff_split(bfir_engine *e, const SplitSource &src)
         rc = upload_counts(l, false);
         if (rc != BFIR_OK) return rc;
     }
-    if (src.ent) { rc = lbank_gather(e, gather, *src.ent, nullptr); if (rc != BFIR_OK) return rc; }
+    if (!src.rows) { rc = source_gather(e, gather, src, nullptr); if (rc != BFIR_OK) return rc; }
     return split_counts_set(e, sp);
 }
 
@@ -2767,7 +2810,7 @@ static int set_coeff_split_fade(bfir_engine *e, const SplitSource &src, int fade
     // queued work may still read what was H before the last fade's swap, and the catch-up below reads the delay lines: the
     // device is idle from here to the end of the call
     HIP_TRY(hipDeviceSynchronize());
-    const size_t n_rows = list ? (size_t)e->Co * e->C : src.rows ? src.rows->taps.size() : src.ent->size();
+    const size_t n_rows = list ? (size_t)e->Co * e->C : source_size(src);
     rc = fade_prepare(e, (int)n_rows);
     if (rc != BFIR_OK) return rc;
     void *gather[BFIR_MAX_LEVELS] = {};   // bank entries: the levels of the one gather behind the loop; a skipped level is not among them
@@ -2779,13 +2822,13 @@ static int set_coeff_split_fade(bfir_engine *e, const SplitSource &src, int fade
         if (list) {
             // the level's store copied on the stream that writes the listed rows and so ordered before them: the level's own
             // where they are loaded, the head's where the one gather behind the loop copies them
-            HIP_TRY(hipMemcpyAsync(l->H2, l->H, n_rows * l->B * cbuf_bytes(l), hipMemcpyDeviceToDevice, src.ent ? e->stream : l->stream));
-            if (src.ent) gather[k] = l->H2;
+            HIP_TRY(hipMemcpyAsync(l->H2, l->H, n_rows * l->B * cbuf_bytes(l), hipMemcpyDeviceToDevice, src.rows ? l->stream : e->stream));
+            if (!src.rows) gather[k] = l->H2;
             else rc = load_listed_rows(l, l->H2, spl.lv[k].rows, spl.lv[k].nb, *list, src.scale);
             if (rc == BFIR_OK) rc = patch_table_set(l, *list);
             if (rc != BFIR_OK) return rc;
         } else if (s.nb_max > 0) {
-            if (src.ent) gather[k] = l->H2;
+            if (!src.rows) gather[k] = l->H2;
             else rc = load_filters(l, l->H2, 0, s.rows, s.nb_max, src.scale);
             if (rc != BFIR_OK) return rc;
         } else {
@@ -2797,7 +2840,7 @@ static int set_coeff_split_fade(bfir_engine *e, const SplitSource &src, int fade
         rc = upload_counts(l, true);
         if (rc != BFIR_OK) return rc;
     }
-    if (src.ent) { rc = lbank_gather(e, gather, *src.ent, list); if (rc != BFIR_OK) return rc; }
+    if (!src.rows) { rc = source_gather(e, gather, src, list); if (rc != BFIR_OK) return rc; }
     if (e->matrix) {
         // Front end: a level pairs channels only while every input is read under BOTH sets (an input is read if any filter of
         // its column has taps on any level); after the fade the new set decides (fade_swap_sets, lfade_finish).  The head of an
@@ -2898,14 +2941,14 @@ static int set_pairs_split(bfir_engine *e, const SplitSource &src, const std::ve
         // a level the active set does not reach was not loaded by the set call (set_coeff_split): its store reads as zeros
         // before the first listed row goes in, as load_filters leaves the rows of the whole matrix
         if (nb_old == 0 && sp.lv[k].nb_max > 0) HIP_TRY(hipMemset(l->H, 0, l->nblk.size() * l->B * cbuf_bytes(l)));
-        if (src.ent) gather[k] = l->H;                          // a listed entry that does not reach the level: its row cleared, as below
+        if (!src.rows) gather[k] = l->H;                        // a listed entry that does not reach the level: its row cleared, as below
         else rc = load_listed_rows(l, l->H, spl.lv[k].rows, spl.lv[k].nb, list, src.scale);
         if (rc != BFIR_OK) return rc;
         l->nblk = sp.lv[k].nb;
         rc = upload_counts(l, false);
         if (rc != BFIR_OK) return rc;
     }
-    if (src.ent) { rc = lbank_gather(e, gather, *src.ent, &list); if (rc != BFIR_OK) return rc; }
+    if (!src.rows) { rc = source_gather(e, gather, src, &list); if (rc != BFIR_OK) return rc; }
     return split_counts_set(e, sp);
 }
 
@@ -3092,6 +3135,62 @@ extern "C" int bfir_engine_set_coeff_matrix_levels_pairs_bank_fade(bfir_engine *
                                                                    const int *inputs, const int *entries, int fade_blocks)
 {
     return set_coeff_lbank(e, true, n_pairs, outputs, inputs, entries, true, fade_blocks);
+}
+
+// The four mix calls (bfir_engine_set_coeff_matrix_levels_bank_mix, _bank_mix_fade, _pairs_bank_mix, _pairs_bank_mix_fade):
+// set_coeff_lbank with n_terms (entry, weight) terms per row in place of one entry, a SplitSource of mix records and ONE
+// k_lbank_mix launch (lbankmix.hip) for all levels.  The refusals of the list, the terms and the bank come first, then the
+// launch's own, then those of the call with taps in its own order.
+static int set_coeff_lbank_mix(bfir_engine *e, bool pairs, int n, const int *outputs, const int *inputs, int n_terms,
+                               const int *entries, const double *weights, bool fade, int fade_blocks)
+{
+    if (!e) return BFIR_ERR_ARG;
+    if (!e->mlevels) return BFIR_ERR_UNSUPPORTED;
+    if (!entries || !weights || (pairs && (!outputs || !inputs || n < 1))) return BFIR_ERR_ARG;
+    if (n_terms < 1 || n_terms > BFIR_BANK_MIX_TERMS) return BFIR_ERR_ARG;
+    if (!e->bank) return BFIR_ERR_STATE;
+    BankList bl;
+    std::vector<int> nb;
+    const std::vector<int> *list = pairs ? &bl.row : nullptr;
+    int rc = pairs ? coeff_tables::list_rows(e->Co, e->C, n, outputs, inputs, bl.row) : BFIR_OK;
+    if (rc == BFIR_OK) rc = coeff_tables::level_mix_records(e->lbank_len, e->lbank_nb, e->n_tail + 1, e->s, list,
+                                                            pairs ? n : e->Co * e->C, n_terms, entries, weights, bl.mix, nb);
+    if (rc != BFIR_OK) return rc;
+    // the launch's own limits (alignment, a partition of whole 16 bytes, rows, grid), before anything is touched or launched
+    void *stores[BFIR_MAX_LEVELS] = {};
+    for (int k = 0; k <= e->n_tail; k++) stores[k] = level(e, k)->H;
+    LBankMixArgs ma = lbank_mix_args(e, stores);
+    ma.n_rows = (int)(bl.mix.size() / BFIR_LBANK_MIX_REC);
+    if (!lbank_mix_supported(ma)) return BFIR_ERR_UNSUPPORTED;
+    for (int k = 0; k <= e->n_tail; k++) if (level(e, k)->s != e->s) return BFIR_ERR_UNSUPPORTED;   // one weight, one precision
+    SplitSource src;
+    src.mix = &bl.mix; src.mix_nb = &nb;
+    if (fade) return set_coeff_split_fade(e, src, fade_blocks, list);
+    return pairs ? set_pairs_split(e, src, bl.row) : set_coeff_split(e, src);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_bank_mix(bfir_engine *e, int n_terms, const int *entries, const double *weights)
+{
+    return set_coeff_lbank_mix(e, false, 0, nullptr, nullptr, n_terms, entries, weights, false, 0);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_bank_mix_fade(bfir_engine *e, int n_terms, const int *entries,
+                                                                 const double *weights, int fade_blocks)
+{
+    return set_coeff_lbank_mix(e, false, 0, nullptr, nullptr, n_terms, entries, weights, true, fade_blocks);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_pairs_bank_mix(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                                  int n_terms, const int *entries, const double *weights)
+{
+    return set_coeff_lbank_mix(e, true, n_pairs, outputs, inputs, n_terms, entries, weights, false, 0);
+}
+
+extern "C" int bfir_engine_set_coeff_matrix_levels_pairs_bank_mix_fade(bfir_engine *e, int n_pairs, const int *outputs,
+                                                                       const int *inputs, int n_terms, const int *entries,
+                                                                       const double *weights, int fade_blocks)
+{
+    return set_coeff_lbank_mix(e, true, n_pairs, outputs, inputs, n_terms, entries, weights, true, fade_blocks);
 }
 
 extern "C" int bfir_engine_fade_remaining_levels(const bfir_engine *e)

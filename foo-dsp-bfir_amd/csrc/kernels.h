@@ -319,6 +319,24 @@ struct LBankArgs {
 bool lbank_gather_supported(const LBankArgs &a);            // alignment, and the grid of the launch fits
 int launch_lbank_gather(LBankArgs a, hipStream_t s);        // 0, or -1 if !lbank_gather_supported(a) (nothing launched)
 
+// lbankmix.hip: k_lbank_mix<R>, k_lbank_gather's grid with k_bank_mix's body (bfir_engine_set_coeff_matrix_levels_bank_mix,
+// _bank_mix_fade, _pairs_bank_mix, _pairs_bank_mix_fade).  On every participating level k, row rec[0] of dst_k gets the sum of
+// the record's rec[1] <= BFIR_BANK_MIX_TERMS terms, each that level's bank entry times a weight in R, every product and every
+// add rounded on its own and the first product starting the sum; term t takes part in the partitions below its own count on
+// the level, rec[2 + 7 t + 3 + k], alone; where no term covers an offset the row gets zeros.  The host lists live terms only
+// (entry >= 0, weight != 0), in the caller's order.
+constexpr int BFIR_LBANK_MIX_TERM = 3 + BFIR_LBANK_LEVELS;  // words of a term: entry, the weight's bits in R (low, high), the count per level
+constexpr int BFIR_LBANK_MIX_REC = 32;                      // words of a record: row, live terms, the terms; the rest unused
+static_assert(2 + BFIR_BANK_MIX_TERMS * BFIR_LBANK_MIX_TERM <= BFIR_LBANK_MIX_REC, "a record holds its terms");
+struct LBankMixArgs {
+    LBankLevel lv[BFIR_LBANK_LEVELS];
+    unsigned end[BFIR_LBANK_LEVELS];                          // workgroups of a row up to and with level k (launch_lbank_mix sets them)
+    const int *tab;                                           // device [n_rows][BFIR_LBANK_MIX_REC]
+    int n_rows;
+};
+bool lbank_mix_supported(const LBankMixArgs &a);            // alignment, and the grid of the launch fits
+int launch_lbank_mix(LBankMixArgs a, int realsize, hipStream_t s);   // 0, or -1 if unsupported (nothing launched)
+
 // a11 + a12: inverse real FFT of Y[gc][t] (grouped layout, times in_scale),
 // first L samples to dst + gc*dst_ch_stride + t*L.
 struct InvArgs {

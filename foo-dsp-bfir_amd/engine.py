@@ -820,6 +820,36 @@ class BrutefirMatrixLevels(BrutefirMatrix):
         return self._lib.bfir_engine_set_coeff_matrix_levels_pairs_bank_fade(self._h, *self._pair_bank_args(pairs, entries),
                                                                              int(fade_blocks))
 
+    # Mixes over the levels bank: set_bank / fade_to_rows_bank / set_pairs_bank / fade_to_pairs_bank with, per row, a list of
+    # up to four (entry, weight) tuples (or None / [] = no path) in place of one entry, as set_coeff_bank_mix takes them.  The
+    # sums are formed on the device on every level in one kernel launch (k_lbank_mix); one term of weight 1.0 is the bank
+    # call.  The inherited set_coeff_bank_mix* methods, the calls of the uniform kinds, keep returning ERR_UNSUPPORTED.
+
+    def set_bank_mix(self, terms):
+        """bfir_engine_set_coeff_matrix_levels_bank_mix: terms[o][i] is the list of (entry, weight) of h_{o,i}.  On every
+        level every stored real is fl(w_1 h_1), then fl(. + fl(w_m h_m)) in listed order over the live terms (entry >= 0,
+        weight != 0 in the working precision) whose entry reaches the partition; the filter's partition count on a level is
+        the largest among its live terms there.  Returns 0 or an ERR_* code."""
+        assert len(terms) == self.n_out and all(len(r) == self.n_in for r in terms)
+        return self._lib.bfir_engine_set_coeff_matrix_levels_bank_mix(self._h, *self._mix_args([t for r in terms for t in r]))
+
+    def fade_to_rows_bank_mix(self, terms, fade_blocks):
+        """bfir_engine_set_coeff_matrix_levels_bank_mix_fade: fade_to_rows to the mixed set."""
+        assert len(terms) == self.n_out and all(len(r) == self.n_in for r in terms)
+        return self._lib.bfir_engine_set_coeff_matrix_levels_bank_mix_fade(
+            self._h, *self._mix_args([t for r in terms for t in r]), int(fade_blocks))
+
+    def set_pairs_bank_mix(self, pairs, terms):
+        """bfir_engine_set_coeff_matrix_levels_pairs_bank_mix: the mix terms[k] (None / [] = the path is removed) replaces
+        h_{o,i} for pairs[k] = (o, i) on every level; every other pair keeps its filter.  Returns 0 or an ERR_* code
+        (ERR_STATE while a fade is pending or running)."""
+        return self._lib.bfir_engine_set_coeff_matrix_levels_pairs_bank_mix(self._h, *self._pair_mix_args(pairs, terms))
+
+    def fade_to_pairs_bank_mix(self, pairs, terms, fade_blocks):
+        """bfir_engine_set_coeff_matrix_levels_pairs_bank_mix_fade: the same change, crossfaded as fade_to_pairs."""
+        return self._lib.bfir_engine_set_coeff_matrix_levels_pairs_bank_mix_fade(self._h, *self._pair_mix_args(pairs, terms),
+                                                                                 int(fade_blocks))
+
     def fade_remaining(self):
         """Head blocks of a pending or running fade_to_rows / fade_to_pairs still to be processed; 0 = none."""
         return self._lib.bfir_engine_fade_remaining_levels(self._h)

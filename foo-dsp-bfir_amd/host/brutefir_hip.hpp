@@ -338,6 +338,29 @@ public:
     {
         return m_e ? bfir_engine_set_coeff_matrix_levels_pairs_bank_fade(m_e, n_pairs, outputs, inputs, entries, fade_blocks) : -1;
     }
+    // The same four with up to BFIR_BANK_MIX_TERMS (entry, weight) terms per row in place of one entry: entries[k * n_terms + j]
+    // and weights[k * n_terms + j] belong to row k, and every level's row is the weighted sum of the entries' rows there, formed
+    // on the device (bfir_engine_set_coeff_matrix_levels_bank_mix, _bank_mix_fade, _pairs_bank_mix, _pairs_bank_mix_fade).
+    int set_coeff_matrix_levels_bank_mix(int n_terms, const int *entries, const double *weights)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_levels_bank_mix(m_e, n_terms, entries, weights) : -1;
+    }
+    int set_coeff_matrix_levels_bank_mix_fade(int n_terms, const int *entries, const double *weights, int fade_blocks)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_levels_bank_mix_fade(m_e, n_terms, entries, weights, fade_blocks) : -1;
+    }
+    int set_coeff_matrix_levels_pairs_bank_mix(int n_pairs, const int *outputs, const int *inputs, int n_terms, const int *entries,
+                                               const double *weights)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_levels_pairs_bank_mix(m_e, n_pairs, outputs, inputs, n_terms, entries, weights) : -1;
+    }
+    int set_coeff_matrix_levels_pairs_bank_mix_fade(int n_pairs, const int *outputs, const int *inputs, int n_terms,
+                                                    const int *entries, const double *weights, int fade_blocks)
+    {
+        return m_e ? bfir_engine_set_coeff_matrix_levels_pairs_bank_mix_fade(m_e, n_pairs, outputs, inputs, n_terms, entries, weights,
+                                                                             fade_blocks)
+                   : -1;
+    }
     // head blocks of such a fade still to be processed; 0 = none
     int fade_remaining_levels() { return m_e ? bfir_engine_fade_remaining_levels(m_e) : -1; }
 

@@ -485,8 +485,10 @@ int bfir_engine_set_coeff_matrix_pairs_bank_fade(bfir_engine *e, int n_pairs, co
  * running.  For _pairs_bank_mix BFIR_ERR_STATE: an engine without coefficients.
  * The calls wait for queued work, upload one table, launch k_bank_mix once on the engine's stream and wait for it; they
  * allocate nothing but that table when it grows (and, as every fade, the second set at the engine's first fade).
- * Out of scope: mixes on the multi-level kinds (BFIR_ERR_UNSUPPORTED there); a gain change that keeps a pair's current
- * entry without naming it; more than BFIR_BANK_MIX_TERMS terms; complex weights (phase or delay interpolation). */
+ * Out of scope: mixes on the multi-level kinds (BFIR_ERR_UNSUPPORTED there) -- theirs, over the bank of
+ * bfir_engine_levels_bank_*, are the bfir_engine_set_coeff_matrix_levels_*bank_mix* calls further below; a gain change that
+ * keeps a pair's current entry without naming it; more than BFIR_BANK_MIX_TERMS terms; complex weights (phase or delay
+ * interpolation). */
 #define BFIR_BANK_MIX_TERMS 4
 int bfir_engine_set_coeff_matrix_bank_mix(bfir_engine *e, int n_terms, const int *entries, const double *weights);
 int bfir_engine_set_coeff_matrix_bank_mix_fade(bfir_engine *e, int n_terms, const int *entries, const double *weights,
@@ -678,6 +680,54 @@ int bfir_engine_set_coeff_matrix_levels_pairs_bank(bfir_engine *e, int n_pairs, 
                                                    const int *entries);
 int bfir_engine_set_coeff_matrix_levels_pairs_bank_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
                                                         const int *entries, int fade_blocks);
+/* Bank mixes on the multi-level kinds: the four calls above with up to BFIR_BANK_MIX_TERMS terms (entry, weight) in place
+ * of one entry, on engines from bfir_engine_create_matrix_levels and bfir_engine_create_mimo_levels in both precisions.  The
+ * entries are those of the engine's levels bank (bfir_engine_levels_bank_create, _load).  The transform of every level is
+ * linear, so no transform runs: one kernel launch (k_lbank_mix) writes the listed rows of all levels.
+ * entries[k * n_terms + j] and weights[k * n_terms + j], j < n_terms <= BFIR_BANK_MIX_TERMS, belong to listed row k: k = o *
+ * n_inputs + i in the whole-matrix calls, the pair (outputs[k], inputs[k]) in the pairs calls -- the layout of the uniform
+ * mix calls (bfir_engine_set_coeff_matrix_bank_mix).
+ * The operation is k_bank_mix's, applied per level.  Every weight is converted once to the working precision R.  A term is
+ * LIVE iff its entry is >= 0 and its converted weight is not zero.  On level k, c_j,k is the partition count of a live
+ * term's entry on that level (bfir_engine_levels_bank_blocks), and the row's count there is c_k = max c_j,k over its live
+ * terms.  With j_1 < j_2 < ... the live terms with c_j,k > p, in listed order, every stored real of partition p < c_k is
+ *       r = fl(w_j1 * h_j1);  r = fl(r + fl(w_jm * h_jm)), m = 2, 3, ...
+ *   every multiply and every add rounded on its own in R (no fma), the first product starting the sum (no 0 + ..., a
+ *   product of -0 stays -0).  Partitions c_k .. blocks[k] - 1 are zeros.  A term whose entry does not reach level k, or is
+ *   shorter there than p, takes no part, and what its store holds past its count is never read.  A row without a live term
+ *   is no path: count 0 on every level, zeros; in a pairs call the path is removed.  Nothing is multiplied by zero.
+ * So n_terms = 1 with weight 1 writes every byte of the call above for the same entry, and a restatement in IEEE single or
+ * double arithmetic from bfir_engine_levels_bank_read is exact to the bit wherever no product or sum is subnormal.
+ * Everything else is the contract of the corresponding _levels_*bank* call above, word for word: the plain whole-matrix call
+ * cuts a fade and initialises the engine; the plain pairs call returns BFIR_ERR_STATE while a fade is pending or running; the
+ * fades refuse, per level, a new set that reaches a level the active set does not, "reaches" decided by the mixed rows'
+ * counts c_k; a newly reached level starts and a left one stops; the pairs fade keeps the merged-set semantics and the
+ * patched y_new, with nb_new = c_k; the front-end pairing rule, bfir_engine_fade_remaining_levels and bfir_engine_reset
+ * behave as there.
+ * All refusals come before the device is touched and change nothing, in this order.  BFIR_ERR_ARG: a null e.
+ * BFIR_ERR_UNSUPPORTED: any kind but the two.  BFIR_ERR_ARG: a null entries, weights, outputs or inputs; n_pairs < 1; n_terms
+ * outside 1 .. BFIR_BANK_MIX_TERMS.  BFIR_ERR_STATE: no bank.  BFIR_ERR_ARG: a pair outside the matrix; the same pair listed
+ * twice; an index outside -1 .. n_entries - 1, live or not; a weight that is NaN or infinite, or becomes infinite in the
+ * working precision.  BFIR_ERR_STATE: a live term names an empty entry (length 0; a dead term may name one).
+ * BFIR_ERR_UNSUPPORTED: a launch the kernel cannot make (a misaligned store, a partition that is not whole 16 bytes, more
+ * than 65535 rows, a grid past the launch limits) -- a launch is never skipped.  Then the refusals of the call with taps, in
+ * its own order: for the fade calls BFIR_ERR_ARG: fade_blocks < 1 or K L > 2^24, then BFIR_ERR_STATE: an engine without
+ * coefficients, a fade pending or running; for _pairs_bank_mix BFIR_ERR_STATE likewise; for the fade calls then
+ * BFIR_ERR_UNSUPPORTED: the mixed set reaches a level the active one does not, or a launch of the fade on an active level
+ * that does not fit its kernel's grid.
+ * Cost: the calls wait for queued work, upload ONE table (per listed row: the row, its live terms, and per term the entry,
+ * the weight and the count on every level) and the counts, launch k_lbank_mix once on the engine's stream for all levels
+ * and wait for it once.  They transform nothing and allocate nothing but the table when it grows (and, as every fade, the
+ * second set at the engine's first fade).
+ * The four uniform mix calls keep returning BFIR_ERR_UNSUPPORTED on the multi-level kinds, and these four on the uniform. */
+int bfir_engine_set_coeff_matrix_levels_bank_mix(bfir_engine *e, int n_terms, const int *entries, const double *weights);
+int bfir_engine_set_coeff_matrix_levels_bank_mix_fade(bfir_engine *e, int n_terms, const int *entries, const double *weights,
+                                                      int fade_blocks);
+int bfir_engine_set_coeff_matrix_levels_pairs_bank_mix(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                       int n_terms, const int *entries, const double *weights);
+int bfir_engine_set_coeff_matrix_levels_pairs_bank_mix_fade(bfir_engine *e, int n_pairs, const int *outputs, const int *inputs,
+                                                            int n_terms, const int *entries, const double *weights,
+                                                            int fade_blocks);
 /* Head blocks of a pending or running fade (fftw_convolver.cpp:275-321 over fade_blocks blocks) of an engine from
  * bfir_engine_create_nup, _levels or _matrix_levels still to be processed; 0 = none.  BFIR_ERR_UNSUPPORTED on every other kind
  * of engine. */
